@@ -16,10 +16,18 @@ full visibility => 800,000 observations PER GPU (weak scaling: N GPUs solve one 
 points sharded, cameras replicated, all-reduce of the reduced camera system every step).
 
 Prints ONE JSON line (rank 0).  `value` = observations x LM-iterations per second over the whole job
-(M_total * K / t / 1e6, "Mobs/s"); `lm_iters_per_s` = K / t is reported beside it, as are the
-residual+Jacobian kernel rates.  `roofline` is for the kernel with the largest share of a step;
-`cpu_baseline` times the reference's algorithm (oracle/sba_oracle.py: numpy model + scipy
-least_squares with the reference's exact arguments) on this host.
+(M_total * K / t / 1e6, "Mobs/s"); `lm_iters_per_s` = K / t and `ms_per_step` = t / K are reported beside it.
+A plain run does only that: set up, warm up, time the K steps, print.
+
+--full adds everything else, each in runs of its own after the timed steps: the residual+Jacobian kernel
+rates and per-kernel durations; `roofline` for the kernel with the largest share of a step; the f64
+engine on the same workload; the end-to-end drop-in call; `cpu_baseline`, which times the reference's
+algorithm (oracle/sba_oracle.py: numpy model + scipy least_squares with the reference's exact arguments)
+on this host.
+
+--dump-outputs DIR writes what the timed solve hands its caller after the last timed step (sba_lm_finish:
+cameras, points, report; plus the per-step cost log) as DIR/<name>.npy, float64.  The inputs are a
+seeded synthetic rig, identical from run to run for the same arguments.
 """
 from __future__ import annotations
 
@@ -133,14 +141,39 @@ def parse():
     ap.add_argument("--tangential", action="store_true", help="13-parameter camera rows (radial + tangential: BASELINE config 5)")
     ap.add_argument("--visibility", type=float, default=1.0, help="probability that a camera sees a point (1.0 = dense, BASELINE's shape)")
     ap.add_argument("--min-views", type=int, default=2, help="cameras every point keeps at least (the reference's example uses 4)")
-    ap.add_argument("--f64-record", default="auto", choices=["auto", "off"], help="also time the f64 engine (PySBA's default dtype) "
-                    "on the same workload and report it as the `f64` block (N=1, f32 runs only)")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
-    ap.add_argument("--e2e", default="auto", choices=["auto", "off"], help="also time the drop-in call PySBA(...).bundleAdjust(1e-4) "
-                    "end to end (upload included) on the same rig, f32 and f64 (N=1)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure per-kernel durations and rooflines, the f64 "
+                    "engine, the end-to-end drop-in call and the scipy CPU baseline (each switchable below); off: the headline alone")
+    ap.add_argument("--f64-record", default="auto", choices=["auto", "off"], help="with --full: also time the f64 engine (PySBA's default "
+                    "dtype) on the same workload and report it as the `f64` block (N=1, f32 runs only)")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"], help="with --full: time the reference's scipy solve on the host")
+    ap.add_argument("--e2e", default="auto", choices=["auto", "off"], help="with --full: also time the drop-in call "
+                    "PySBA(...).bundleAdjust(1e-4) end to end (upload included) on the same rig, f32 and f64 (N=1)")
     ap.add_argument("--cpu-points", type=int, default=0, help="points of the CPU baseline solve; 0 = the GPU workload's own point count "
                     "(16 x 50,000: about 2 minutes of scipy); pass e.g. 5000 for a short sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the cameras, points, report and per-step costs of the "
+                    "timed solve as DIR/<name>.npy (float64; rank 0, its own points)")
     return ap.parse_args()
+
+
+DUMP_BYTES_MAX = 60 * 1000 * 1000      # all arrays of --dump-outputs together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(d, cams, pts, rep, costs):
+    """What the timed solve returns to its caller after the last timed step, as float64 .npy files under `d`.
+    Points beyond the byte budget are replaced by a fixed, seeded sample of rows (`points_index.npy` names them)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"cameras": np.asarray(cams, dtype=np.float64),
+              "report": np.array([rep.cost, rep.initial_cost, rep.optimality, rep.step_norm, rep.lambda_], dtype=np.float64),
+              "cost_per_step": np.asarray(costs, dtype=np.float64)}
+    pts = np.asarray(pts, dtype=np.float64)
+    room = (DUMP_BYTES_MAX - sum(v.nbytes for v in arrays.values())) // (4 * 8)      # a sampled row: 3 coordinates + its index
+    if pts.nbytes > DUMP_BYTES_MAX - sum(v.nbytes for v in arrays.values()):
+        idx = np.sort(np.random.default_rng(0).choice(pts.shape[0], size=int(room), replace=False))
+        arrays["points_index"] = idx.astype(np.float64)
+        pts = pts[idx]
+    arrays["points"] = pts
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
 
 
 def algorithmic_bytes_per_obs(kernel, s, C, N, M):
@@ -335,7 +368,7 @@ def main():
         sc = torch.empty(sdist.NSCALARS, dtype=torch.float64, device="cuda")
 
         def run(iters, profile=False):
-            """`iters` LM iterations from the initial guess; returns (seconds, costs)."""
+            """`iters` LM iterations from the initial guess; returns (seconds, costs, (cameras, points, report) from sba_lm_finish)."""
             pr.set_params(x0)
             opts = pr.make_opts(ftol=0.0, xtol=0.0, gtol=0.0, max_iter=iters, always_relinearize=True, profile=profile)
             if not phase_api:
@@ -348,15 +381,17 @@ def main():
                 pr.lm_begin(opts)
                 barrier()
                 t0 = time.perf_counter()
-                pr.lm_run()
+                _, done = pr.lm_run()
                 barrier()
                 t1 = time.perf_counter()
+                if done != iters:
+                    raise SystemExit(f"bench.py: the solve stopped after {done} of {iters} LM iterations")
                 costs = [r.cost for r in pr.iteration_log()]
-                pr.lm_finish()
+                fin = pr.lm_finish()
                 barrier()
                 per_solve["lm_begin"] = (t0 - tb) * 1e6
                 per_solve["lm_finish"] = (time.perf_counter() - t1) * 1e6
-                return t1 - t0, costs
+                return t1 - t0, costs, fin
             # phase API (torch.distributed carries the exchanges): same timed region, the iterations alone
             barrier()
             tb = time.perf_counter()
@@ -374,45 +409,42 @@ def main():
                     sc_all = comm.all_gather_rows(sc)
                     pr.lm_decide_async(sc_all.data_ptr(), world)
                 status, done = pr.lm_poll()
+                if status >= 0:
+                    break
             barrier()
             t1 = time.perf_counter()
+            if done != iters:
+                raise SystemExit(f"bench.py: the solve stopped after {done} of {iters} LM iterations")
             costs = [r.cost for r in pr.iteration_log()]
-            pr.lm_finish()
+            fin = pr.lm_finish()
             barrier()
             per_solve["lm_begin"] = (t0 - tb) * 1e6
             per_solve["lm_finish"] = (time.perf_counter() - t1) * 1e6
-            return t1 - t0, costs
+            return t1 - t0, costs, fin
         return run
 
     run = make_runner(prob)
     if a.warmup > 0:
         run(a.warmup)
-    dt, costs = run(a.steps)
+    dt, costs, (cams_out, pts_out, rep_out) = run(a.steps)
     per_solve_main = dict(per_solve)
-    run(min(a.steps, 20), profile=True)      # separate pass with one HIP event pair per kernel class per step
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, cams_out, pts_out, rep_out, costs)
     t = torch.tensor([dt], dtype=torch.float64, device="cuda" if (world == 1 or dist.get_backend() == "nccl") else "cpu")
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
 
-    # kernel durations: LIVE over the timed region (one HIP event pair per kernel class per step on the
-    # engine's stream); residual / resjac are not part of a step and are timed back-to-back afterwards.
-    kt = prob.kernel_profile()
-    kt.update({k: prob.time_kernel(k, 20) for k in ("residual", "resjac")})
+    if a.full:
+        run(min(a.steps, 20), profile=True)      # separate pass with one HIP event pair per kernel class per step
+        # kernel durations: LIVE over the timed region (one HIP event pair per kernel class per step on the
+        # engine's stream); residual / resjac are not part of a step and are timed back-to-back afterwards.
+        kt = prob.kernel_profile()
+        kt.update({k: prob.time_kernel(k, 20) for k in ("residual", "resjac")})
     step_us = dt / a.steps * 1e6
     out = None
     if rank == 0:
         n = P * C
-        s = 4 if a.dtype == "f32" else 8
-        fused = kt["linearize_points"] == 0 and kt["linearize_cams"] == 0 and kt["schur"] > 0
-        roof = roofline_of_step(kt, a.dtype, P, C, Nloc, M_local, shape)
-        rj_bytes = algorithmic_bytes_per_obs("resjac", s, C, Nloc, M_local) * M_local
-        if P == 13:
-            rj_bytes += 4 * s * M_local          # two more camera columns of the 2 x P block
-        tb, tsrc = pmc_traffic_bytes("resjac", *shape)
-        rj = {"kernel": "k_resjac", "bound": "hbm", "achieved": rj_bytes / (kt["resjac"] * 1e-6) / 1e9, "peak": HBM_PEAK_GBS,
-              "unit": "GB/s", "frac": rj_bytes / (kt["resjac"] * 1e-6) / 1e9 / HBM_PEAK_GBS, "launch_us": kt["resjac"],
-              "algorithmic_bytes_per_launch": rj_bytes, "mobs_per_s": M_local / kt["resjac"], "traffic": tb, "traffic_source": tsrc}
         vis_txt = "full visibility" if a.visibility >= 1.0 else f"visibility {a.visibility:g} (>= {a.min_views} views per point)"
         out = {
             "metric": "LM iters/sec and residual+Jacobian Mobs/s at 16 cams x 50k points",
@@ -430,10 +462,18 @@ def main():
                                        "RCCL inside libsba_hip.so: per step 1 all-reduce of n(n+1)/2+3n+1 doubles + 1 all-gather of 8 doubles per rank"),
                        "exchange_doubles_per_step": (0 if world == 1 else n * n + 3 * n + 1 if phase_api else n * (n + 1) // 2 + 3 * n + 1)},
             "lm_iters_per_s": a.steps / dt,
-            "resjac_mobs_per_s": M_local / kt["resjac"],
-            "fused_linearize_mobs_per_s": M_local / (kt["schur"] if fused else (kt["linearize_points"] + kt["linearize_cams"])),
-            "linearize_fused_into_schur": bool(fused),
-            "kernel_us": kt, "step_us": step_us,
+        }
+        if a.full:
+            s = 4 if a.dtype == "f32" else 8
+            fused = kt["linearize_points"] == 0 and kt["linearize_cams"] == 0 and kt["schur"] > 0
+            out.update({
+                "resjac_mobs_per_s": M_local / kt["resjac"],
+                "fused_linearize_mobs_per_s": M_local / (kt["schur"] if fused else (kt["linearize_points"] + kt["linearize_cams"])),
+                "linearize_fused_into_schur": bool(fused),
+                "kernel_us": kt,
+            })
+        out.update({
+            "step_us": step_us,
             # the timed region is the K iterations (sba_lm_run); once per solve, outside it: sba_lm_begin (reset + cost of the initial
             # point) and sba_lm_finish (gradient at the returned point + download of cameras and points to pageable host memory)
             "timed_region": "K LM iterations (sba_lm_run) between sba_lm_begin and sba_lm_finish",
@@ -443,18 +483,27 @@ def main():
             "per_solve_us": per_solve_main,
             "ms_per_step_with_begin_and_finish": (dt + (per_solve_main.get("lm_begin", 0.0) + per_solve_main.get("lm_finish", 0.0)) * 1e-6) / a.steps * 1e3,
             "cost_first_last": [costs[0], costs[-1]] if costs else None,
-            "roofline": roof, "roofline_resjac": rj,
-        }
+        })
+        if a.full:
+            roof = roofline_of_step(kt, a.dtype, P, C, Nloc, M_local, shape)
+            rj_bytes = algorithmic_bytes_per_obs("resjac", s, C, Nloc, M_local) * M_local
+            if P == 13:
+                rj_bytes += 4 * s * M_local          # two more camera columns of the 2 x P block
+            tb, tsrc = pmc_traffic_bytes("resjac", *shape)
+            rj = {"kernel": "k_resjac", "bound": "hbm", "achieved": rj_bytes / (kt["resjac"] * 1e-6) / 1e9, "peak": HBM_PEAK_GBS,
+                  "unit": "GB/s", "frac": rj_bytes / (kt["resjac"] * 1e-6) / 1e9 / HBM_PEAK_GBS, "launch_us": kt["resjac"],
+                  "algorithmic_bytes_per_launch": rj_bytes, "mobs_per_s": M_local / kt["resjac"], "traffic": tb, "traffic_source": tsrc}
+            out.update({"roofline": roof, "roofline_resjac": rj})
     # the f64 engine on the same workload: PySBA's default dtype (the reference computes in f64), i.e. what an unmodified
     # calibrate_camera.py runs.  Outside the timed headline; same step definition, fewer steps.
-    if world == 1 and a.dtype == "f32" and a.f64_record != "off":
+    if a.full and world == 1 and a.dtype == "f32" and a.f64_record != "off":
         prob.close()
         prob = _native.Problem(rig["cams0"], shard["pts"], shard["uv"], shard["ci"], shard["pi_local"], dtype="f64",
                                device=local, stream=stream)
         run64 = make_runner(prob)
         k64 = min(a.steps, 20)
         run64(min(max(a.warmup, 1), 5))
-        dt64, costs64 = run64(k64)
+        dt64, costs64, _ = run64(k64)
         run64(k64, profile=True)
         kt64 = prob.kernel_profile()
         out["f64"] = {"dtype": "f64", "steps": k64, "ms_per_step": dt64 / k64 * 1e3, "lm_iters_per_s": k64 / dt64,
@@ -463,14 +512,14 @@ def main():
                       "roofline": roofline_of_step(kt64, "f64", P, C, Nloc, M_local, (C, Np, "f64", a.tangential, a.visibility)),
                       "note": "the drop-in class's default engine (LASERCALIB_SBA_DTYPE unset): same workload and step as the headline"}
     # end-to-end wall time of the drop-in call on the same rig (SURVEY 8(d) metric (1): "report both incl./excl." upload), N = 1
-    if world == 1 and rank == 0 and a.e2e != "off":
+    if a.full and world == 1 and rank == 0 and a.e2e != "off":
         prob.close()
         out["e2e"] = {dt_: e2e_block(rig, dt_) for dt_ in ("f32", "f64")}
         out["lm_iters_per_s_incl_upload"] = out["e2e"][a.dtype]["lm_iters_per_s_incl_upload"]
     # SBA_BENCH_COMPARE_IPC=1 (N > 1, opt-in): the same steps once more over the one-shot exchange through peer-mapped buffers
     # (csrc/sba_ipc.hpp) on a second handle, reported beside the headline as `ipc_exchange` -- the comparison of the two exchange
     # mechanisms on whatever node this runs on.  Off by default: the headline is the RCCL path BASELINE.json names.
-    if world > 1 and not use_ipc and os.environ.get("SBA_BENCH_COMPARE_IPC"):
+    if a.full and world > 1 and not use_ipc and os.environ.get("SBA_BENCH_COMPARE_IPC"):
         saved_phase = phase_api
         prob2 = _native.Problem(rig["cams0"], shard["pts"], shard["uv"], shard["ci"], shard["pi_local"], dtype=a.dtype,
                                 device=local, stream=stream)
@@ -480,7 +529,7 @@ def main():
         phase_api = False                      # the library's own loop
         run2 = make_runner(prob2)
         run2(max(a.warmup, 1))
-        dt2, costs2 = run2(a.steps)
+        dt2, costs2, _ = run2(a.steps)
         t2 = torch.tensor([dt2], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t2, op=dist.ReduceOp.MAX)
         dt2 = float(t2.item())
@@ -492,7 +541,7 @@ def main():
                                    "cost_first_last": [costs2[0], costs2[-1]] if costs2 else None,
                                    "note": "same workload and steps through sba_ipc_export / sba_ipc_attach instead of the headline's collectives"}
     if rank == 0:
-        if a.cpu_baseline != "off" and world == 1:
+        if a.full and a.cpu_baseline != "off" and world == 1:
             cpu_pts = a.cpu_points if a.cpu_points > 0 else Np
             cb = cpu_baseline(C, cpu_pts, rig_kw=rig_kw)
             out["cpu_baseline"] = cb
