@@ -225,6 +225,53 @@ typedef enum { SBA_LOSS_LINEAR = 0, SBA_LOSS_HUBER = 1, SBA_LOSS_SOFT_L1 = 2, SB
 int sba_set_fixed_points(sba_handle* h, const uint8_t* fixed_mask /*N bytes or NULL*/);
 int sba_set_robust_loss(sba_handle* h, int32_t loss /*sba_loss*/, double f_scale);
 
+/* ---------------------------------------------------------------- parameter covariance (Gauss-Newton, at the current parameters)
+ * sba_covariance: the covariance of the calibrated cameras and points under the problem the handle solves -- weighted residuals,
+ * the robust loss's IRLS row scaling sqrt(rho') when one is set (sba_set_robust_loss), anchored points (sba_set_fixed_points)
+ * excluded from the unknowns -- evaluated at the handle's current parameters (after sba_solve_lm: the optimum).  In cov(theta):
+ *   cameras   Sigma_cc = S^+,  S = U - sum_p W_p V_p^-1 W_p^T  the reduced camera system with UNDAMPED point blocks (lambda = 0)
+ *   points    Sigma_pp = V_p^-1 + V_p^-1 W_p^T Sigma_cc W_p V_p^-1              (3 x 3 per point)
+ * Gauge rank g (the dimension of the null space of S taken out by the inverse):
+ *   g = 0  when any point is anchored: Sigma_cc = S^-1 by a Cholesky factorisation.  The anchors must fix the datum: fewer
+ *          than 3 anchored points, or collinear ones, return SBA_ERR_INVALID.  If the factorisation still meets a
+ *          non-positive pivot, rep->info is set to its 1-based row and every output is NaN.
+ *   g = 7  with no anchor (the reference's default): the similarity gauge (3 rotation, 3 translation, 1 scale).  Its null
+ *          vectors Q (n x 7, orthonormalised) are built analytically from the camera rows (d rvec = -J_r^-1(rvec) omega,
+ *          d t = -R(rvec) tau + t s, intrinsics 0) and Sigma_cc = P (S + alpha Q Q^T)^-1 P, P = I - Q Q^T, alpha = mean diag S:
+ *          the Moore-Penrose pseudo-inverse of S in the raw units of the camera rows (the minimum-norm datum).
+ *          rep->gauge_residual = ||S Q||_F / (||S||_F ||Q||_F) on the device-formed S says how well Q spans the null space.
+ *   g = 0  with cams_fixed (cameras held: PySBA.bundleAdjust_nocam): Sigma_pp = V_p^-1, no camera output.
+ * Points seen by fewer than two distinct cameras (or with a singular V_p) constrain no camera: they are left out of S, their
+ * 3 x 3 block is NaN and they are counted in rep->n_points_degenerate.  Anchored points get a zero block.
+ * sigma2 = sum r~^2 / dof over the observations of non-degenerate points (r~: weighted residual; with a robust loss the term
+ * f_scale^2 rho(z), so sigma2 = 2 cost / dof), dof = 2 M' - (P C + 3 N_free - g) (M': those observations, N_free: non-anchored,
+ * non-degenerate points; cams_fixed: dof = 2 M' - 3 N_free).  opts->scale != 0 multiplies every output by sigma2.
+ * Outputs (host, any may be NULL): cam_full n x n (n = P C, row-major), cam_blocks C x P x P (the diagonal blocks), pt_cov
+ * N x 6 packed (xx, xy, xz, yy, yz, zz; NULL skips the point pass).  Always computed in float64, for either dtype.
+ * The handle is left as it was found: parameters, LM state and work buffers are untouched (private buffers, freed on return).
+ * A handle of a multi-rank job (sba_comm_init / sba_ipc_attach) returns SBA_ERR_UNSUPPORTED. */
+typedef struct {
+  int32_t cams_fixed;      /* 1: cameras held, points-only covariance (Sigma_pp = V_p^-1; PySBA.bundleAdjust_nocam) */
+  int32_t scale;           /* 1: multiply every output by sigma2                                                 */
+  int32_t reserved[6];
+} sba_cov_opts;
+typedef struct {
+  double  sigma2;              /* sum r~^2 / dof (NaN when dof <= 0)                                 */
+  int64_t dof;
+  int32_t gauge_rank;          /* g: 0 or 7                                                           */
+  int32_t n_points_degenerate; /* points seen by fewer than two cameras: NaN blocks, left out of S    */
+  int32_t info;                /* 0, or the 1-based row of the non-positive pivot (outputs are NaN)  */
+  int32_t n_points_anchored;
+  double  gauge_residual;      /* ||S Q||_F / (||S||_F ||Q||_F); 0 when g = 0                         */
+  double  seconds_device;      /* HIP-event time of the kernels alone: form + inverse + points below  */
+  double  seconds_form;        /* ... linearisation of every point and the undamped S                 */
+  double  seconds_inverse;     /* ... regularisation, factorisation, inverse, gauge projection        */
+  double  seconds_points;      /* ... camera blocks and the point pass                                */
+  double  seconds_total;       /* wall time of the whole call: host layout pass, uploads, kernels, read-back */
+} sba_cov_report;
+int sba_covariance(sba_handle* h, const sba_cov_opts* opts, double* cam_full /*n*n or NULL*/,
+                   double* cam_blocks /*C*P*P or NULL*/, double* pt_cov /*N*6 or NULL*/, sba_cov_report* rep);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

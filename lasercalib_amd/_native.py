@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = (
     "sba_get_gradient", "sba_get_transform", "sba_lm_get_step", "sba_ipc_export", "sba_ipc_attach", "sba_residual", "sba_residual_jacobian", "sba_solve_lm",
     "sba_lm_exchange_size", "sba_lm_begin", "sba_lm_linearize", "sba_lm_form_reduced",
     "sba_lm_solve_trial", "sba_lm_decide", "sba_lm_decide_async", "sba_lm_poll", "sba_lm_run", "sba_lm_finish", "sba_lm_get_log", "sba_time_kernel", "sba_get_kernel_profile",
-    "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss",
+    "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
 )
 
 
@@ -60,6 +60,38 @@ class LmIterLog(C.Structure):
     _fields_ = [("iteration", C.c_int32), ("accepted", C.c_int32), ("nfev", C.c_int64),
                 ("cost", C.c_double), ("cost_reduction", C.c_double), ("step_norm", C.c_double),
                 ("optimality", C.c_double), ("lambda_", C.c_double), ("rho", C.c_double)]
+
+
+class CovOpts(C.Structure):
+    _fields_ = [("cams_fixed", C.c_int32), ("scale", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class CovReport(C.Structure):
+    _fields_ = [("sigma2", C.c_double), ("dof", C.c_int64), ("gauge_rank", C.c_int32), ("n_points_degenerate", C.c_int32),
+                ("info", C.c_int32), ("n_points_anchored", C.c_int32), ("gauge_residual", C.c_double),
+                ("seconds_device", C.c_double), ("seconds_form", C.c_double), ("seconds_inverse", C.c_double),
+                ("seconds_points", C.c_double), ("seconds_total", C.c_double)]
+
+
+class Covariance:
+    """Result of Problem.covariance: camera blocks (C, P, P), optionally the full camera matrix (n, n) and the point blocks
+    (N, 3, 3), plus sigma2, dof, gauge_rank, n_points_degenerate, n_points_anchored, info, gauge_residual and the timings
+    (seconds_device = seconds_form + seconds_inverse + seconds_points, kernels only; seconds_total, the whole call)."""
+
+    def __init__(self, cameras, cameras_full, points, rep):
+        self.cameras, self.cameras_full, self.points = cameras, cameras_full, points
+        for name, _t in CovReport._fields_:
+            setattr(self, name, getattr(rep, name))
+
+    def camera_std(self):
+        """(C, P) standard deviations of the camera parameters."""
+        return np.sqrt(np.einsum("cii->ci", self.cameras))
+
+    def point_std(self):
+        """(N, 3) standard deviations of the point coordinates (NaN for points seen by fewer than two cameras)."""
+        if self.points is None:
+            raise ValueError("the point covariance was not computed (points=False)")
+        return np.sqrt(np.einsum("nii->ni", self.points))
 
 
 _lib = None
@@ -140,6 +172,7 @@ def load():
         "sba_ipc_attach": (C.c_int, [H, C.c_int32, C.c_int32, C.c_char_p]),
         "sba_set_fixed_points": (C.c_int, [H, C.c_void_p]),
         "sba_set_robust_loss": (C.c_int, [H, C.c_int32, C.c_double]),
+        "sba_covariance": (C.c_int, [H, C.POINTER(CovOpts), dp, dp, dp, C.POINTER(CovReport)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -303,6 +336,21 @@ class Problem:
         if code is None:
             raise ValueError("loss must be 'linear', 'huber', 'soft_l1' or 'cauchy'")
         _check(self._lib.sba_set_robust_loss(self._h, code, float(f_scale)), self._h)
+
+    # -- parameter covariance at the current parameters (sba_covariance, include/sba_hip.h)
+    def covariance(self, scale=True, full=False, points=True, cams_fixed=False):
+        """Gauss-Newton covariance of the cameras and points; returns a Covariance (see include/sba_hip.h for the gauge)."""
+        n = self.P * self.C
+        cams = np.empty((self.C, self.P, self.P))
+        cfull = np.empty((n, n)) if full else None
+        pts = np.empty((self.N, 6)) if points else None
+        rep = CovReport()
+        opts = CovOpts(1 if cams_fixed else 0, 1 if scale else 0, (C.c_int32 * 6)())
+        _check(self._lib.sba_covariance(self._h, C.byref(opts), _dptr(cfull), _dptr(cams), _dptr(pts), C.byref(rep)), self._h)
+        pcov = None
+        if pts is not None:
+            pcov = pts[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(self.N, 3, 3)
+        return Covariance(cams, cfull, pcov, rep)
 
     # -- lifetime
     def close(self):

@@ -260,6 +260,13 @@ int sba_set_robust_loss(sba_handle* h, int32_t loss, double f_scale) {
   return guarded(h, [&] { return h->eng->set_robust_loss(loss, f_scale); });
 }
 
+int sba_covariance(sba_handle* h, const sba_cov_opts* opts, double* cam_full, double* cam_blocks, double* pt_cov, sba_cov_report* rep) {
+  if (!h) return SBA_ERR_INVALID;
+  sba_cov_opts o{};
+  if (opts) o = *opts;
+  return guarded(h, [&] { return h->eng->covariance(&o, cam_full, cam_blocks, pt_cov, rep); });
+}
+
 int sba_time_kernel(sba_handle* h, const char* name, int32_t reps, double* mean_us_out) {
   if (!h || !name || !mean_us_out) return SBA_ERR_INVALID;
   return guarded(h, [&] { return h->eng->time_kernel(name, reps, mean_us_out); });

@@ -284,6 +284,7 @@ struct EngineBase {
   virtual int ipc_attach(int rank, int n_ranks, const uint8_t* handles) = 0;
   virtual int set_fixed_points(const uint8_t* mask) = 0;
   virtual int set_robust_loss(int loss, double f_scale) = 0;
+  virtual int covariance(const sba_cov_opts* o, double* cam_full, double* cam_blocks, double* pt_cov, sba_cov_report* rep) = 0;
 };
 
 }  // namespace sba_host

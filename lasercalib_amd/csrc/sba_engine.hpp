@@ -11,6 +11,7 @@
 #include "sba_schur_wide.hpp"
 #include "sba_schur_f64.hpp"
 #include "sba_ipc.hpp"
+#include "sba_covariance.hpp"
 
 namespace SBA_NS {
 using namespace sba_host;
@@ -2002,6 +2003,17 @@ struct Engine : EngineBase {
     loss_kind = loss;
     push_ptrs();
     return SBA_OK;
+  }
+
+  // ------------------------------------------------------------------ parameter covariance (sba_covariance.hpp)
+  int covariance(const sba_cov_opts* o, double* cam_full, double* cam_blocks, double* pt_cov, sba_cov_report* rep) override {
+    if (!uploaded) { err = "sba_upload has not been called"; return SBA_ERR_STATE; }
+    if (multi()) { err = "sba_covariance: a handle of a multi-rank job is not supported (sharded covariance)"; return SBA_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(device));
+    sync();
+    CovIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
+                has_fixed ? pt_fixed_mask.p : nullptr, RLoss<double>{loss_delta, loss_kind}};
+    return cov_run<T>(in, *o, cam_full, cam_blocks, pt_cov, rep, err);
   }
 
   // ------------------------------------------------------------------ small accessors of the C ABI

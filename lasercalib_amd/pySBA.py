@@ -311,6 +311,18 @@ class PySBA:
             log = list(log1) + list(log)
         return self._package(mode, cams_opt, pts_opt, rep, log, fvec, verbose)
 
+    def covariance(self, scale=True, points=True):
+        """Extension: Gauss-Newton covariance of ``cameraArray`` / ``points3D`` as they stand (after ``bundleAdjust``: at the
+        optimum), on the device.  The problem is built as ``bundleAdjust`` builds it (weights, anchors, loss, dtype, device).
+        Returns a ``_native.Covariance``: ``cameras`` (C, P, P), ``points`` (N, 3, 3) or None, ``sigma2``, ``dof``,
+        ``gauge_rank``, ``n_points_degenerate``, ``camera_std()``, ``point_std()``."""
+        cams = np.ascontiguousarray(self.cameraArray, dtype=np.float64)
+        pts = np.ascontiguousarray(self.points3D, dtype=np.float64)
+        with _native.Problem(cams, pts, self.points2D, self.cameraIndices, self.point2DIndices,
+                             weights=self._weights_or_none(), dtype=_env_dtype(), device=_env_device()) as prob:
+            self._apply_extensions(prob, pts.shape[0])
+            return prob.covariance(scale=scale, full=False, points=points)
+
     def _package(self, mode, cams_opt, pts_opt, rep, log, fvec, verbose):
         C_, N_ = cams_opt.shape[0], pts_opt.shape[0]
         if mode == _native.MODE_POINTS_ONLY:

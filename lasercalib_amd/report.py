@@ -40,6 +40,16 @@ def camera_table(sba) -> str:
     return "\n".join([head] + rows)
 
 
+def camera_uncertainty_table(sba, cov) -> str:
+    """``camera_table`` with the standard deviation of every parameter (``cov``: the result of ``PySBA.covariance``)."""
+    cams = np.asarray(sba.cameraArray, dtype=np.float64)
+    std = cov.camera_std()
+    cols = _COLS if cams.shape[1] == 11 else _COLS[:9] + ("p1", "p2") + _COLS[9:]
+    head = " cam " + " ".join(f"{c:>22s}" for c in cols[: cams.shape[1]])
+    rows = [f"{i:4d} " + " ".join(f"{v:11.5g} +-{s:8.2g}" for v, s in zip(row, srow)) for i, (row, srow) in enumerate(zip(cams, std))]
+    return "\n".join([head] + rows)
+
+
 def camera_extrinsics(sba) -> np.ndarray:
     """(C,4,4) matrices ``ex`` of sba_print.py:33-42: rotation block = R(-rotvec), translation = -R(-rotvec) t."""
     cams = np.asarray(sba.cameraArray, dtype=np.float64)
