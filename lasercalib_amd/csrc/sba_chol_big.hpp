@@ -20,8 +20,7 @@
 //                        (j,r)): the lower block (r,j) is still being read by the other workgroups of the launch.  Workgroup 0
 //                        publishes the inverse of the diagonal factor (Minv) and the factor's sub-blocks (Ld).
 //   k_chol_big_back_all<T>   b = last .. 0:  x_b = Minv_b^T y_b, y_t -= L(b,t)^T x_b, block row = workgroup, in one launch, and the LM
-//                        epilogue (trial cameras, predicted reduction, failure flag) by the block row that finishes last
-//                        (k_chol_big_back_init / k_chol_big_back: one launch per block, SBA_CHOL_BIG_BACK=launches).
+//                        epilogue (trial cameras, predicted reduction, failure flag) by the block row that finishes last.
 // Both forms share the 64 x 64 building block chol_big_factor64 (16 x 16 sub-blocks, the pivot chains of sba_chol_blocked.hpp).
 #pragma once
 #include "sba_chol_blocked.hpp"
@@ -35,8 +34,8 @@ constexpr int CHOLBIG_LDS_BLOCKS = 54;       // k_chol_big_step / k_chol_big_dag
 constexpr double CHOLBIG_RHS_DIAG = 1e300;  // diagonal entry of the appended rhs row: keeps the augmented matrix PD
 constexpr float CHOLBIG_RHS_DIAG_F32 = 1e30f;   // ... on f32 lanes (k_chol_big_dag<float>)
 
-__host__ __device__ inline int cholbig_rhs_row(int n) { return ((n + CB - 1) / CB) * CB; }
-__host__ __device__ inline int cholbig_npad(int n) { return ((cholbig_rhs_row(n) + 1 + BB - 1) / BB) * BB; }
+__host__ __device__ constexpr int cholbig_rhs_row(int n) { return ((n + CB - 1) / CB) * CB; }
+__host__ __device__ constexpr int cholbig_npad(int n) { return ((cholbig_rhs_row(n) + 1 + BB - 1) / BB) * BB; }
 
 // Everything below works on 16 x 16 sub-blocks in LDS in either scalar type: S = double (17-double rows, v_mfma_f64_16x16x4: 64
 // cycles on gfx950) or S = float (20-float rows, v_mfma_f32_16x16x4: 32 cycles; the fp32 engine's k_chol_big_dag).  CholLay<S>
@@ -828,56 +827,9 @@ __global__ __launch_bounds__(CHOLBIG_THREADS) void k_chol_big_dag(const double* 
   choldag_body<S>(E, n, st, D2c, W, npad, Mimg_ws, flags, epoch, info, tau, dbg);
 }
 
-// ------------------------------------------------------------------ back substitution
-// y = row R of L, columns < n (zero beyond)
-__global__ void k_chol_big_back_init(const double* __restrict__ W, int npad, int n, const double* __restrict__ Ld_ws,
-                                     double* __restrict__ yv, const LMState* __restrict__ st) {
-  if (st->status >= 0) return;
-  const int R = cholbig_rhs_row(n), Rb = R / BB, Rl = R % BB;
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < npad; k += gridDim.x * blockDim.x) {
-    double v = 0;
-    if (k < n) {
-      const int b = k / BB, kl = k % BB;
-      v = (b < Rb) ? W[(size_t)(b * BB + Rl) * npad + Rb * BB + kl] : Ld_ws[(size_t)Rb * BB * BB + Rl * BB + kl];
-    }
-    yv[k] = v;
-  }
-}
-
-// block b: grid = b + 1 workgroups of 256.  Workgroup t: x_b = Minv_b^T y_b ; t == b writes it out, t < b: y_t -= L(b,t)^T x_b
-__global__ __launch_bounds__(256) void k_chol_big_back(const double* __restrict__ W, int npad, int b, int n,
-                                                       const double* __restrict__ Minv_ws, double* __restrict__ yv,
-                                                       double* __restrict__ sol, const LMState* __restrict__ st) {
-  __shared__ double s_y[BB], s_x[BB], s_p[4][BB];
-  if (st->status >= 0) return;
-  const int i = threadIdx.x & 63, part = threadIdx.x >> 6, t = blockIdx.x;
-  if (threadIdx.x < BB) s_y[threadIdx.x] = yv[b * BB + threadIdx.x];
-  __syncthreads();
-  const double* Mg = Minv_ws + (size_t)b * BB * BB;
-  double s = 0;
-  for (int k = part; k < BB; k += 4) s += Mg[k * BB + i] * s_y[k];          // Minv is lower: entries k < i are stored zeros
-  s_p[part][i] = s;
-  __syncthreads();
-  if (part == 0) {
-    const double x = (s_p[0][i] + s_p[1][i]) + (s_p[2][i] + s_p[3][i]);
-    s_x[i] = x;
-    if (t == b && b * BB + i < n) sol[b * BB + i] = x;
-  }
-  __syncthreads();
-  if (t == b) return;
-  const double* Lb = W + (size_t)(t * BB) * npad + b * BB;                     // L(b,t)[lr][lc] at Lb[lr*npad + lc]... see below
-  // L(b,t) was published into block (t, b): element (lr, lc) of L(b,t) sits at W[(t*64 + lr)*npad + b*64 + lc]
-  double u = 0;
-  for (int k = part; k < BB; k += 4) u += Lb[(size_t)k * npad + i] * s_x[k];
-  __syncthreads();
-  s_p[part][i] = u;
-  __syncthreads();
-  if (part == 0) yv[t * BB + i] -= (s_p[0][i] + s_p[1][i]) + (s_p[2][i] + s_p[3][i]);
-}
-
 // ------------------------------------------------------------------ back substitution in ONE launch (round 4)
-// The per-block launches above cost ~10 us each for a 64 x 64 matrix-vector product (launch + three dependent round trips to memory):
-// 11 of them at n = 704, 26 at n = 1664.  Here block row t is ONE workgroup for the whole substitution,
+// One launch per block (rounds 1-3) cost ~10 us each for a 64 x 64 matrix-vector product (launch + three dependent round trips to
+// memory): 11 of them at n = 704, 26 at n = 1664.  Here block row t is ONE workgroup for the whole substitution,
 //     y_t -= L(b,t)^T x_b   for b = last .. t + 1, as the x_b arrive;      x_t = Minv_t^T y_t,   published as its own flag (below),
 // so the chain through the blocks is a hand-over between resident workgroups (at most 27 of them) instead of a launch
 // boundary: the L(b,t) block a workgroup needs next is already in its registers when x_b arrives.  The waits are bounded

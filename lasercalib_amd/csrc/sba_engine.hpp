@@ -16,6 +16,241 @@
 namespace SBA_NS {
 using namespace sba_host;
 
+constexpr int MAX_CAMS = 128;        // sba_upload refuses larger rigs
+
+// ============================================================================================== switches
+// The environment switches ("Environment switches"), read once per handle, at sba_create: a process may change
+// them between two handles.  read_knobs is the only place in the engine that looks at the environment.
+struct Knobs {
+  bool no_dense = false;             // SBA_NO_DENSE: no lane = (point, camera) kernels (fused Schur, dense back substitution)
+  bool no_fused64 = false;           // SBA_NO_FUSED64: fp64 keeps the pair kernels (no k_schur_fused_f64 / k_schur_fused_wide_f64)
+  bool no_wide = false;              // SBA_NO_WIDE: no wide kernels for 17+ cameras (pair kernels, point-aligned back substitution)
+  bool wide_pw2 = false;             // SBA_WIDE_PW2: two points per producer wave in the wide kernels, never three
+  // one-workgroup factorisations of up to 256 unknowns: the right-looking all-in-LDS kernel up to 176 (k_cholesky_blocked),
+  // the left-looking kernel with the factor on chip above that (k_cholesky_ll, sba_chol_ll.hpp: 17..23 cameras).
+  // SBA_CHOL=ll: the left-looking kernel for every size up to 256; SBA_CHOL=blocked: never (the streamed kernel above 176) -- A/B runs, tests
+  bool chol_ll = true, chol_ll_all = false;
+  // fp32 engine, up to 176 unknowns: factor on f32 lanes (v_mfma_f32_16x16x4, f32 pivot chain) and repeat in f64 only when that is
+  // refused -- a non-positive pivot, or one below chol_f32_tau times its diagonal entry (2^-23: the entry's own rounding noise).
+  // SBA_CHOL_F32=0 keeps the f64 factorisation of rounds 1-3; SBA_CHOL_F32_TAU overrides the threshold.
+  bool chol_f32 = true;
+  float chol_f32_tau = 1.1920929e-7f;
+  bool chol_big_dag = true;          // SBA_CHOL_BIG=launches keeps one launch per block column (rounds 1-3)
+  // systems larger than this take the multi-workgroup factorisation (sba_chol_big.hpp); up to CS_MAX_NB * CB = 512 unknowns the
+  // streamed one-workgroup kernel could run too, but it only wins below ~210 (measured at 50k points, fp32: 17 cameras 379 vs 388 us
+  // per iteration, 20: 417 vs 409, 24: 487 vs 454, 32: 647 vs 515).  SBA_CHOL_BIG_MIN_N moves it (diagnostics).
+  int chol_big_min_n = 209;
+  bool decide_kernel = false;        // SBA_DECIDE_KERNEL=1 keeps the separate k_decide launch (A/B measurements)
+  bool schur_scan = false;           // SBA_SCHUR_SCAN=1: several groups, producers scan the point's observations (no k_group_index)
+  bool no_bf3_pairs = false;         // SBA_NO_BF3_PAIRS=1: f32-input MFMA kernels for every group pair (A/B, equivalence test)
+  // The lane = (point, camera) kernels (fused linearise + Schur, wide, dense back substitution) cost the DENSE instruction count
+  // whatever the visibility; below this fraction of the N x C slots filled the observation-driven three-pass path would take over.
+  // Rounds 1-3 set it to 0.35 unmeasured.  Round 4 measured it (profiles/r4_visibility_sweep*.txt: 16 / 17 cameras, 10k and 50k points,
+  // fill 0.14 .. 0.45, both dtypes): the one-launch kernels win at EVERY fill a rig can have (two views of 16 cameras = 0.13: fp32
+  // 78 vs 102 us per iteration at 16 x 10k, 111 vs 163 at 17 x 10k, 118 vs 155 at 16 x 50k; fp64 212 vs 245) because the three-pass
+  // path is bound by its launches and pair kernels, not by the observation count.  So the threshold is 0; SBA_DENSE_MIN_VIS restores one.
+  double dense_min_vis = 0.0;
+  // instruments (stderr)
+  bool schur_debug = false;          // SBA_SCHUR_DEBUG=k: stamps of the k-th fused Schur launch (k >= 2: one with the decision in its prologue)
+  int schur_debug_skip = 0;
+  bool chol_debug = false;           // SBA_CHOL_DEBUG: stamps of the first factorisation
+  bool upload_debug = false;         // SBA_UPLOAD_DEBUG: phase times of sba_upload
+  bool solve_debug = false;          // SBA_SOLVE_DEBUG: host-side phase times of every sba_solve
+  // one-shot exchange (sba_ipc.hpp)
+  long long ipc_timeout_ticks = IPC_TIMEOUT_TICKS;   // SBA_IPC_TIMEOUT_S: how long a gate waits for a peer (100 MHz ticks)
+  bool ipc_allow_cached = false;     // SBA_IPC_ALLOW_CACHED=1: an exchange area in cached memory when uncached is not available
+};
+
+inline Knobs read_knobs() {
+  Knobs k;
+  auto set = [](const char* name) { return getenv(name) != nullptr; };
+  k.no_dense = set("SBA_NO_DENSE");
+  k.no_fused64 = set("SBA_NO_FUSED64");
+  k.no_wide = set("SBA_NO_WIDE");
+  k.wide_pw2 = set("SBA_WIDE_PW2");
+  k.decide_kernel = set("SBA_DECIDE_KERNEL");
+  k.schur_scan = set("SBA_SCHUR_SCAN");
+  k.no_bf3_pairs = set("SBA_NO_BF3_PAIRS");
+  k.chol_debug = set("SBA_CHOL_DEBUG");
+  k.upload_debug = set("SBA_UPLOAD_DEBUG");
+  k.solve_debug = set("SBA_SOLVE_DEBUG");
+  k.ipc_allow_cached = set("SBA_IPC_ALLOW_CACHED");
+  if (const char* e = getenv("SBA_CHOL")) { k.chol_ll = std::string(e) != "blocked"; k.chol_ll_all = std::string(e) == "ll"; }
+  if (const char* e = getenv("SBA_CHOL_F32")) k.chol_f32 = atoi(e) != 0;
+  if (const char* e = getenv("SBA_CHOL_F32_TAU")) { char* end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0 && v < 1) k.chol_f32_tau = (float)v; }
+  if (const char* e = getenv("SBA_CHOL_BIG")) k.chol_big_dag = std::string(e) != "launches";
+  if (const char* e = getenv("SBA_CHOL_BIG_MIN_N")) {
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (end != e && *end == 0 && v >= 0) k.chol_big_min_n = (int)std::min<long>(v, CS_MAX_NB * CB);
+  }
+  if (const char* e = getenv("SBA_DENSE_MIN_VIS")) { char* end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0 && v <= 1) k.dense_min_vis = v; }
+  if (const char* e = getenv("SBA_SCHUR_DEBUG")) { k.schur_debug = true; k.schur_debug_skip = std::max(0, atoi(e) - 1); }
+  if (const char* e = getenv("SBA_IPC_TIMEOUT_S")) {
+    char* end = nullptr;
+    const double sec = strtod(e, &end);
+    if (end != e && sec > 0 && sec < 3600) k.ipc_timeout_ticks = (long long)(sec * 1e8);
+  }
+  return k;
+}
+
+// ============================================================================================== routes
+// What sba_upload knows about a problem when it picks the kernels
+struct Layout {
+  int C, N;
+  int64_t M;
+  bool dense, masked_ok, grp_indexed;
+  int ngroups, npairs;
+  int ncu;                           // compute units of the device
+};
+
+// What runs on a handle: every kernel choice that follows from its layout and its switches (plan_route)
+struct Route {
+  int ksplit = 1;                    // Schur launches: workgroups over the points per group pair (per slice for the wide kernels)
+  bool fused_ok = false;             // the linearisation runs inside the Schur kernel (k_schur_fused_bf3 / _f64 / _wide / _wide_f64)
+  bool fused_wide = false;           // ... k_schur_fused_wide(_f64): compact rows, one launch (implies fused_ok)
+  bool fused_f64 = false;            // ... k_schur_fused_f64: fp64, one group, 11 parameters (sba_schur_f64.hpp)
+  bool fused_masked = false;         // ... with the visibility mask
+  bool lin_pts_ok = false;           // f64, one group: the point linearisation runs inside k_schur_sym (LIN)
+  int wide_pw = 2;                   // wide kernels: points per producer wave, 3 (packed lanes, 12-point rounds) or 2
+  int wide_ts = 1;                   // fp64 wide kernel: workgroups per slice (tile split, grid.y)
+  bool dense_one_group = false;      // dense and <= 16 cameras: lane = (point, camera) kernels apply
+  bool backsub_masked = false;       // sparse one-group rig dense enough for the lane = (point, camera) back substitution (visibility mask)
+  bool backsub_wide = false;         // 17 .. 32 cameras: k_backsub_dense<T, 32>
+  bool backsub_pack = false;         // ... three points per wave (17 .. 21 cameras): k_backsub_dense<T, 0>
+  bool backsub_wave = false;         // 33 .. 128 cameras: k_backsub_dense<T, 64>
+  int linp_lw = 0;                   // 24 .. 128 cameras with (point, camera) tables: k_linearize_points_wave<T, 32 / 64>; 0 = k_linearize_points
+  int nlinp = 0;                     // ... its (persistent) workgroups = entries of cost_part / gmax_part
+  int nbs_dense = 1;                 // workgroups of k_backsub_dense
+  bool pairs_bf3 = false;            // several groups, fp32, indexed producers: the group pairs run on the bf16 pipe (k_schur_diag_bf3 / _offdiag_bf3)
+  bool pairs_fold_u = false;         // ... and k_schur_diag_bf3 accumulates the camera blocks itself (no k_linearize_cams in the loop)
+  bool vis_mask = false;             // a kernel of the route reads the one-group visibility mask
+};
+
+// No HIP call, no allocation, no environment: the layout and the switches in, the kernel choices out
+template <typename T>
+Route plan_route(const Layout& L, const Knobs& k) {
+  Route r;
+  const int C = L.C, N = L.N;
+  const bool dense = L.dense;
+  const bool dense_enough = (double)L.M >= k.dense_min_vis * (double)N * C;
+  {
+    const int target = 256;
+    // workgroups per k-split: every pair is dealt to TS workgroups (tile split, grid.z of k_schur)
+    // the diagonal and the off-diagonal pairs are two launches, one after the other, with the same k-split: it is sized so
+    // that the SMALLER of the two still fills the chip (sized for the larger one, the 4 diagonal pairs of a 64-camera rig ran
+    // on 84 of 256 CUs); the larger launch then simply takes several rounds of shorter workgroups
+    const int wg_diag = L.ngroups * SchurSel<T, true>::TS, wg_off = (L.npairs - L.ngroups) * SchurSel<T, false>::TS;
+    const int wg_per_ks = wg_off > 0 ? std::min(wg_diag, wg_off) : wg_diag;
+    int ks = std::max(1, (target + wg_per_ks - 1) / wg_per_ks);
+    const int maxks = std::max(1, (N + SCHUR_PTS - 1) / SCHUR_PTS);
+    r.ksplit = std::min(ks, maxks);
+    // Round 4: several camera groups -- the launches run in ROUNDS of one workgroup per CU, and a last round that is half empty costs
+    // as much as a full one (64 cameras, k-split 64: 384 off-diagonal workgroups = 1.5 rounds).  Measured (profiles/r4_ksplit_sweep.txt):
+    // 64 x 200k 3 674 -> 3 330 us per iteration with twice the k-split (512 + 768 workgroups: whole rounds, and a finer tail), 128 x 125k
+    // with 13 parameters 10.67 -> 9.98 ms, 32 x 50k 470 -> 435 us.  So: aim at two rounds for the smaller launch, then pick, in a window
+    // around that, the k-split with the smallest modelled makespan  sum over the two launches of  rounds x points per workgroup
+    // (an off-diagonal workgroup builds two panels and 121 tiles: weight 2).
+    if (L.ngroups > 1) {
+      const int ncu = L.ncu;
+      const int ks0 = std::max(1, (2 * ncu + wg_per_ks - 1) / wg_per_ks);
+      double best = 1e300;
+      int best_ks = ks0;
+      for (int q = std::max(1, ks0 * 3 / 4); q <= ks0 * 3 / 2; ++q) {
+        const double per = std::ceil((double)N / q);
+        const double cost = std::ceil((double)wg_diag * q / ncu) * per + (wg_off > 0 ? 2.0 * std::ceil((double)wg_off * q / ncu) * per : 0.0);
+        if (cost < best * (1 - 1e-9)) { best = cost; best_ks = q; }
+      }
+      r.ksplit = std::min(best_ks, maxks);
+    }
+  }
+  // Up to 256 reduced-system rows, f32: the one-launch fused kernel of sba_schur_wide.hpp -- 17 .. 23 cameras of the 11-parameter
+  // model (one group has k_schur_fused_bf3), every rig of up to 19 cameras of the 13-parameter model.  Like the masked
+  // one-group kernel its producer cost does not shrink with the visibility (dense_min_vis).
+  if constexpr (sizeof(T) == 4) {
+    const bool rig_ok = C > GROUP_CAMS ? (dense || (L.grp_indexed && dense_enough))
+                                       : (NCP != 11 && !k.no_dense && (dense || (L.masked_ok && dense_enough)));
+    r.fused_wide = rig_ok && C * NCP <= 16 * WIDE_MAX_NTW && N > 0 && !k.no_wide;
+    if (r.fused_wide) {
+      r.wide_pw = (wide_ntw(C) <= 13 && 3 * C <= 64 && !k.wide_pw2) ? 3 : 2;
+      r.ksplit = std::max(1, std::min(256, (N + 4 * r.wide_pw - 1) / (4 * r.wide_pw)));
+    }
+  }
+#if SBA_NCP == 11
+  // fp64, 17 and 18 cameras (12 / 13 row tiles): k_schur_fused_wide_f64 (sba_schur_f64.hpp), same eligibility; SBA_NO_FUSED64=1 or
+  // SBA_NO_WIDE=1 keep the pair kernels
+  if constexpr (sizeof(T) == 8) {
+    r.fused_wide = C > GROUP_CAMS && C * NCP <= 16 * WIDE_MAX_NTW && (dense || (L.grp_indexed && dense_enough)) && N > 0 &&
+                   !k.no_fused64 && !k.no_wide;
+    if (r.fused_wide) {
+      // 17, 18 cameras (12, 13 row tiles): one workgroup per slice, three points per producer wave; 19 .. 23 (14 .. 16 tiles): two
+      // workgroups per slice share its tiles (a consumer wave holds at most ~23 f64 accumulator tiles), two points per wave
+      r.wide_ts = wide_ntw(C) > 13 ? 2 : 1;
+      r.wide_pw = (r.wide_ts == 1 && !k.wide_pw2) ? 3 : 2;
+      r.ksplit = std::max(1, std::min(256 / r.wide_ts, (N + 4 * r.wide_pw - 1) / (4 * r.wide_pw)));
+    }
+  }
+#endif
+  r.dense_one_group = dense && C <= GROUP_CAMS && N > 0 && !k.no_dense;
+  // 17 .. 23 cameras, dense or group-indexed and dense enough (the rigs of the wide fused kernels): the same back substitution
+  // with a point per 32-lane wave half
+  r.backsub_wide = C > GROUP_CAMS && C <= 32 && N > 0 && (dense || (L.grp_indexed && dense_enough)) && !k.no_dense && !k.no_wide;
+  r.backsub_pack = r.backsub_wide && 3 * C <= 64 && !k.wide_pw2;       // three points per wave (17 .. 21 cameras)
+  // 33 .. 128 cameras (round 4): a point per wave, up to two cameras per lane (k_backsub_dense<T, 64>)
+  r.backsub_wave = C > 32 && N > 0 && (dense || (L.grp_indexed && dense_enough)) && !k.no_dense && !k.no_wide;
+  const int bs_ppc = r.backsub_wave ? 4 : r.backsub_pack ? 12 : r.backsub_wide ? 8 : 16;
+  // (the wave linearisation also forms the point factors inside the LM loop: k_point_factor's work)
+  r.linp_lw = r.backsub_wave ? 64 : (r.backsub_wide && C > 23) ? 32 : 0;
+  r.nlinp = r.linp_lw ? std::max(1, std::min((N + (PM_BLOCK / r.linp_lw) - 1) / (PM_BLOCK / r.linp_lw), 1024)) : 0;
+  r.nbs_dense = std::max(1, std::min((N + bs_ppc - 1) / bs_ppc, sizeof(T) == 4 ? 768 : 512));
+  // the fused linearise+Schur kernel also serves sparse one-group rigs through the visibility mask
+  const bool masked_fused = L.masked_ok && N > 0 && dense_enough && !k.no_dense;
+  // (the fused kernel is built for the 11-parameter model only: 77 register accumulators per lane; 13 parameters need 104)
+  // (fp64, round 3: k_schur_fused_f64, same structure on the f64 matrix pipe; SBA_NO_FUSED64=1 keeps the three-launch path)
+  r.fused_f64 = NCP == 11 && sizeof(T) == 8 && (r.dense_one_group || masked_fused) && !k.no_fused64;
+  r.fused_ok = (NCP == 11 && (r.dense_one_group || masked_fused) && sizeof(T) == 4) || r.fused_wide || r.fused_f64;
+  r.fused_masked = r.fused_ok && !r.dense_one_group && !r.fused_wide;
+  r.lin_pts_ok = (r.dense_one_group || masked_fused) && SCHUR_LIN_OK<T> && !r.fused_f64;
+  // (the lane = (point, camera) back substitution serves sparse one-group rigs through the same mask, down to the visibility
+  //  where the point-aligned kernel, whose cost follows the observation count, wins)
+  r.backsub_masked = L.masked_ok && C <= GROUP_CAMS && N > 0 && dense_enough && !k.no_dense;
+  r.vis_mask = r.fused_masked || (r.lin_pts_ok && !r.dense_one_group) || (r.fused_wide && C <= GROUP_CAMS && !dense) || r.backsub_masked;
+  // several camera groups on the bf16 pair kernels (round 4); the diagonal pairs also accumulate U_c / g_c
+  r.pairs_bf3 = sizeof(T) == 4 && L.ngroups > 1 && L.grp_indexed && !k.no_bf3_pairs;
+  r.pairs_fold_u = r.pairs_bf3 && !r.fused_ok;
+  return r;
+}
+
+// The factorisation of the reduced camera system (n_sys unknowns: C * NCP, or the tied ones of SBA_MODE_SHARED_INTR)
+enum class CholRoute {
+  LL,              // k_cholesky_ll: left-looking, factor on chip, up to 256 unknowns (sba_chol_ll.hpp)
+  LL_F32,          // ... behind k_cholesky_blocked on f32 lanes: k_cholesky_ll only runs when that one refused the system
+  BLOCKED,         // k_cholesky_blocked: right-looking, all in LDS, up to 176 unknowns (fp32 engine: on f32 lanes, f64 on a refusal)
+  STREAM,          // k_cholesky_stream: one workgroup, finished block columns streamed through L2, up to chol_big_min_n
+  BIG_DAG,         // k_chol_big_dag<double>: one launch, walker + tiles (sba_chol_big.hpp), then k_chol_big_back_all
+  BIG_DAG_F32,     // ... k_chol_big_dag<float>, the f64 instance behind it for the systems it refuses
+  BIG_LAUNCHES,    // k_chol_big_prepare + one k_chol_big_step per block column, then k_chol_big_back_all
+};
+// (the largest system, MAX_CAMS cameras of 13 parameters, fits the one-launch forms: k_chol_big_dag's block rows and the x of
+//  k_chol_big_back_all in LDS)
+static_assert(cholbig_npad(MAX_CAMS * 13) / BB <= CHOLDAG_MAX_NBR && (MAX_CAMS * 13 + BB - 1) / BB <= CHOLBIG_MAX_NBX, "large Cholesky sizes");
+
+template <typename T>
+CholRoute chol_route(int n_sys, int ncam /* C * NCP */, const Knobs& k, bool card_shared) {
+  if (k.chol_ll && (n_sys > CHOL_LDS_MAX_N || k.chol_ll_all) && n_sys <= CLL_MAX_NB * CB && ncam <= CLL_THREADS) {
+    // fp32 engine (round 4): the right-looking all-in-LDS kernel on f32 lanes in front of it
+    const bool f32 = sizeof(T) == 4 && k.chol_f32 && !k.chol_ll_all && n_sys > CHOL_LDS_MAX_N && ncam <= CHOLB_LDS_THREADS;
+    return f32 ? CholRoute::LL_F32 : CholRoute::LL;
+  }
+  // (up to 176 unknowns C * NCP <= CHOLB_LDS_THREADS holds: a tied system has 3 + 8 C or 3 + 10 C unknowns)
+  if (n_sys <= CHOL_LDS_MAX_N) return CholRoute::BLOCKED;
+  if (n_sys <= k.chol_big_min_n) return CholRoute::STREAM;             // (chol_big_min_n <= CS_MAX_NB * CB)
+  // ranks that share a card: k_chol_big_dag's progress argument (in-order dispatch of ONE launch) does not cover several such
+  // launches holding each other's CUs
+  if (!k.chol_big_dag || card_shared) return CholRoute::BIG_LAUNCHES;
+  return sizeof(T) == 4 && k.chol_f32 ? CholRoute::BIG_DAG_F32 : CholRoute::BIG_DAG;
+}
+
 // ============================================================================================== engine
 template <typename T>
 struct Engine : EngineBase {
@@ -29,35 +264,17 @@ struct Engine : EngineBase {
   bool has_w = false;
   bool identity_perm = true;
   bool dense = false;                // every point is observed by every camera exactly once
-  bool dense_one_group = false;      // dense and <= 16 cameras: lane = (point, camera) kernels apply
-  int nbs_dense = 1;                 // workgroups of k_backsub_dense
-  // The lane = (point, camera) kernels (fused linearise + Schur, wide, dense back substitution) cost the DENSE instruction count
-  // whatever the visibility; below this fraction of the N x C slots filled the observation-driven three-pass path would take over.
-  // Rounds 1-3 set it to 0.35 unmeasured.  Round 4 measured it (profiles/r4_visibility_sweep*.txt: 16 / 17 cameras, 10k and 50k points,
-  // fill 0.14 .. 0.45, both dtypes): the one-launch kernels win at EVERY fill a rig can have (two views of 16 cameras = 0.13: fp32
-  // 78 vs 102 us per iteration at 16 x 10k, 111 vs 163 at 17 x 10k, 118 vs 155 at 16 x 50k; fp64 212 vs 245) because the three-pass
-  // path is bound by its launches and pair kernels, not by the observation count.  So the threshold is 0; SBA_DENSE_MIN_VIS restores one.
-  double dense_min_vis = 0.0;
-  bool fused_masked = false;         // the fused kernel runs with the visibility mask
-  bool lin_pts_ok = false;           // f64, one group: the point linearisation runs inside k_schur_sym (LIN)
   bool masked_ok = false;            // one group, no duplicate (point, camera) pairs, not dense: visibility mask available
   DevBuf<uint16_t> vis_mask;
   DevBuf<uint16_t> grp_mask;         // several camera groups: k_group_index tables [ngroups][N] (Schur producers)
   DevBuf<int32_t> grp_start;
   bool grp_indexed = false;
-  bool pairs_fold_u = false;         // multi-group fp32: k_schur_diag_bf3 accumulates the camera blocks itself (no k_linearize_cams in the loop)
-  bool no_bf3_pairs = false;         // SBA_NO_BF3_PAIRS=1: f32-input MFMA kernels for every group pair (A/B, equivalence test)
-  bool no_bf3_offdiag = false;       // SBA_NO_BF3_OFFDIAG=1: ... for the off-diagonal pairs only
-  bool fused_ok = false;             // dense, one camera group, f32: the linearisation runs inside the Schur kernel
-  bool fused_bf3 = true;             // ... with the Schur products on the bf16 matrix pipe (k_schur_fused_bf3)
-  bool fused_f64 = false;            // fp64, one group, 11 parameters: k_schur_fused_f64 (sba_schur_f64.hpp)
-  int wide_ts = 1;                   // fp64 wide kernel: workgroups per slice (tile split, grid.y)
-  bool fused_wide = false;           // 17 .. 23 cameras: k_schur_fused_wide (compact rows, one launch; implies fused_ok)
-  int wide_pw = 2;                   // ... points per producer wave: 3 (packed lanes, 12-point rounds) for 17 and 18 cameras, else 2
   DevBuf<double> gdpart;
   std::vector<int64_t> perm;          // pm position -> caller's observation index
-  int nblk = 0, nchunk = 0, ngroups = 0, npairs = 0, ksplit = 1;
+  int nblk = 0, nchunk = 0, ngroups = 0, npairs = 0;
   int n = 0;                          // 11*C
+  Knobs kn;                           // the environment switches, read at sba_create
+  Route rt;                           // the kernels this handle runs, chosen at sba_upload
 
   // static problem data
   DevBuf<T2> uv_pm, uv_cm;
@@ -83,7 +300,6 @@ struct Engine : EngineBase {
   bool pending_decide = false;        // lm_decide_async was called and its decision has not been enqueued yet
   const double* pend_scal = nullptr;
   int pend_ranks = 1;
-  bool defer_decide = true;           // SBA_DECIDE_KERNEL=1 keeps the separate k_decide launch (A/B measurements)
   DevBuf<double> gmax_alt;            // second array of gradient maxima (the fused kernel reads one and writes the other)
   double* gmax_cur = nullptr;         // the array the last linearisation wrote
   DevBuf<sba_lm_iter_log> d_log;
@@ -92,35 +308,18 @@ struct Engine : EngineBase {
   LMState* h_state = nullptr;         // pinned
   sba_lm_opts opts{};
   bool lm_active = false;
-  bool chol_old = false;
-  // one-workgroup factorisations of up to 256 unknowns: the right-looking all-in-LDS kernel up to 176 (k_cholesky_blocked),
-  // the left-looking kernel with the factor on chip above that (k_cholesky_ll, sba_chol_ll.hpp: 17..23 cameras).
-  // SBA_CHOL=ll: the left-looking kernel for every size up to 256; SBA_CHOL=blocked: never (the streamed kernel above 176) -- A/B runs, tests
-  bool chol_ll = true, chol_ll_all = false;
-  // fp32 engine, up to 176 unknowns: factor on f32 lanes (v_mfma_f32_16x16x4, f32 pivot chain) and repeat in f64 only when that is
-  // refused -- a non-positive pivot, or one below chol_f32_tau times its diagonal entry (2^-23: the entry's own rounding noise).
-  // SBA_CHOL_F32=0 keeps the f64 factorisation of rounds 1-3; SBA_CHOL_F32_TAU overrides the threshold.
-  int chol_f32 = 1;
-  float chol_f32_tau = 1.1920929e-7f;
-  // systems larger than this take the multi-workgroup factorisation (sba_chol_big.hpp); up to CS_MAX_NB * CB = 512 unknowns the
-  // streamed one-workgroup kernel could run too, but it only wins below ~210 (measured at 50k points, fp32: 17 cameras 379 vs 388 us
-  // per iteration, 20: 417 vs 409, 24: 487 vs 454, 32: 647 vs 515)
-  int chol_big_min_n = 209;
   DevBuf<double> chol_sol, chol_work, chol_W, chol_Minv, chol_Ld, chol_yv;
   DevBuf<int> chol_info;
   unsigned chol_epoch = 0;              // k_chol_big_back_all: launches so far (its parity picks the copy of x the launch works in)
-  bool chol_big_back_one = true;        // SBA_CHOL_BIG_BACK=launches keeps one launch per block (rounds 1-3)
   DevBuf<unsigned> chol_dag_flags;      // k_chol_big_dag: Mimg_j / W(r,c) published (value = the launch's epoch)
   DevBuf<double> chol_Mimg;             // k_chol_big_dag: the factored diagonal blocks and their inverses, as they lie in LDS
   unsigned chol_dag_epoch = 0;
-  bool chol_big_dag = true;             // SBA_CHOL_BIG=launches keeps one launch per block column (rounds 1-3)
-  int chol_dag_max_nbr = CHOLDAG_MAX_NBR;   // SBA_CHOL_DAG_MAX_NBR: block rows up to which the one-launch factorisation is used
   bool card_shared = false;             // sba_ipc_attach found a peer rank's exchange area on THIS device (a rehearsal of N ranks on one card):
                                         // kernels whose workgroups wait for each other are then not used where a launch-per-step form exists
+  // SBA_CHOL_DEBUG / SBA_SCHUR_DEBUG: armed from the switches at sba_create, cleared once their stamps are printed
   bool chol_debug = false;
   bool schur_debug = false;
-  int schur_exp = 0;                  // SBA_SCHUR_EXP: timing experiments of k_schur_fused_bf3 (its results are wrong when set)
-  int schur_debug_skip = 0;           // SBA_SCHUR_DEBUG=k: stamps of the (k+1)-th fused launch (k >= 1: one with the decision in its prologue)
+  int schur_debug_skip = 0;           // fused Schur launches still to pass before the one whose stamps are printed
   // multi-rank (one handle per GPU, points sharded, cameras replicated): RCCL communicator + exchange buffers
   DevBuf<double> raw_uv, raw_w;         // the caller's raw arrays on the device (dense fast path of upload)
   DevBuf<long long> raw_ci, raw_pi;
@@ -141,7 +340,6 @@ struct Engine : EngineBase {
   uint8_t ipc_my_handle[SBA_IPC_HANDLE_BYTES] = {};
   std::vector<double*> ipc_area;        // every rank's area as mapped into this process (own entry = ipc_mine)
   std::vector<char> ipc_opened;         // ... 1 where this handle called hipIpcOpenMemHandle (and has to close it)
-  long long ipc_timeout_ticks = IPC_TIMEOUT_TICKS;       // SBA_IPC_TIMEOUT_S: how long a gate waits for a peer (100 MHz ticks)
   DevBuf<double*> ipc_ptrs;             // ... the same table on the device
   DevBuf<int> ipc_fail;                 // set by a gate that ran out of time outside the LM loop
   IpcLayout ipc_L{};
@@ -160,8 +358,6 @@ struct Engine : EngineBase {
   bool prof_on = false;
   double prof_us[KP_N] = {};
   long long prof_cnt[KP_N] = {};
-  int pslot = 0;
-  void pslot_advance() {}
   void prof_begin(int k) { if (prof_on) HIPCHK(hipEventRecord(pev[k][0], stream)); }
   void prof_end(int k) { if (prof_on) { HIPCHK(hipEventRecord(pev[k][1], stream)); pev_used[k] = true; } }
   void prof_collect() {   // call after a stream sync
@@ -217,96 +413,73 @@ struct Engine : EngineBase {
     for (int k = 0; k < KP_N; ++k) for (int j = 0; j < 2; ++j) pev[k][j] = hres.ev[2 + 2 * k + j];
     d_state_buf.alloc(2);
     d_state.p = d_state_buf.p;
-    if (getenv("SBA_DECIDE_KERNEL")) defer_decide = false;
-    if (const char* e = getenv("SBA_DENSE_MIN_VIS")) {
-      char* end = nullptr;
-      const double v = strtod(e, &end);
-      if (end != e && v >= 0 && v <= 1) dense_min_vis = v;
-    }
-    // SBA_FUSED_MFMA=f32 keeps the f32-input MFMA kernel (A/B measurements, equivalence test); default: bf16 x 3 split
-    if (const char* e = getenv("SBA_FUSED_MFMA")) fused_bf3 = (std::string(e) != "f32");
-    if (const char* e = getenv("SBA_CHOL")) {
-      chol_old = (std::string(e) == "old"); chol_ll = (std::string(e) != "blocked") && !chol_old; chol_ll_all = (std::string(e) == "ll");
-    }
-    if (getenv("SBA_CHOL_DEBUG")) chol_debug = true;
-    if (const char* e = getenv("SBA_SCHUR_EXP")) schur_exp = atoi(e);
-    if (const char* e = getenv("SBA_CHOL_BIG_BACK")) chol_big_back_one = std::string(e) != "launches";
-    if (const char* e = getenv("SBA_CHOL_BIG")) chol_big_dag = std::string(e) != "launches";
-    if (const char* e = getenv("SBA_LINP_PF")) linp_pf = atoi(e) != 0;
-    if (const char* e = getenv("SBA_CHOL_DAG_MAX_NBR")) chol_dag_max_nbr = std::max(1, std::min(CHOLDAG_MAX_NBR, atoi(e)));
-    if (const char* e = getenv("SBA_CHOL_F32")) chol_f32 = atoi(e) != 0;
-    if (const char* e = getenv("SBA_CHOL_F32_TAU")) { char* end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0 && v < 1) chol_f32_tau = (float)v; }
-    if (const char* e = getenv("SBA_CHOL_BIG_MIN_N")) {      // diagnostic: route smaller systems through the big path too
-      char* end = nullptr;
-      const long v = strtol(e, &end, 10);
-      if (end != e && *end == 0 && v >= 0) chol_big_min_n = (int)std::min<long>(v, CS_MAX_NB * CB);
-    }
-    if (const char* e = getenv("SBA_SCHUR_DEBUG")) { schur_debug = true; schur_debug_skip = std::max(0, atoi(e) - 1); schur_dbg.alloc(64); schur_dbg.zero(stream); }
+    kn = read_knobs();
+    chol_debug = kn.chol_debug;
+    if (kn.schur_debug) { schur_debug = true; schur_debug_skip = kn.schur_debug_skip; schur_dbg.alloc(64); schur_dbg.zero(stream); }
     static bool attrs_set[16] = {};          // the function attributes are per process (and device), not per handle
     if (device < 16 && attrs_set[device]) return;
     // kernels whose dynamic LDS can exceed the 64 KB default
     // only the Schur flavours this dtype launches are instantiated (f32: producer/consumer + fused; f64: symmetric + PARTIAL)
-    auto big_lds = [&](const void* fn) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); };
     if constexpr (SCHUR_SYM<T>) {
-      HIPCHK(big_lds(reinterpret_cast<const void*>(&k_schur_sym<T, true, false>)));
-      HIPCHK(big_lds(reinterpret_cast<const void*>(&k_schur_sym<T, false, false>)));
-      HIPCHK(big_lds(reinterpret_cast<const void*>(&k_schur_sym<T, true, true>)));
-      HIPCHK(big_lds(reinterpret_cast<const void*>(&k_schur_sym<T, false, true>)));
-      if constexpr (SCHUR_LIN_OK<T>) HIPCHK(big_lds(reinterpret_cast<const void*>(&k_schur_sym<T, true, false, true>)));
+      set_lds(&k_schur_sym<T, true, false>, 156 * 1024);
+      set_lds(&k_schur_sym<T, false, false>, 156 * 1024);
+      set_lds(&k_schur_sym<T, true, true>, 156 * 1024);
+      set_lds(&k_schur_sym<T, false, true>, 156 * 1024);
+      if constexpr (SCHUR_LIN_OK<T>) set_lds(&k_schur_sym<T, true, false, true>, 156 * 1024);
 #if SBA_NCP == 11
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_f64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurF64Cfg::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide_f64<12, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWide64Cfg<12, 2, 1>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide_f64<13, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWide64Cfg<13, 2, 1>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide_f64<12, 3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWide64Cfg<12, 3, 1>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide_f64<13, 3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWide64Cfg<13, 3, 1>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide_f64<14, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWide64Cfg<14, 2, 2>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide_f64<15, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWide64Cfg<15, 2, 2>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide_f64<16, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWide64Cfg<16, 2, 2>::LDS_BYTES));
+      set_lds(&k_schur_fused_f64, SchurF64Cfg::LDS_BYTES);
+      set_lds(&k_schur_fused_wide_f64<12, 2, 1>, SchurWide64Cfg<12, 2, 1>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide_f64<13, 2, 1>, SchurWide64Cfg<13, 2, 1>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide_f64<12, 3, 1>, SchurWide64Cfg<12, 3, 1>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide_f64<13, 3, 1>, SchurWide64Cfg<13, 3, 1>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide_f64<14, 2, 2>, SchurWide64Cfg<14, 2, 2>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide_f64<15, 2, 2>, SchurWide64Cfg<15, 2, 2>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide_f64<16, 2, 2>, SchurWide64Cfg<16, 2, 2>::LDS_BYTES);
 #endif
     } else {
-      HIPCHK(big_lds(reinterpret_cast<const void*>(&k_schur<T, true, false>)));
-      HIPCHK(big_lds(reinterpret_cast<const void*>(&k_schur<T, false, false>)));
+      set_lds(&k_schur<T, true, false>, 156 * 1024);
+      set_lds(&k_schur<T, false, false>, 156 * 1024);
 #if SBA_NCP == 11
-      HIPCHK(big_lds(reinterpret_cast<const void*>(&k_schur_fused)));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_bf3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurBf3Cfg::LDS_BYTES));
+      set_lds(&k_schur_fused_bf3, SchurBf3Cfg::LDS_BYTES);
 #endif
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<12, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<12, 2>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<13, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<13, 2>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<14, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<14, 2>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<15, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<15, 2>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<16, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<16, 2>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<12, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<12, 3>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<13, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<13, 3>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<8, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<8, 2>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_fused_wide<8, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurWideCfg<8, 3>::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_diag_bf3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurPairCfg::LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_offdiag_bf3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SchurBf3OffCfg::LDS_BYTES));
+      set_lds(&k_schur_fused_wide<12, 2>, SchurWideCfg<12, 2>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide<13, 2>, SchurWideCfg<13, 2>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide<14, 2>, SchurWideCfg<14, 2>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide<15, 2>, SchurWideCfg<15, 2>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide<16, 2>, SchurWideCfg<16, 2>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide<12, 3>, SchurWideCfg<12, 3>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide<13, 3>, SchurWideCfg<13, 3>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide<8, 2>, SchurWideCfg<8, 2>::LDS_BYTES);
+      set_lds(&k_schur_fused_wide<8, 3>, SchurWideCfg<8, 3>::LDS_BYTES);
+      set_lds(&k_schur_diag_bf3, SchurPairCfg::LDS_BYTES);
+      set_lds(&k_schur_offdiag_bf3, SchurBf3OffCfg::LDS_BYTES);
     }
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_resjac<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholesky_solve<true, T>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    set_lds(&k_resjac<T>, 100 * 1024);
     // (dynamic: the block triangle of 176 unknowns in doubles + two vectors = 146,432 B; the kernel's static LDS -- tables, damping,
     //  right-hand side, trial cameras -- comes on top of it and both must fit the 160 KB of a CU)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholesky_blocked<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)((CHOLB_MAX_NB * (CHOLB_MAX_NB + 1) / 2 * CBS + 2 * CHOLB_MAX_NB * CB) * sizeof(double))));
+    set_lds(&k_cholesky_blocked<T>, (CHOLB_MAX_NB * (CHOLB_MAX_NB + 1) / 2 * CBS + 2 * CHOLB_MAX_NB * CB) * sizeof(double));
     if constexpr (sizeof(T) == 4) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholesky_blocked<T, 16, 20>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)((14 * 15 / 2 * CB * 20 + 2 * 14 * CB) * sizeof(float))));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholesky_blocked<T, 16, 17>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)((16 * 17 / 2 * CB * 17 + 2 * 16 * CB) * sizeof(float))));
+      set_lds(&k_cholesky_blocked<T, 16, 20>, (14 * 15 / 2 * CB * 20 + 2 * 14 * CB) * sizeof(float));
+      set_lds(&k_cholesky_blocked<T, 16, 17>, (16 * 17 / 2 * CB * 17 + 2 * 16 * CB) * sizeof(float));
     }
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholesky_stream), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cholesky_ll<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CLL_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_big_step), hipFuncAttributeMaxDynamicSharedMemorySize, CHOLBIG_LDS_BLOCKS * CBS * (int)sizeof(double)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_big_dag<double>), hipFuncAttributeMaxDynamicSharedMemorySize, CHOLBIG_LDS_BLOCKS * CBS * (int)sizeof(double)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_big_dag<float>), hipFuncAttributeMaxDynamicSharedMemorySize, CHOLBIG_LDS_BLOCKS * CholLay<float>::BS * (int)sizeof(float)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_backsub_trial<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_linearize_points<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_residual<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sq_linearize<T, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sq_linearize<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sq_trial<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sq_trial<T, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+    set_lds(&k_cholesky_stream, 150 * 1024);
+    set_lds(&k_cholesky_ll<T>, CLL_LDS_BYTES);
+    set_lds(&k_chol_big_step, CHOLBIG_LDS_BLOCKS * CBS * sizeof(double));
+    set_lds(&k_chol_big_dag<double>, CHOLBIG_LDS_BLOCKS * CBS * sizeof(double));
+    set_lds(&k_chol_big_dag<float>, CHOLBIG_LDS_BLOCKS * CholLay<float>::BS * sizeof(float));
+    set_lds(&k_backsub_trial<T>, 100 * 1024);
+    set_lds(&k_linearize_points<T>, 100 * 1024);
+    set_lds(&k_residual<T>, 100 * 1024);
+    set_lds(&k_sq_linearize<T, 2>, 100 * 1024);
+    set_lds(&k_sq_linearize<T, 1>, 100 * 1024);
+    set_lds(&k_sq_trial<T, 1>, 100 * 1024);
+    set_lds(&k_sq_trial<T, 2>, 100 * 1024);
     if (device < 16) attrs_set[device] = true;
+  }
+
+  // the dynamic LDS a kernel may ask for beyond the 64 KB default
+  template <typename K> static void set_lds(K* kernel, size_t bytes) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   }
 
   void sync() { HIPCHK(hipStreamSynchronize(stream)); }
@@ -329,7 +502,7 @@ struct Engine : EngineBase {
   int upload(const double* cams_h, const double* pts_h, const double* uv_h, const int64_t* ci_h,
              const int64_t* pi_h, const double* w_h) override {
     HIPCHK(hipSetDevice(device));
-    const bool up_dbg = getenv("SBA_UPLOAD_DEBUG") != nullptr;
+    const bool up_dbg = kn.upload_debug;
     auto up_t0 = std::chrono::steady_clock::now();
     auto up_lap = [&](const char* what) {
       if (!up_dbg) return;
@@ -338,7 +511,7 @@ struct Engine : EngineBase {
       up_t0 = t;
     };
     if (C <= 0 || N < 0 || M < 0) { err = "bad problem size"; return SBA_ERR_INVALID; }
-    if (C > 128) { err = "more than 128 cameras is not supported yet"; return SBA_ERR_UNSUPPORTED; }
+    if (C > MAX_CAMS) { err = "more than 128 cameras is not supported yet"; return SBA_ERR_UNSUPPORTED; }
     if (M > (int64_t)0x7fffffff - 1024) { err = "too many observations for int32 device indices"; return SBA_ERR_UNSUPPORTED; }
     has_w = (w_h != nullptr);
     // Device-side layout: when the list can only be the canonical dense one -- M = N*C -- the caller's raw
@@ -351,7 +524,7 @@ struct Engine : EngineBase {
     bool sorted = true, cam_sorted = true;
     std::vector<uint16_t> vmask;
     bool nodup = (C <= GROUP_CAMS);
-    if (M > 0 && M == (int64_t)N * C && !getenv("SBA_HOST_LAYOUT")) {
+    if (M > 0 && M == (int64_t)N * C) {
       raw_uv.alloc((size_t)M * 2); raw_ci.alloc(M); raw_pi.alloc(M);
       if (has_w) raw_w.alloc(M);
       uv_pm.alloc(M); ci_pm.alloc(M); pi_pm.alloc(M); uv_cm.alloc(M); pi_cm.alloc(M); pt_start.alloc((size_t)N + 1);
@@ -504,39 +677,6 @@ struct Engine : EngineBase {
     for (int a = 0; a < ngroups; ++a)
       for (int b = a + 1; b < ngroups; ++b) { pga.push_back(a); pgb.push_back(b); }
     npairs = (int)pga.size();
-    {
-      int target = 256;
-      if (const char* e = getenv("SBA_SCHUR_WGS")) target = std::max(1, atoi(e));
-      // workgroups per k-split: every pair is dealt to TS workgroups (tile split, grid.z of k_schur)
-      // the diagonal and the off-diagonal pairs are two launches, one after the other, with the same k-split: it is sized so
-      // that the SMALLER of the two still fills the chip (sized for the larger one, the 4 diagonal pairs of a 64-camera rig ran
-      // on 84 of 256 CUs); the larger launch then simply takes several rounds of shorter workgroups
-      const int wg_diag = ngroups * SchurSel<T, true>::TS, wg_off = (npairs - ngroups) * SchurSel<T, false>::TS;
-      const int wg_per_ks = wg_off > 0 ? std::min(wg_diag, wg_off) : wg_diag;
-      int ks = std::max(1, (target + wg_per_ks - 1) / wg_per_ks);
-      const int maxks = std::max(1, (N + SCHUR_PTS - 1) / SCHUR_PTS);
-      ksplit = std::min(ks, maxks);
-      // Round 4: several camera groups -- the launches run in ROUNDS of one workgroup per CU, and a last round that is half empty costs
-      // as much as a full one (64 cameras, k-split 64: 384 off-diagonal workgroups = 1.5 rounds).  Measured (profiles/r4_ksplit_sweep.txt):
-      // 64 x 200k 3 674 -> 3 330 us per iteration with twice the k-split (512 + 768 workgroups: whole rounds, and a finer tail), 128 x 125k
-      // with 13 parameters 10.67 -> 9.98 ms, 32 x 50k 470 -> 435 us.  So: aim at two rounds for the smaller launch, then pick, in a window
-      // around that, the k-split with the smallest modelled makespan  sum over the two launches of  rounds x points per workgroup
-      // (an off-diagonal workgroup builds two panels and 121 tiles: weight 2).  SBA_SCHUR_WGS pins the target and skips the search.
-      if (ngroups > 1 && !getenv("SBA_SCHUR_WGS")) {
-        int ncu = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
-        const int ks0 = std::max(1, (2 * ncu + wg_per_ks - 1) / wg_per_ks);
-        double best = 1e300;
-        int best_ks = ks0;
-        for (int k = std::max(1, ks0 * 3 / 4); k <= ks0 * 3 / 2; ++k) {
-          const double per = std::ceil((double)N / k);
-          const double cost = std::ceil((double)wg_diag * k / ncu) * per + (wg_off > 0 ? 2.0 * std::ceil((double)wg_off * k / ncu) * per : 0.0);
-          if (cost < best * (1 - 1e-9)) { best = cost; best_ks = k; }
-        }
-        ksplit = std::min(best_ks, maxks);
-      }
-    }
 
     up_lap("blocks + camera-major copies");
     if (!dev_dense) {
@@ -550,9 +690,7 @@ struct Engine : EngineBase {
     cam_chunk_start.upload(cam_ch, stream);
     pair_ga.upload(pga, stream); pair_gb.upload(pgb, stream);
     grp_indexed = false;
-    no_bf3_pairs = getenv("SBA_NO_BF3_PAIRS") != nullptr;
-    no_bf3_offdiag = getenv("SBA_NO_BF3_OFFDIAG") != nullptr;
-    if (ngroups > 1 && N > 0 && !getenv("SBA_SCHUR_SCAN")) {
+    if (ngroups > 1 && N > 0 && !kn.schur_scan) {
       grp_mask.alloc((size_t)ngroups * N); grp_start.alloc((size_t)ngroups * N);
       if (up_flag.n == 0) up_flag.alloc(1);
       up_flag.zero(stream);
@@ -563,40 +701,11 @@ struct Engine : EngineBase {
       sync();
       grp_indexed = (flag == 0);     // cameras strictly ascending inside every point; otherwise the producers scan
     }
-    // Up to 256 reduced-system rows, f32: the one-launch fused kernel of sba_schur_wide.hpp -- 17 .. 23 cameras of the 11-parameter
-    // model (one group has k_schur_fused_bf3), every rig of up to 19 cameras of the 13-parameter model.  Like the masked
-    // one-group kernel its producer cost does not shrink with the visibility, so below ~35 % the three-pass path stays.
-    fused_wide = false;
-    if constexpr (sizeof(T) == 4) {
-      const bool dense_enough = (double)M >= dense_min_vis * (double)N * C;
-      const bool rig_ok = C > GROUP_CAMS ? (dense || (grp_indexed && dense_enough))
-                                         : (NCP != 11 && !getenv("SBA_NO_DENSE") && (dense || (masked_ok && dense_enough)));
-      fused_wide = rig_ok && C * NCP <= 16 * WIDE_MAX_NTW && N > 0 && fused_bf3 && !getenv("SBA_NO_FUSED") && !getenv("SBA_NO_WIDE");
-      if (fused_wide) {
-        int target = 256;
-        if (const char* e = getenv("SBA_SCHUR_WGS")) target = std::max(1, atoi(e));
-        wide_pw = (wide_ntw(C) <= 13 && 3 * C <= 64 && !getenv("SBA_WIDE_PW2")) ? 3 : 2;
-        ksplit = std::max(1, std::min(target, (N + 4 * wide_pw - 1) / (4 * wide_pw)));
-      }
-    }
-#if SBA_NCP == 11
-    // fp64, 17 and 18 cameras (12 / 13 row tiles): k_schur_fused_wide_f64 (sba_schur_f64.hpp), same eligibility; SBA_NO_FUSED64=1 or
-    // SBA_NO_WIDE=1 keep the pair kernels
-    if constexpr (sizeof(T) == 8) {
-      const bool dense_enough = (double)M >= dense_min_vis * (double)N * C;
-      fused_wide = C > GROUP_CAMS && C * NCP <= 16 * WIDE_MAX_NTW && (dense || (grp_indexed && dense_enough)) && N > 0 &&
-                   !getenv("SBA_NO_FUSED") && !getenv("SBA_NO_FUSED64") && !getenv("SBA_NO_WIDE");
-      if (fused_wide) {
-        int target = 256;
-        if (const char* e = getenv("SBA_SCHUR_WGS")) target = std::max(1, atoi(e));
-        // 17, 18 cameras (12, 13 row tiles): one workgroup per slice, three points per producer wave; 19 .. 23 (14 .. 16 tiles): two
-        // workgroups per slice share its tiles (a consumer wave holds at most ~23 f64 accumulator tiles), two points per wave
-        wide_ts = wide_ntw(C) > 13 ? 2 : 1;
-        wide_pw = (wide_ts == 1 && !getenv("SBA_WIDE_PW2")) ? 3 : 2;
-        ksplit = std::max(1, std::min(target / wide_ts, (N + 4 * wide_pw - 1) / (4 * wide_pw)));
-      }
-    }
-#endif
+    int ncu = 256;
+    hipDeviceProp_t prop;
+    if (ngroups > 1 && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
+    rt = plan_route<T>(Layout{C, N, M, dense, masked_ok, grp_indexed, ngroups, npairs, ncu}, kn);
+    const int ksplit = rt.ksplit;
 
     for (int b = 0; b < 2; ++b) {
       cams[b].alloc((size_t)C * NCP); pts[b].alloc((size_t)N * 3);
@@ -605,44 +714,18 @@ struct Engine : EngineBase {
     pfac.alloc((size_t)std::max(N, 1) * PF);
     V.alloc((size_t)N * 6); gp.alloc((size_t)N * 3); D2p.alloc((size_t)N * 3); D2c.alloc(n);
     U.alloc((size_t)C * NCP * NCP); gc.alloc(n); Upart.alloc((size_t)std::max(1, nchunk) * 256);
-    bpart.alloc(std::max((size_t)ngroups * ksplit * GROUP_ROWS, fused_wide ? (size_t)ksplit * WIDE_ROWS : (size_t)0));
-    slabs.alloc(std::max((size_t)npairs * ksplit * GROUP_TILES * GROUP_TILES * 256, fused_wide ? (size_t)ksplit * WIDE_SLOTS * 256 : (size_t)0));
+    bpart.alloc(std::max((size_t)ngroups * ksplit * GROUP_ROWS, rt.fused_wide ? (size_t)ksplit * WIDE_ROWS : (size_t)0));
+    slabs.alloc(std::max((size_t)npairs * ksplit * GROUP_TILES * GROUP_TILES * 256, rt.fused_wide ? (size_t)ksplit * WIDE_SLOTS * 256 : (size_t)0));
     E_own.alloc((size_t)n * n + 3 * n + 1); scal_own.alloc(NSCAL); delta_c.alloc(n);
     const int nres_blocks = (int)((M + PM_BLOCK - 1) / PM_BLOCK);
-    dense_one_group = dense && C <= GROUP_CAMS && N > 0 && !getenv("SBA_NO_DENSE");
-    // 17 .. 23 cameras, dense or group-indexed and dense enough (the rigs of the wide fused kernels): the same back substitution
-    // with a point per 32-lane wave half
-    backsub_wide = C > GROUP_CAMS && C <= 32 && N > 0 && (dense || (grp_indexed && (double)M >= dense_min_vis * (double)N * C)) &&
-                   !getenv("SBA_NO_DENSE") && !getenv("SBA_NO_WIDE");
-    backsub_pack = backsub_wide && 3 * C <= 64 && !getenv("SBA_WIDE_PW2");       // three points per wave (17 .. 21 cameras)
-    // 33 .. 128 cameras (round 4): a point per wave, up to two cameras per lane (k_backsub_dense<T, 64>)
-    backsub_wave = C > 32 && N > 0 && (dense || (grp_indexed && (double)M >= dense_min_vis * (double)N * C)) && !getenv("SBA_NO_DENSE") && !getenv("SBA_NO_WIDE");
-    const int bs_ppc = backsub_wave ? 4 : backsub_pack ? 12 : backsub_wide ? 8 : 16;
-    linp_lw = getenv("SBA_LINP_BLOCKS") ? 0 : backsub_wave ? 64 : (backsub_wide && C > 23) ? 32 : 0;
-    nlinp = linp_lw ? std::max(1, std::min((N + (PM_BLOCK / linp_lw) - 1) / (PM_BLOCK / linp_lw), 1024)) : 0;
-    nbs_dense = std::max(1, std::min((N + bs_ppc - 1) / bs_ppc, getenv("SBA_BS_WGS") ? atoi(getenv("SBA_BS_WGS")) : (sizeof(T) == 4 ? 768 : 512)));
-    // the fused linearise+Schur kernel also serves sparse one-group rigs through the visibility mask; its producer cost
-    // does not shrink with the number of observations, so below ~35 % visibility the three-pass path is used
-    const bool masked_fused = masked_ok && N > 0 && (double)M >= dense_min_vis * (double)N * C && !getenv("SBA_NO_DENSE");
-    // (the fused kernel is built for the 11-parameter model only: 77 register accumulators per lane; 13 parameters need 104)
-    // (fp64, round 3: k_schur_fused_f64, same structure on the f64 matrix pipe; SBA_NO_FUSED64=1 keeps the three-launch path)
-    fused_f64 = NCP == 11 && sizeof(T) == 8 && (dense_one_group || masked_fused) && !getenv("SBA_NO_FUSED") && !getenv("SBA_NO_FUSED64");
-    fused_ok = (NCP == 11 && (dense_one_group || masked_fused) && sizeof(T) == 4 && !getenv("SBA_NO_FUSED")) || fused_wide || fused_f64;
-    fused_masked = fused_ok && !dense_one_group && !fused_wide;
-    lin_pts_ok = (dense_one_group || masked_fused) && SCHUR_LIN_OK<T> && !getenv("SBA_NO_FUSED") && !fused_f64;
-    // (the lane = (point, camera) back substitution serves sparse one-group rigs through the same mask, down to the visibility
-    //  where the point-aligned kernel, whose cost follows the observation count, wins)
-    backsub_masked = masked_ok && C <= GROUP_CAMS && N > 0 && (double)M >= dense_min_vis * (double)N * C && !getenv("SBA_NO_DENSE");
-    if (fused_masked || (lin_pts_ok && !dense_one_group) || (fused_wide && C <= GROUP_CAMS && !dense) || backsub_masked) vis_mask.upload(vmask, stream);
-    if (fused_ok) gdpart.alloc((size_t)ksplit * 2 * (fused_wide ? WIDE_ROWS : GROUP_ROWS));
-    // several camera groups on the bf16 pair kernels (round 4): the diagonal pairs also accumulate U_c / g_c (SBA_PAIRS_LINC=1 keeps
-    // k_linearize_cams + k_reduce_cams)
-    pairs_fold_u = sizeof(T) == 4 && ngroups > 1 && grp_indexed && !no_bf3_pairs && !fused_ok && !getenv("SBA_PAIRS_LINC");
-    if (pairs_fold_u) gdpart.alloc((size_t)ngroups * ksplit * 2 * GROUP_ROWS);
+    const int nlinp = rt.nlinp;
+    if (rt.vis_mask) vis_mask.upload(vmask, stream);
+    if (rt.fused_ok) gdpart.alloc((size_t)ksplit * 2 * (rt.fused_wide ? WIDE_ROWS : GROUP_ROWS));
+    if (rt.pairs_fold_u) gdpart.alloc((size_t)ngroups * ksplit * 2 * GROUP_ROWS);
     cost_part.alloc((size_t)std::max(std::max(std::max(std::max(nblk, nres_blocks), ksplit), nlinp), 1)); gmax_part.alloc(std::max(std::max(std::max(nblk, ksplit), nlinp), 1)); gmax_alt.alloc(std::max(std::max(std::max(nblk, ksplit), nlinp), 1));
     // (k_backsub_dense writes one partial row per WORKGROUP: nbs_dense of them, which exceeds the number of point-aligned blocks on
     //  dense rigs with few cameras -- 8 x 1000: 63 vs 32; sized for nblk alone the rows used to run over into the next buffer)
-    trial_part.alloc((size_t)4 * std::max(std::max(nblk, nbs_dense), 1));
+    trial_part.alloc((size_t)4 * std::max(std::max(nblk, rt.nbs_dense), 1));
     up_lap("allocations + H2D enqueue");
     sync();   // the staging vectors go out of scope now
     up_lap("H2D completion");
@@ -696,22 +779,37 @@ struct Engine : EngineBase {
     hipLaunchKernelGGL(k_resjac<T>, dim3(g), dim3(PM_BLOCK), lds, stream, campre[cur].p, C, ptsT[cur].p, uv_pm.p,
                        has_w ? w_pm.p : nullptr, ci_pm.p, pi_pm.p, M, r_out, Jc_pm.p, Jp_pm.p);
   }
+  // the route's choices that also depend on the solve: points-only mode (free_cams == 0) has no camera system
+  bool free_cams() const { return h_state && h_state->free_cams; }
+  // the linearisation is folded into the Schur kernel (k_schur_fused_bf3 and its kin) whenever the cameras are free
+  bool fused() const { return rt.fused_ok && free_cams(); }
+  bool lin_pts() const { return rt.lin_pts_ok && free_cams(); }   // f64: points linearised inside k_schur_sym
+  // inside the LM loop with free cameras the wave linearisation also forms the trial's point factors (launch_schur skips k_point_factor)
+  bool linp_folds_pf(const LMState* st) const { return st != nullptr && rt.linp_lw != 0 && free_cams() && !lin_pts() && !fused(); }
+  int n_linp_blocks() const { return rt.linp_lw ? rt.nlinp : nblk; }
+  int n_lin_parts() const { return (fused() || lin_pts()) ? rt.ksplit : n_linp_blocks(); }       // entries of cost_part / gmax_part
+  bool backsub_dense() const { return rt.dense_one_group || rt.backsub_masked || rt.backsub_wide || rt.backsub_wave; }
+  int n_trial_parts() const { return backsub_dense() ? rt.nbs_dense : nblk; }
+  // several camera groups, fp32, indexed producers: the group pairs run on the bf16 pipe (k_schur_diag_bf3 / k_schur_offdiag_bf3)
+  bool pairs_bf3() const { return rt.pairs_bf3 && !fused(); }
+  // (the name is historical: every Schur kernel that takes the previous step's decision in its prologue -- k_schur_fused_bf3,
+  //  k_schur_fused_wide(_f64), k_schur_fused_f64)
+  bool bf3_path() const { return fused() && !sq_mode(); }
+
   // st == nullptr: unconditional (used outside the LM loop); otherwise the launch is a no-op once the solve has
   // terminated or when the last step was rejected and nothing has to be re-linearized
-  bool linp_folds_pf(const LMState* st) const { return st != nullptr && linp_lw != 0 && linp_pf && h_state && h_state->free_cams && !lin_pts() && !fused(); }
   void launch_linearize_points(const LMState* st) {
     if (nblk == 0) return;
-    if (linp_lw) {
+    if (rt.linp_lw) {
       const uint16_t* tm = dense ? (const uint16_t*)nullptr : grp_mask.p;
       const int32_t* ts = dense ? (const int32_t*)nullptr : grp_start.p;
-      // inside the LM loop with free cameras the launch also forms the trial's point factors (k_point_factor's work: launch_schur skips it)
       T* pfp = linp_folds_pf(st) ? pfac.p : nullptr;
       const unsigned char* fx = has_fixed ? pt_fixed_mask.p : (const unsigned char*)nullptr;
-      if (linp_lw == 64)
-        hipLaunchKernelGGL((k_linearize_points_wave<T, 64>), dim3(nlinp), dim3(PM_BLOCK), 0, stream, st ? ps_lm() : ps_now(), st, C, uv_pm.p,
+      if (rt.linp_lw == 64)
+        hipLaunchKernelGGL((k_linearize_points_wave<T, 64>), dim3(rt.nlinp), dim3(PM_BLOCK), 0, stream, st ? ps_lm() : ps_now(), st, C, uv_pm.p,
                            has_w ? w_pm.p : nullptr, N, tm, ts, V.p, gp.p, D2p.p, cost_part.p, gmax_part.p, pfp, fx);
       else
-        hipLaunchKernelGGL((k_linearize_points_wave<T, 32>), dim3(nlinp), dim3(PM_BLOCK), 0, stream, st ? ps_lm() : ps_now(), st, C, uv_pm.p,
+        hipLaunchKernelGGL((k_linearize_points_wave<T, 32>), dim3(rt.nlinp), dim3(PM_BLOCK), 0, stream, st ? ps_lm() : ps_now(), st, C, uv_pm.p,
                            has_w ? w_pm.p : nullptr, N, tm, ts, V.p, gp.p, D2p.p, cost_part.p, gmax_part.p, pfp, fx);
       return;
     }
@@ -726,137 +824,18 @@ struct Engine : EngineBase {
                        has_w ? w_cm.p : nullptr, pi_cm.p, chunk_cam.p, chunk_begin.p, chunk_end.p, Upart.p);
     hipLaunchKernelGGL(k_reduce_cams, dim3(C), dim3(1024), 0, stream, Upart.p, cam_chunk_start.p, U.p, gc.p, st);
   }
-  // the linearisation is folded into the Schur kernel (k_schur_fused) whenever the cameras are free
-  bool fused() const { return fused_ok && h_state && h_state->free_cams; }
-  bool lin_pts() const { return lin_pts_ok && h_state && h_state->free_cams; }   // f64: points linearised inside k_schur_sym
-  int n_lin_parts() const { return (fused() || lin_pts()) ? ksplit : n_linp_blocks(); }       // entries of cost_part / gmax_part
   void launch_schur() {
-    if constexpr (sizeof(T) == 4) {
-      if (fused() && fused_wide) { launch_schur_wide(); return; }
-    }
+    if (fused() && rt.fused_wide) { launch_schur_wide(); return; }
 #if SBA_NCP == 11
-    if constexpr (sizeof(T) == 8) {
-      if (fused() && fused_wide) {
-        double* gm_out = nullptr;
-        const FusedDecide fd = make_fused_decide(gm_out);
-        const bool tables = !dense;
-        const uint16_t* tmask = tables ? grp_mask.p : nullptr;
-        const int32_t* tstart = tables ? grp_start.p : nullptr;
-        auto go = [&](auto ntw_c, auto pw_c, auto ts_c) {
-          constexpr int NTW = decltype(ntw_c)::value, PW = decltype(pw_c)::value, TS = decltype(ts_c)::value;
-          constexpr size_t lds64 = SchurWide64Cfg<NTW, PW, TS>::LDS_BYTES;
-          hipLaunchKernelGGL((k_schur_fused_wide_f64<NTW, PW, TS>), dim3(ksplit, TS), dim3(SCHUR_THREADS), lds64, stream,
-                             ps_lm(), fd, C, uv_pm.p, has_w ? w_pm.p : nullptr, tmask, tstart, N, ksplit, D2p.p, gp.p, pfac.p, slabs.p, bpart.p,
-                             gdpart.p, cost_part.p, gm_out, (schur_debug && schur_debug_skip == 0) ? schur_dbg.p : nullptr);
-        };
-        using P2 = std::integral_constant<int, 2>;
-        using P3 = std::integral_constant<int, 3>;
-        using S1 = std::integral_constant<int, 1>;
-        using S2 = std::integral_constant<int, 2>;
-        switch (wide_ntw(C)) {
-          case 12: if (wide_pw == 3) go(std::integral_constant<int, 12>{}, P3{}, S1{}); else go(std::integral_constant<int, 12>{}, P2{}, S1{}); break;
-          case 13: if (wide_pw == 3) go(std::integral_constant<int, 13>{}, P3{}, S1{}); else go(std::integral_constant<int, 13>{}, P2{}, S1{}); break;
-          case 14: go(std::integral_constant<int, 14>{}, P2{}, S2{}); break;
-          case 15: go(std::integral_constant<int, 15>{}, P2{}, S2{}); break;
-          default: go(std::integral_constant<int, 16>{}, P2{}, S2{}); break;
-        }
-        d_state.p = fd.st_out;
-        pending_decide = false;
-        gmax_cur = gm_out;
-        if (schur_debug && schur_debug_skip > 0) { --schur_debug_skip; return; }
-        if (schur_debug) {
-          std::vector<long long> st(64);
-          HIPCHK(hipMemcpyAsync(st.data(), schur_dbg.p, 64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-          sync();
-          fprintf(stderr, "[schur_fused_wide_f64 stamps, cycles since the first producer stamp; per chunk of 8 or 12 points: producer-done consumer-done]\n");
-          for (int i = 0; i < 14; ++i) fprintf(stderr, "  it %2d: P %7lld  C %7lld\n", i, st[2 * i] - st[0], st[2 * i + 1] - st[0]);
-          fprintf(stderr, "  phases (cycles): prologue %lld | main loop %lld | fold U %lld | slab stores %lld | tail %lld | whole kernel %lld\n",
-                  st[49] - st[48], st[50] - st[49], st[51] - st[50], st[52] - st[51], st[53] - st[52], st[53] - st[48]);
-          schur_debug = false;
-        }
-        return;
-      }
-      if (fused() && fused_f64) {
-        double* gm_out = nullptr;
-        const FusedDecide fd = make_fused_decide(gm_out);
-        hipLaunchKernelGGL(k_schur_fused_f64, dim3(ksplit), dim3(SCHUR_THREADS), SchurF64Cfg::LDS_BYTES, stream,
-                           ps_lm(), fd, C, uv_pm.p, has_w ? w_pm.p : nullptr, pt_start.p, fused_masked ? vis_mask.p : (const uint16_t*)nullptr,
-                           N, ksplit, D2p.p, gp.p, pfac.p, slabs.p, bpart.p, gdpart.p, cost_part.p, gm_out,
-                           (schur_debug && schur_debug_skip == 0) ? schur_dbg.p : nullptr);
-        d_state.p = fd.st_out;
-        pending_decide = false;
-        gmax_cur = gm_out;
-        if (schur_debug && schur_debug_skip > 0) { --schur_debug_skip; return; }
-        if (schur_debug) {
-          std::vector<long long> st(64);
-          HIPCHK(hipMemcpyAsync(st.data(), schur_dbg.p, 64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-          sync();
-          fprintf(stderr, "[schur_fused_f64 stamps, cycles since the first producer stamp; per chunk: producer-done consumer-done]\n");
-          for (int i = 0; i < 14; ++i) fprintf(stderr, "  it %2d: P %7lld  C %7lld\n", i, st[2 * i] - st[0], st[2 * i + 1] - st[0]);
-          fprintf(stderr, "  phases (cycles): prologue %lld | main loop %lld | fold U %lld | slab stores %lld | tail %lld | whole kernel %lld\n",
-                  st[49] - st[48], st[50] - st[49], st[51] - st[50], st[52] - st[51], st[53] - st[52], st[53] - st[48]);
-          schur_debug = false;
-        }
-        return;
-      }
-    }
-#endif
-#if SBA_NCP == 11
-    if constexpr (sizeof(T) == 4) {
-      if (fused()) {
-        if (fused_bf3) {
-          FusedDecide fd{};
-          fd.st_in = fd.st_out = d_state.p;
-          double* gm_out = (gmax_cur == gmax_part.p) ? gmax_alt.p : gmax_part.p;      // never the array a decision may still read
-          if (pending_decide) {
-            st_slot ^= 1;
-            fd.st_out = d_state_buf.p + st_slot;
-            fd.do_decide = 1;
-            fd.scal_all = pend_scal; fd.n_ranks = pend_ranks;
-            fd.trial_part = trial_part.p; fd.gmax_in = gmax_cur;
-            fd.n_trial = n_trial_parts(); fd.n_gmax = n_lin_parts();
-            fd.log = reinterpret_cast<LMLogRow*>(d_log.p); fd.log_cap = LOG_CAP;
-          }
-          hipLaunchKernelGGL(k_schur_fused_bf3, dim3(ksplit), dim3(SCHUR_THREADS), SchurBf3Cfg::LDS_BYTES, stream,
-                             ps_lm(), fd, C, uv_pm.p, has_w ? w_pm.p : nullptr, pt_start.p, fused_masked ? vis_mask.p : (const uint16_t*)nullptr,
-                             N, ksplit, D2p.p, gp.p, pfac.p,
-                             slabs.p, bpart.p, gdpart.p, cost_part.p, gm_out, (schur_debug && schur_debug_skip == 0) ? schur_dbg.p : nullptr,
-                             schur_exp);
-          d_state.p = fd.st_out;
-          pending_decide = false;
-          gmax_cur = gm_out;
-        } else
-          hipLaunchKernelGGL(k_schur_fused, dim3(ksplit), dim3(SCHUR_THREADS), SchurFusedCfg<float>::LDS_BYTES, stream,
-                             ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, pt_start.p, fused_masked ? vis_mask.p : (const uint16_t*)nullptr,
-                             N, ksplit, D2p.p, gp.p, pfac.p,
-                             slabs.p, bpart.p, gdpart.p, cost_part.p, gmax_part.p, schur_debug ? schur_dbg.p : nullptr);
-        if (schur_debug && schur_debug_skip > 0) { --schur_debug_skip; return; }
-        if (schur_debug) {
-          std::vector<long long> st(64);
-          HIPCHK(hipMemcpyAsync(st.data(), schur_dbg.p, 64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-          sync();
-          fprintf(stderr, "[schur_fused stamps, cycles since the first producer stamp; per chunk: producer-done consumer-done]\n");
-          for (int i = 0; i < 14; ++i) fprintf(stderr, "  it %2d: P %7lld  C %7lld\n", i, st[2 * i] - st[0], st[2 * i + 1] - st[0]);
-          fprintf(stderr, "  phases (cycles): prologue %lld | main loop %lld | fold U %lld | slab stores %lld | tail %lld | whole kernel %lld\n",
-                  st[49] - st[48], st[50] - st[49], st[51] - st[50], st[52] - st[51], st[53] - st[52], st[53] - st[48]);
-          if (fused_bf3)
-            fprintf(stderr, "  prologue (cycles): loads requested + LDS zeroed %lld | first barrier passed (record arrived) %lld | decision taken %lld | camera table in LDS %lld | producers set up %lld\n",
-                    st[54] - st[48], st[55] - st[48], st[57] - st[48], st[56] - st[48], st[49] - st[48]);
-          if (fused_bf3 && st[58])
-            fprintf(stderr, "  decision (cycles since kernel start): partial sums folded %lld | record updated %lld\n", st[58] - st[48], st[59] - st[48]);
-          schur_debug = false;
-        }
-        return;
-      }
-    }
+    if (fused()) { launch_schur_fused(); return; }
 #endif
     if constexpr (SCHUR_LIN_OK<T>) {
       if (lin_pts()) {
         using CfgD = SchurSel<T, true>;
-        hipLaunchKernelGGL((k_schur_sym<T, true, false, true>), dim3(ksplit, 1, CfgD::TS), dim3(CfgD::THREADS), CfgD::LDS_BYTES,
+        hipLaunchKernelGGL((k_schur_sym<T, true, false, true>), dim3(rt.ksplit, 1, CfgD::TS), dim3(CfgD::THREADS), CfgD::LDS_BYTES,
                            stream, ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pi_pm.p, pt_start.p, N,
-                           pfac.p, pair_ga.p, pair_gb.p, 0, ksplit, 1, slabs.p, bpart.p, (long long*)nullptr,
-                           dense_one_group ? (const uint16_t*)nullptr : vis_mask.p, D2p.p, gp.p, cost_part.p, gmax_part.p);
+                           pfac.p, pair_ga.p, pair_gb.p, 0, rt.ksplit, 1, slabs.p, bpart.p, (long long*)nullptr,
+                           rt.dense_one_group ? (const uint16_t*)nullptr : vis_mask.p, D2p.p, gp.p, cost_part.p, gmax_part.p);
         return;
       }
     }
@@ -887,51 +866,105 @@ struct Engine : EngineBase {
     }
     return fd;
   }
-  void launch_schur_wide() {
-    if constexpr (sizeof(T) == 4) {
-      double* gm_out = nullptr;
-      const FusedDecide fd = make_fused_decide(gm_out);
-      // sparse rigs: per (16-camera group, point) visibility mask + index of the point's first observation in the group -- the
-      // k_group_index tables with several groups, the one-group mask and the point's start otherwise
-      const bool tables = !dense;
-      const uint16_t* tmask = !tables ? nullptr : C > GROUP_CAMS ? grp_mask.p : vis_mask.p;
-      const int32_t* tstart = !tables ? nullptr : C > GROUP_CAMS ? grp_start.p : pt_start.p;
-      auto go = [&](auto ntw_c, auto pw_c) {
-        constexpr int NTW = decltype(ntw_c)::value, PW = decltype(pw_c)::value;
-        constexpr size_t lds = SchurWideCfg<NTW, PW>::LDS_BYTES;
-        hipLaunchKernelGGL((k_schur_fused_wide<NTW, PW>), dim3(ksplit), dim3(SCHUR_THREADS), lds, stream,
-                           ps_lm(), fd, C, uv_pm.p, has_w ? w_pm.p : nullptr, tmask, tstart, N, ksplit, D2p.p, gp.p, pfac.p, slabs.p, bpart.p, gdpart.p,
-                           cost_part.p, gm_out, (schur_debug && schur_debug_skip == 0) ? schur_dbg.p : nullptr);
-      };
-      using P2 = std::integral_constant<int, 2>;
-      using P3 = std::integral_constant<int, 3>;
-      switch (wide_ntw(C)) {
-        case 8: if (wide_pw == 3) go(std::integral_constant<int, 8>{}, P3{}); else go(std::integral_constant<int, 8>{}, P2{}); break;
-        case 12: if (wide_pw == 3) go(std::integral_constant<int, 12>{}, P3{}); else go(std::integral_constant<int, 12>{}, P2{}); break;
-        case 13: if (wide_pw == 3) go(std::integral_constant<int, 13>{}, P3{}); else go(std::integral_constant<int, 13>{}, P2{}); break;
-        case 14: go(std::integral_constant<int, 14>{}, P2{}); break;
-        case 15: go(std::integral_constant<int, 15>{}, P2{}); break;
-        default: go(std::integral_constant<int, 16>{}, P2{}); break;
-      }
-      d_state.p = fd.st_out;
-      pending_decide = false;
-      gmax_cur = gm_out;
-      if (schur_debug && schur_debug_skip > 0) { --schur_debug_skip; return; }
-      if (schur_debug) {
-        std::vector<long long> st(64);
-        HIPCHK(hipMemcpyAsync(st.data(), schur_dbg.p, 64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-        sync();
-        fprintf(stderr, "[schur_fused_wide stamps, cycles since the first producer stamp; per round: producer-done consumer-done]\n");
-        for (int i = 0; i < 14; ++i) fprintf(stderr, "  it %2d: P %7lld  C %7lld\n", i, st[2 * i] - st[0], st[2 * i + 1] - st[0]);
-        fprintf(stderr, "  phases (cycles): prologue %lld | main loop %lld | fold U %lld | slab stores %lld | tail %lld | whole kernel %lld\n",
-                st[49] - st[48], st[50] - st[49], st[51] - st[50], st[52] - st[51], st[53] - st[52], st[53] - st[48]);
-        schur_debug = false;
-      }
+  // after a fused launch: the record it published is the current one, its gradient maxima the ones a decision reads next
+  void fused_launched(const FusedDecide& fd, double* gm_out) {
+    d_state.p = fd.st_out;
+    pending_decide = false;
+    gmax_cur = gm_out;
+  }
+  std::vector<long long> read_stamps(const DevBuf<long long>& b, size_t count) {
+    std::vector<long long> st(count);
+    HIPCHK(hipMemcpyAsync(st.data(), b.p, count * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    sync();
+    return st;
+  }
+  long long* fused_stamps() const { return (schur_debug && schur_debug_skip == 0) ? schur_dbg.p : nullptr; }
+  // SBA_SCHUR_DEBUG=k: the stamps of the k-th fused Schur launch on stderr
+  void print_fused_stamps(const char* kernel, const char* per, bool prologue) {
+    if (!schur_debug) return;
+    if (schur_debug_skip > 0) { --schur_debug_skip; return; }
+    const std::vector<long long> st = read_stamps(schur_dbg, 64);
+    fprintf(stderr, "[%s stamps, cycles since the first producer stamp; per %s: producer-done consumer-done]\n", kernel, per);
+    for (int i = 0; i < 14; ++i) fprintf(stderr, "  it %2d: P %7lld  C %7lld\n", i, st[2 * i] - st[0], st[2 * i + 1] - st[0]);
+    fprintf(stderr, "  phases (cycles): prologue %lld | main loop %lld | fold U %lld | slab stores %lld | tail %lld | whole kernel %lld\n",
+            st[49] - st[48], st[50] - st[49], st[51] - st[50], st[52] - st[51], st[53] - st[52], st[53] - st[48]);
+    if (prologue) {
+      fprintf(stderr, "  prologue (cycles): loads requested + LDS zeroed %lld | first barrier passed (record arrived) %lld | decision taken %lld | camera table in LDS %lld | producers set up %lld\n",
+              st[54] - st[48], st[55] - st[48], st[57] - st[48], st[56] - st[48], st[49] - st[48]);
+      if (st[58])
+        fprintf(stderr, "  decision (cycles since kernel start): partial sums folded %lld | record updated %lld\n", st[58] - st[48], st[59] - st[48]);
     }
+    schur_debug = false;
+  }
+#if SBA_NCP == 11
+  // one camera group: k_schur_fused_bf3 (f32) / k_schur_fused_f64
+  void launch_schur_fused() {
+    double* gm_out = nullptr;
+    const FusedDecide fd = make_fused_decide(gm_out);
+    const uint16_t* vis = rt.fused_masked ? vis_mask.p : (const uint16_t*)nullptr;
+    if constexpr (sizeof(T) == 4) {
+      hipLaunchKernelGGL(k_schur_fused_bf3, dim3(rt.ksplit), dim3(SCHUR_THREADS), SchurBf3Cfg::LDS_BYTES, stream,
+                         ps_lm(), fd, C, uv_pm.p, has_w ? w_pm.p : nullptr, pt_start.p, vis, N, rt.ksplit, D2p.p, gp.p, pfac.p,
+                         slabs.p, bpart.p, gdpart.p, cost_part.p, gm_out, fused_stamps());
+      fused_launched(fd, gm_out);
+      print_fused_stamps("schur_fused", "chunk", true);
+    } else {
+      hipLaunchKernelGGL(k_schur_fused_f64, dim3(rt.ksplit), dim3(SCHUR_THREADS), SchurF64Cfg::LDS_BYTES, stream,
+                         ps_lm(), fd, C, uv_pm.p, has_w ? w_pm.p : nullptr, pt_start.p, vis, N, rt.ksplit, D2p.p, gp.p, pfac.p,
+                         slabs.p, bpart.p, gdpart.p, cost_part.p, gm_out, fused_stamps());
+      fused_launched(fd, gm_out);
+      print_fused_stamps("schur_fused_f64", "chunk", false);
+    }
+  }
+#endif
+  // the instantiation of the wide kernels for this rig: go(NTW, PW) with wide_ntw(C) row tiles, the route's points per wave
+  template <typename F> void wide_dispatch(F&& go) const {
+    using std::integral_constant;
+    using P2 = integral_constant<int, 2>;
+    auto pw = [&](auto ntw) { if (rt.wide_pw == 3) go(ntw, integral_constant<int, 3>{}); else go(ntw, P2{}); };
+    switch (wide_ntw(C)) {
+      case 8: if constexpr (sizeof(T) == 4) pw(integral_constant<int, 8>{}); break;      // (fp64: 17 cameras and more, 12 tiles at least)
+      case 12: pw(integral_constant<int, 12>{}); break;
+      case 13: pw(integral_constant<int, 13>{}); break;
+      case 14: go(integral_constant<int, 14>{}, P2{}); break;
+      case 15: go(integral_constant<int, 15>{}, P2{}); break;
+      default: go(integral_constant<int, 16>{}, P2{}); break;
+    }
+  }
+  // k_schur_fused_wide (f32) / k_schur_fused_wide_f64: one launch, compact rows
+  void launch_schur_wide() {
+    double* gm_out = nullptr;
+    const FusedDecide fd = make_fused_decide(gm_out);
+    // sparse rigs: per (16-camera group, point) visibility mask + index of the point's first observation in the group -- the
+    // k_group_index tables with several groups, the one-group mask and the point's start otherwise
+    const bool tables = !dense;
+    const uint16_t* tmask = !tables ? nullptr : C > GROUP_CAMS ? grp_mask.p : vis_mask.p;
+    const int32_t* tstart = !tables ? nullptr : C > GROUP_CAMS ? grp_start.p : pt_start.p;
+    wide_dispatch([&](auto ntw_c, auto pw_c) {
+      constexpr int NTW = decltype(ntw_c)::value, PW = decltype(pw_c)::value;
+      if constexpr (sizeof(T) == 4) {
+        constexpr size_t lds = SchurWideCfg<NTW, PW>::LDS_BYTES;
+        hipLaunchKernelGGL((k_schur_fused_wide<NTW, PW>), dim3(rt.ksplit), dim3(SCHUR_THREADS), lds, stream,
+                           ps_lm(), fd, C, uv_pm.p, has_w ? w_pm.p : nullptr, tmask, tstart, N, rt.ksplit, D2p.p, gp.p, pfac.p, slabs.p,
+                           bpart.p, gdpart.p, cost_part.p, gm_out, fused_stamps());
+      } else {
+#if SBA_NCP == 11
+        constexpr int TS = NTW > 13 ? 2 : 1;      // = rt.wide_ts
+        constexpr size_t lds64 = SchurWide64Cfg<NTW, PW, TS>::LDS_BYTES;
+        hipLaunchKernelGGL((k_schur_fused_wide_f64<NTW, PW, TS>), dim3(rt.ksplit, TS), dim3(SCHUR_THREADS), lds64, stream,
+                           ps_lm(), fd, C, uv_pm.p, has_w ? w_pm.p : nullptr, tmask, tstart, N, rt.ksplit, D2p.p, gp.p, pfac.p, slabs.p,
+                           bpart.p, gdpart.p, cost_part.p, gm_out, fused_stamps());
+#endif
+      }
+    });
+    fused_launched(fd, gm_out);
+    if constexpr (sizeof(T) == 4) print_fused_stamps("schur_fused_wide", "round", false);
+    else print_fused_stamps("schur_fused_wide_f64", "chunk of 8 or 12 points", false);
   }
   template <bool PARTIAL> void launch_schur_kernels() {
     using CfgD = SchurSel<T, true>;
     using CfgO = SchurSel<T, false>;
+    const int ksplit = rt.ksplit;
     if constexpr (SCHUR_SYM<T>) {
       hipLaunchKernelGGL((k_schur_sym<T, true, PARTIAL>), dim3(ksplit, ngroups, CfgD::TS), dim3(CfgD::THREADS), CfgD::LDS_BYTES,
                          stream, ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pi_pm.p, pt_start.p, N,
@@ -939,9 +972,7 @@ struct Engine : EngineBase {
                          (const uint16_t*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr,
                          grp_indexed ? grp_mask.p : (const uint16_t*)nullptr, grp_indexed ? grp_start.p : (const int32_t*)nullptr);
       if (schur_debug) {
-        std::vector<long long> st(64);
-        HIPCHK(hipMemcpyAsync(st.data(), schur_dbg.p, 64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-        sync();
+        const std::vector<long long> st = read_stamps(schur_dbg, 64);
         fprintf(stderr, "[schur_sym stamps, cycles; per chunk: produce-done after-barrier consume-done]\n");
         for (int i = 0; i < 8; ++i)
           fprintf(stderr, "  it %2d: P %7lld  B %7lld  C %7lld\n", i, st[3 * i] - st[0], st[3 * i + 1] - st[0], st[3 * i + 2] - st[0]);
@@ -954,75 +985,62 @@ struct Engine : EngineBase {
                            pair_ga.p, pair_gb.p, ngroups, ksplit, (int)dense, slabs.p, bpart.p, nullptr,
                            (const uint16_t*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr,
                            grp_indexed ? grp_mask.p : (const uint16_t*)nullptr, grp_indexed ? grp_start.p : (const int32_t*)nullptr);
-      return;
     } else {
-    if (diag_pairs_bf3()) {
-      hipLaunchKernelGGL(k_schur_diag_bf3, dim3(ksplit, ngroups), dim3(SCHUR_THREADS), SchurPairCfg::LDS_BYTES, stream,
-                         ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, grp_mask.p, grp_start.p, N, pfac.p, pair_ga.p, 0, ksplit,
-                         slabs.p, bpart.p, pairs_fold_u ? gdpart.p : (double*)nullptr);
-    } else
-    hipLaunchKernelGGL((k_schur<T, true, PARTIAL>), dim3(ksplit, ngroups, CfgD::TS), dim3(CfgD::THREADS), CfgD::LDS_BYTES,
-                       stream, ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pi_pm.p, pt_start.p, N,
-                       pfac.p, pair_ga.p, pair_gb.p, 0, ksplit, (int)dense, slabs.p, bpart.p,
-                       schur_debug ? schur_dbg.p : nullptr, grp_indexed ? grp_mask.p : (const uint16_t*)nullptr,
-                       grp_indexed ? grp_start.p : (const int32_t*)nullptr);
-    if (schur_debug) {
-      std::vector<long long> st(64);
-      HIPCHK(hipMemcpyAsync(st.data(), schur_dbg.p, 64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-      sync();
-      fprintf(stderr, "[schur stamps, cycles since first barrier; per chunk: producer-done consumer-done barrier-out]\n");
-      for (int i = 0; i < 14; ++i)
-        fprintf(stderr, "  it %2d: P %7lld  C %7lld  out %7lld\n", i, st[3 * i] - st[2], st[3 * i + 1] - st[2], st[3 * i + 2] - st[2]);
-      schur_debug = false;
-    }
-    if (npairs > ngroups && offdiag_pairs_bf3()) {
-      hipLaunchKernelGGL(k_schur_offdiag_bf3, dim3(ksplit, npairs - ngroups), dim3(SCHUR_THREADS), SchurBf3OffCfg::LDS_BYTES, stream,
-                         ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, grp_mask.p, grp_start.p, N, pfac.p, pair_ga.p, pair_gb.p,
-                         ngroups, ksplit, slabs.p);
-    } else
-    if (npairs > ngroups)
-      hipLaunchKernelGGL((k_schur<T, false, PARTIAL>), dim3(ksplit, npairs - ngroups, CfgO::TS), dim3(CfgO::THREADS),
-                         CfgO::LDS_BYTES, stream, ps_lm(), d_state.p, C, uv_pm.p,
-                         has_w ? w_pm.p : nullptr, ci_pm.p, pi_pm.p, pt_start.p, N, pfac.p,
-                         pair_ga.p, pair_gb.p, ngroups, ksplit, (int)dense, slabs.p, bpart.p, nullptr,
-                         grp_indexed ? grp_mask.p : (const uint16_t*)nullptr, grp_indexed ? grp_start.p : (const int32_t*)nullptr);
+      if (pairs_bf3())
+        hipLaunchKernelGGL(k_schur_diag_bf3, dim3(ksplit, ngroups), dim3(SCHUR_THREADS), SchurPairCfg::LDS_BYTES, stream,
+                           ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, grp_mask.p, grp_start.p, N, pfac.p, pair_ga.p, 0, ksplit,
+                           slabs.p, bpart.p, rt.pairs_fold_u ? gdpart.p : (double*)nullptr);
+      else
+        hipLaunchKernelGGL((k_schur<T, true, PARTIAL>), dim3(ksplit, ngroups, CfgD::TS), dim3(CfgD::THREADS), CfgD::LDS_BYTES,
+                           stream, ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pi_pm.p, pt_start.p, N,
+                           pfac.p, pair_ga.p, pair_gb.p, 0, ksplit, (int)dense, slabs.p, bpart.p,
+                           schur_debug ? schur_dbg.p : nullptr, grp_indexed ? grp_mask.p : (const uint16_t*)nullptr,
+                           grp_indexed ? grp_start.p : (const int32_t*)nullptr);
+      if (schur_debug) {
+        const std::vector<long long> st = read_stamps(schur_dbg, 64);
+        fprintf(stderr, "[schur stamps, cycles since first barrier; per chunk: producer-done consumer-done barrier-out]\n");
+        for (int i = 0; i < 14; ++i)
+          fprintf(stderr, "  it %2d: P %7lld  C %7lld  out %7lld\n", i, st[3 * i] - st[2], st[3 * i + 1] - st[2], st[3 * i + 2] - st[2]);
+        schur_debug = false;
+      }
+      if (npairs > ngroups) {
+        if (pairs_bf3())
+          hipLaunchKernelGGL(k_schur_offdiag_bf3, dim3(ksplit, npairs - ngroups), dim3(SCHUR_THREADS), SchurBf3OffCfg::LDS_BYTES, stream,
+                             ps_lm(), d_state.p, C, uv_pm.p, has_w ? w_pm.p : nullptr, grp_mask.p, grp_start.p, N, pfac.p, pair_ga.p, pair_gb.p,
+                             ngroups, ksplit, slabs.p);
+        else
+          hipLaunchKernelGGL((k_schur<T, false, PARTIAL>), dim3(ksplit, npairs - ngroups, CfgO::TS), dim3(CfgO::THREADS),
+                             CfgO::LDS_BYTES, stream, ps_lm(), d_state.p, C, uv_pm.p,
+                             has_w ? w_pm.p : nullptr, ci_pm.p, pi_pm.p, pt_start.p, N, pfac.p,
+                             pair_ga.p, pair_gb.p, ngroups, ksplit, (int)dense, slabs.p, bpart.p, nullptr,
+                             grp_indexed ? grp_mask.p : (const uint16_t*)nullptr, grp_indexed ? grp_start.p : (const int32_t*)nullptr);
+      }
     }
   }
-  // dense visibility with one camera group: the row-reduction kernel (any dtype); its partial rows are per workgroup
-  bool backsub_masked = false;       // sparse one-group rig dense enough for the lane = (point, camera) back substitution (visibility mask)
-  bool backsub_wide = false;         // 17 .. 23 cameras: k_backsub_dense<T, 32> / <T, 0>
-  bool backsub_pack = false;
-  bool backsub_wave = false;         // 33 .. 128 cameras: k_backsub_dense<T, 64>
-  int linp_lw = 0;                   // 24 .. 128 cameras with (point, camera) tables: k_linearize_points_wave<T, 32 / 64>; 0 = k_linearize_points
-  bool linp_pf = true;               // ... which also forms the point factors (SBA_LINP_PF=0: k_point_factor in a launch of its own)
-  int nlinp = 0;                     // ... its (persistent) workgroups = entries of cost_part / gmax_part
-  int n_linp_blocks() const { return linp_lw ? nlinp : nblk; }
-  bool backsub_dense() const { return dense_one_group || backsub_masked || backsub_wide || backsub_wave; }
-  int n_trial_parts() const { return backsub_dense() ? nbs_dense : nblk; }
   void launch_backsub_trial() {
     if (nblk == 0) return;
-    if (backsub_pack) {
-      hipLaunchKernelGGL((k_backsub_dense<T, 0>), dim3(nbs_dense), dim3(PM_BLOCK), 0, stream, ps_lm(), C, uv_pm.p,
-                         has_w ? w_pm.p : nullptr, N, pfac.p, gp.p, D2p.p, delta_c.p, d_state.p, trial_part.p, nbs_dense,
-                         dense ? (const uint16_t*)nullptr : grp_mask.p, dense ? (const int32_t*)nullptr : grp_start.p);
+    const int nbs = rt.nbs_dense;
+    const uint16_t* gm = dense ? (const uint16_t*)nullptr : grp_mask.p;
+    const int32_t* gs = dense ? (const int32_t*)nullptr : grp_start.p;
+    if (rt.backsub_pack) {
+      hipLaunchKernelGGL((k_backsub_dense<T, 0>), dim3(nbs), dim3(PM_BLOCK), 0, stream, ps_lm(), C, uv_pm.p,
+                         has_w ? w_pm.p : nullptr, N, pfac.p, gp.p, D2p.p, delta_c.p, d_state.p, trial_part.p, nbs, gm, gs);
       return;
     }
-    if (backsub_wave) {
-      hipLaunchKernelGGL((k_backsub_dense<T, 64>), dim3(nbs_dense), dim3(PM_BLOCK), 0, stream, ps_lm(), C, uv_pm.p,
-                         has_w ? w_pm.p : nullptr, N, pfac.p, gp.p, D2p.p, delta_c.p, d_state.p, trial_part.p, nbs_dense,
-                         dense ? (const uint16_t*)nullptr : grp_mask.p, dense ? (const int32_t*)nullptr : grp_start.p);
+    if (rt.backsub_wave) {
+      hipLaunchKernelGGL((k_backsub_dense<T, 64>), dim3(nbs), dim3(PM_BLOCK), 0, stream, ps_lm(), C, uv_pm.p,
+                         has_w ? w_pm.p : nullptr, N, pfac.p, gp.p, D2p.p, delta_c.p, d_state.p, trial_part.p, nbs, gm, gs);
       return;
     }
-    if (backsub_wide) {
-      hipLaunchKernelGGL((k_backsub_dense<T, 32>), dim3(nbs_dense), dim3(PM_BLOCK), 0, stream, ps_lm(), C, uv_pm.p,
-                         has_w ? w_pm.p : nullptr, N, pfac.p, gp.p, D2p.p, delta_c.p, d_state.p, trial_part.p, nbs_dense,
-                         dense ? (const uint16_t*)nullptr : grp_mask.p, dense ? (const int32_t*)nullptr : grp_start.p);
+    if (rt.backsub_wide) {
+      hipLaunchKernelGGL((k_backsub_dense<T, 32>), dim3(nbs), dim3(PM_BLOCK), 0, stream, ps_lm(), C, uv_pm.p,
+                         has_w ? w_pm.p : nullptr, N, pfac.p, gp.p, D2p.p, delta_c.p, d_state.p, trial_part.p, nbs, gm, gs);
       return;
     }
-    if (backsub_dense()) {
-      hipLaunchKernelGGL(k_backsub_dense<T>, dim3(nbs_dense), dim3(PM_BLOCK), 0, stream, ps_lm(), C, uv_pm.p,
-                         has_w ? w_pm.p : nullptr, N, pfac.p, gp.p, D2p.p, delta_c.p, d_state.p, trial_part.p, nbs_dense,
-                         dense_one_group ? (const uint16_t*)nullptr : vis_mask.p, dense_one_group ? (const int32_t*)nullptr : pt_start.p);
+    if (backsub_dense()) {      // one group: dense, or through the visibility mask
+      hipLaunchKernelGGL(k_backsub_dense<T>, dim3(nbs), dim3(PM_BLOCK), 0, stream, ps_lm(), C, uv_pm.p,
+                         has_w ? w_pm.p : nullptr, N, pfac.p, gp.p, D2p.p, delta_c.p, d_state.p, trial_part.p, nbs,
+                         rt.dense_one_group ? (const uint16_t*)nullptr : vis_mask.p, rt.dense_one_group ? (const int32_t*)nullptr : pt_start.p);
       return;
     }
     const size_t lds = (size_t)PM_BLOCK * 6 * sizeof(double) + (2 * (size_t)C * CAMPRE + (size_t)C * NCP) * sizeof(T);
@@ -1208,18 +1226,13 @@ struct Engine : EngineBase {
     if (comm) { err = "the handle already has an RCCL communicator (the two exchanges are exclusive)"; return SBA_ERR_STATE; }
     HIPCHK(hipSetDevice(device));
     ipc_L = IpcLayout::make(n);
-    if (const char* e = getenv("SBA_IPC_TIMEOUT_S")) {
-      char* end = nullptr;
-      const double sec = strtod(e, &end);
-      if (end != e && sec > 0 && sec < 3600) ipc_timeout_ticks = (long long)(sec * 1e8);
-    }
     void* pmem = nullptr;
     // uncached: the peers read what this rank's kernels wrote without a kernel boundary of THEIR stream in between.  A cached
     // allocation would still work between ranks that share one device (one L2) but not between GPUs, so it is never taken
     // silently: SBA_IPC_ALLOW_CACHED=1 asks for it (one-card rehearsals on a stack without the uncached flag) and says so.
     if (hipExtMallocWithFlags(&pmem, ipc_L.total * sizeof(double), hipDeviceMallocUncached) != hipSuccess) {
       (void)hipGetLastError();
-      if (!getenv("SBA_IPC_ALLOW_CACHED")) {
+      if (!kn.ipc_allow_cached) {
         err = "sba_ipc_export: uncached device memory (hipDeviceMallocUncached) is not available; the one-shot exchange needs it between GPUs "
               "(SBA_IPC_ALLOW_CACHED=1 accepts cached memory for ranks that share ONE device)";
         return SBA_ERR_HIP;
@@ -1290,7 +1303,7 @@ struct Engine : EngineBase {
   }
   void ipc_gate(int kind, unsigned long long seq, LMState* st, size_t copy_off, int ncopy, double* dst) {
     hipLaunchKernelGGL(k_ipc_gate, dim3(1), dim3(64), 0, stream, ipc_ptrs.p, comm_n, ipc_L.flag_of(kind, (int)(seq & 1)), seq, st,
-                       st ? (int*)nullptr : ipc_fail.p, copy_off, ncopy, dst, ipc_timeout_ticks);
+                       st ? (int*)nullptr : ipc_fail.p, copy_off, ncopy, dst, kn.ipc_timeout_ticks);
   }
   void comm_reduce(double* v, int count, int op) {
     for (int i = 0; i < count; ++i) h_comm[i] = v[i];
@@ -1330,7 +1343,6 @@ struct Engine : EngineBase {
     pending_decide = false;
     prof_on = opts.reserved[0] != 0;
     for (int k = 0; k < KP_N; ++k) { prof_us[k] = 0; prof_cnt[k] = 0; }
-    pslot = 0;
     for (auto& u : pev_used) u = false;
     if (opts.mode < SBA_MODE_FULL || opts.mode > SBA_MODE_TRANSFORM_SQ) { err = "unsupported mode"; return SBA_ERR_UNSUPPORTED; }
     if (opts.mode == SBA_MODE_SHARED_INTR) build_tie_tables();
@@ -1424,13 +1436,13 @@ struct Engine : EngineBase {
     poll_clean = false;
     if (!bf3_path()) flush_decide();
     if (sq_mode()) { launch_sq_linearize(d_state.p); return SBA_OK; }
-    if (fused()) return SBA_OK;          // k_schur_fused linearises
+    if (fused()) return SBA_OK;          // the fused Schur kernel linearises
     if (!lin_pts()) {                    // (f64 one-group rigs: k_schur_sym<LIN> linearises the points)
       prof_begin(KP_LINP);
       launch_linearize_points(d_state.p);
       prof_end(KP_LINP);
     }
-    if (h_state->free_cams && !(pairs_fold_u && diag_pairs_bf3())) { prof_begin(KP_LINC); launch_linearize_cams(d_state.p); prof_end(KP_LINC); }
+    if (h_state->free_cams && !rt.pairs_fold_u) { prof_begin(KP_LINC); launch_linearize_cams(d_state.p); prof_end(KP_LINC); }
     return SBA_OK;
   }
 
@@ -1452,17 +1464,18 @@ struct Engine : EngineBase {
     prof_begin(KP_REDUCE);
     {
       const int fc = (int)h_state->free_cams;
-      const bool wide = fused() && fused_wide;
+      const bool wide = fused() && rt.fused_wide;
       // (wide: one slab per workgroup with ntw (ntw + 1) / 2 tiles, passed as one "pair")
       // tile slots per pair the grid covers: one pair -> its own tile count (no workgroups that return at once)
       const int ntw = wide_ntw(C);
       const int nt_launch = wide ? ntw * (ntw + 1) / 2 : npairs == 1 ? GROUP_TILES * (GROUP_TILES + 1) / 2 : GROUP_TILES * GROUP_TILES;
       const int np_arg = wide ? 1 : npairs;
       const int nblocks = (fc ? 4 * nt_launch * np_arg + (n + 15) / 16 : 0) + 1;
-      hipLaunchKernelGGL(k_build_exchange<T>, dim3(nblocks), dim3(1024), 0, stream, slabs.p, bpart.p, ksplit, pair_ga.p,
+      // slab tiles: 3 = the wide kernels' compact rows, 1 = parameter-major (the bf16 kernels), 0 = camera-major
+      const int emajor_mode = wide ? 3 : ((fused() && sizeof(T) == 4) || pairs_bf3()) ? 1 : 0;
+      hipLaunchKernelGGL(k_build_exchange<T>, dim3(nblocks), dim3(1024), 0, stream, slabs.p, bpart.p, rt.ksplit, pair_ga.p,
                          pair_gb.p, np_arg, U.p, gc.p, cost_part.p, n_lin_parts(), C, fc, E, d_state.p,
-                         (fused() || (pairs_fold_u && diag_pairs_bf3())) ? gdpart.p : (const double*)nullptr, Pk, (fused() && fused_wide) ? 3 : (fused() && fused_bf3 && sizeof(T) == 4) ? 1 : (diag_pairs_bf3() ? (offdiag_pairs_bf3() ? 1 : 2) : 0),
-                         nt_launch);
+                         (fused() || rt.pairs_fold_u) ? gdpart.p : (const double*)nullptr, Pk, emajor_mode, nt_launch);
     }
     prof_end(KP_REDUCE);
     return SBA_OK;
@@ -1470,7 +1483,7 @@ struct Engine : EngineBase {
 
   // A = S + lam D (n_sys x n_sys, in E) -> chol_sol = A^-1 rhs, chol_info != 0 when A is not positive definite
   // factorisation, both substitutions and the LM epilogue (k_chol_epilogue's work) of a large reduced system
-  void launch_chol_big(double* Esys, int n_sys, bool tied) {
+  void launch_chol_big(double* Esys, int n_sys, bool tied, CholRoute route) {
     const int npad = cholbig_npad(n_sys), nbr = npad / BB, nbx = (n_sys + BB - 1) / BB;
     if (chol_W.n < (size_t)npad * npad) {
       chol_W.alloc((size_t)npad * npad); chol_Minv.alloc((size_t)nbr * BB * BB); chol_Ld.alloc((size_t)nbr * BB * BB);
@@ -1481,8 +1494,7 @@ struct Engine : EngineBase {
     }
     if (chol_sol.n < (size_t)n_sys) { chol_sol.alloc(n_sys); chol_info.alloc(1); }
     const size_t lds = (size_t)CHOLBIG_LDS_BLOCKS * CBS * sizeof(double);
-    const bool dag = chol_big_dag && !card_shared && chol_big_back_one && nbr <= chol_dag_max_nbr && nbx <= CHOLBIG_MAX_NBX;     // (the per-block back substitution reads the dense copies)
-    const bool dag32 = dag && sizeof(T) == 4 && chol_f32;
+    const bool dag = route != CholRoute::BIG_LAUNCHES, dag32 = route == CholRoute::BIG_DAG_F32;
     if (dag) {
       // factorisation (and k_chol_big_prepare's work) in one launch: a walker workgroup on the diagonal, workgroup = tile behind it,
       // columns handed over through flags (sba_chol_big.hpp).  fp32 engine: on f32 lanes first, the f64 instance behind it only
@@ -1494,14 +1506,12 @@ struct Engine : EngineBase {
       if (dag32)
         hipLaunchKernelGGL(k_chol_big_dag<float>, grid, dim3(CHOLBIG_THREADS), (size_t)CHOLBIG_LDS_BLOCKS * CholLay<float>::BS * sizeof(float), stream,
                            Esys, n_sys, d_state.p, D2c.p, reinterpret_cast<float*>(chol_W.p), npad, reinterpret_cast<float*>(chol_Mimg.p),
-                           chol_dag_flags.p, ++chol_dag_epoch, chol_info.p, 0, chol_f32_tau, chol_debug ? chol_dbg.p : nullptr);
+                           chol_dag_flags.p, ++chol_dag_epoch, chol_info.p, 0, kn.chol_f32_tau, chol_debug ? chol_dbg.p : nullptr);
       hipLaunchKernelGGL(k_chol_big_dag<double>, grid, dim3(CHOLBIG_THREADS), lds, stream, Esys, n_sys, d_state.p, D2c.p, chol_W.p, npad,
                          chol_Mimg.p, chol_dag_flags.p, ++chol_dag_epoch, chol_info.p, dag32 ? 1 : 0, 0.0,
                          (chol_debug && !dag32) ? chol_dbg.p : nullptr);
       if (chol_debug) {
-        std::vector<long long> sv(8 * (CHOLDAG_MAX_NBR + 1));
-        HIPCHK(hipMemcpyAsync(sv.data(), chol_dbg.p, sv.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
-        sync();
+        const std::vector<long long> sv = read_stamps(chol_dbg, 8 * (CHOLDAG_MAX_NBR + 1));
         fprintf(stderr, "[chol_dag%s, the walker, x10 ns: wait for W(c,c-1), W(c,c) | load | panel | downdate | factor+inverse | image stored | flag]\n", dag32 ? " on f32 lanes" : "");
         for (int cc = 0; cc < nbr; ++cc) {
           const long long* v = sv.data() + 8 * cc;
@@ -1520,20 +1530,10 @@ struct Engine : EngineBase {
                            chol_Minv.p, chol_Ld.p, chol_info.p, d_state.p);
       }
     }
-    if (chol_big_back_one && nbx <= CHOLBIG_MAX_NBX) {
-      // the whole back substitution in one launch: block row = workgroup, x_b handed over as its own flag; block row 0 runs the epilogue
-      hipLaunchKernelGGL(k_chol_big_back_all<T>, dim3(nbx), dim3(256), 0, stream, (const void*)chol_W.p, npad, n_sys, chol_Ld.p, chol_Minv.p,
-                         chol_yv.p, ++chol_epoch, chol_sol.p, chol_info.p, d_state.p, dag ? (const void*)chol_Mimg.p : (const void*)nullptr,
-                         dag32 ? 1 : 0, Esys, C, D2c.p, ps_lm(), delta_c.p, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr);
-      return;
-    }
-    hipLaunchKernelGGL(k_chol_big_back_init, dim3((npad + 255) / 256), dim3(256), 0, stream, chol_W.p, npad, n_sys, chol_Ld.p,
-                       chol_yv.p, d_state.p);
-    for (int b = nbx - 1; b >= 0; --b)
-      hipLaunchKernelGGL(k_chol_big_back, dim3(b + 1), dim3(256), 0, stream, chol_W.p, npad, b, n_sys, chol_Minv.p, chol_yv.p,
-                         chol_sol.p, d_state.p);
-    hipLaunchKernelGGL(k_chol_epilogue<T>, dim3(1), dim3(1024), 0, stream, Esys, C, n_sys, d_state.p, D2c.p, ps_lm(), delta_c.p,
-                       chol_sol.p, chol_info.p, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr);
+    // the whole back substitution in one launch: block row = workgroup, x_b handed over as its own flag; block row 0 runs the epilogue
+    hipLaunchKernelGGL(k_chol_big_back_all<T>, dim3(nbx), dim3(256), 0, stream, (const void*)chol_W.p, npad, n_sys, chol_Ld.p, chol_Minv.p,
+                       chol_yv.p, ++chol_epoch, chol_sol.p, chol_info.p, d_state.p, dag ? (const void*)chol_Mimg.p : (const void*)nullptr,
+                       dag32 ? 1 : 0, Esys, C, D2c.p, ps_lm(), delta_c.p, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr);
   }
 
   // scal == nullptr: single rank, the partials are folded inside k_decide and no scalar exchange is needed
@@ -1555,105 +1555,99 @@ struct Engine : EngineBase {
                            E_tied.p, d_state.p);
         Esys = E_tied.p;
       }
-      if (chol_ll && (n_sys > CHOL_LDS_MAX_N || chol_ll_all) && n_sys <= CLL_MAX_NB * CB && C * NCP <= CLL_THREADS) {
-        // up to 256 unknowns (23 cameras): left-looking, factor on chip (sba_chol_ll.hpp)
-        const int nb = (n_sys + CB - 1) / CB;
-        if (chol_work.n < (size_t)nb * (nb + 1) / 2 * CB * CB) chol_work.alloc((size_t)CLL_MAX_NB * (CLL_MAX_NB + 1) / 2 * CB * CB);
-        if (chol_debug && chol_dbg.n < 128) { chol_dbg.alloc(128); chol_dbg.zero(stream); }
-        // fp32 engine (round 4): the right-looking all-in-LDS kernel on f32 lanes in front of it (the f32 triangle of up to 16 block
-        // rows fits the LDS: 20-float rows up to 14 block rows, 17-float rows at 15 and 16); the f64 kernel then only runs when that
-        // factorisation refused the system (LMState::chol_retry)
-        int only_if_retry = 0;
-        if constexpr (sizeof(T) == 4) {
-          if (chol_f32 && !chol_ll_all && n_sys > CHOL_LDS_MAX_N && C * NCP <= CHOLB_LDS_THREADS) {
-            only_if_retry = 1;
-            if (nb <= 14) {
-              const size_t lds32 = ((size_t)(nb * (nb + 1) / 2) * CB * 20 + 2 * (size_t)nb * CB) * sizeof(float);
-              hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 20>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
-                                 ps_lm(), delta_c.p, n_sys, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr,
-                                 (long long*)nullptr, 1, chol_f32_tau);
-            } else {
-              const size_t lds32 = ((size_t)(nb * (nb + 1) / 2) * CB * 17 + 2 * (size_t)nb * CB) * sizeof(float);
-              hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 17>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
-                                 ps_lm(), delta_c.p, n_sys, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr,
-                                 (long long*)nullptr, 1, chol_f32_tau);
+      const int32_t* tie = tied ? tie_map.p : nullptr;
+      const int32_t* first = tied ? tie_first.p : nullptr;
+      const int nb = (n_sys + CB - 1) / CB;
+      const CholRoute route = chol_route<T>(n_sys, n, kn, card_shared);
+      switch (route) {
+        case CholRoute::LL:
+        case CholRoute::LL_F32: {
+          // up to 256 unknowns (23 cameras): left-looking, factor on chip (sba_chol_ll.hpp)
+          if (chol_work.n < (size_t)nb * (nb + 1) / 2 * CB * CB) chol_work.alloc((size_t)CLL_MAX_NB * (CLL_MAX_NB + 1) / 2 * CB * CB);
+          if (chol_debug && chol_dbg.n < 128) { chol_dbg.alloc(128); chol_dbg.zero(stream); }
+          // fp32 engine (round 4): the right-looking all-in-LDS kernel on f32 lanes in front of it (the f32 triangle of up to 16 block
+          // rows fits the LDS: 20-float rows up to 14 block rows, 17-float rows at 15 and 16); the f64 kernel then only runs when that
+          // factorisation refused the system (LMState::chol_retry)
+          if constexpr (sizeof(T) == 4) {
+            if (route == CholRoute::LL_F32) {
+              if (nb <= 14) {
+                const size_t lds32 = ((size_t)(nb * (nb + 1) / 2) * CB * 20 + 2 * (size_t)nb * CB) * sizeof(float);
+                hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 20>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
+                                   ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau);
+              } else {
+                const size_t lds32 = ((size_t)(nb * (nb + 1) / 2) * CB * 17 + 2 * (size_t)nb * CB) * sizeof(float);
+                hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 17>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
+                                   ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau);
+              }
             }
           }
-        }
-        hipLaunchKernelGGL(k_cholesky_ll<T>, dim3(1), dim3(CLL_THREADS), CLL_LDS_BYTES, stream, Esys, C, d_state.p, D2c.p,
-                           ps_lm(), delta_c.p, n_sys, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr, chol_work.p,
-                           chol_debug ? chol_dbg.p : nullptr, only_if_retry);
-        if (chol_debug) {
-          std::vector<long long> st(128);
-          HIPCHK(hipMemcpyAsync(st.data(), chol_dbg.p, 128 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-          sync();
-          if (nb > 6) {
-            const long long x0 = st[2 + 2 * 3], y0 = st[3 + 2 * 3];      // start of X_3 / Y_3 (thread 0)
-            fprintf(stderr, "[chol_ll step 3, cycles after the step's barrier, per wave] X done:");
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[64 + w] - x0);
-            fprintf(stderr, " | Y done:");
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[72 + w] - y0);
-            fprintf(stderr, "\n[chol_ll back substitution, block row 5] x done (per wave, from wave 0's):");
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[80 + w] - st[80]);
-            fprintf(stderr, " | barrier passed %lld | update done:", st[96] - st[80]);
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[88 + w] - st[96]);
-            fprintf(stderr, " | barrier passed %lld\n", st[97] - st[96]);
+          hipLaunchKernelGGL(k_cholesky_ll<T>, dim3(1), dim3(CLL_THREADS), CLL_LDS_BYTES, stream, Esys, C, d_state.p, D2c.p,
+                             ps_lm(), delta_c.p, n_sys, tie, first, chol_work.p, chol_debug ? chol_dbg.p : nullptr,
+                             route == CholRoute::LL_F32 ? 1 : 0);
+          if (chol_debug) {
+            const std::vector<long long> st = read_stamps(chol_dbg, 128);
+            if (nb > 6) {
+              const long long x0 = st[2 + 2 * 3], y0 = st[3 + 2 * 3];      // start of X_3 / Y_3 (thread 0)
+              fprintf(stderr, "[chol_ll step 3, cycles after the step's barrier, per wave] X done:");
+              for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[64 + w] - x0);
+              fprintf(stderr, " | Y done:");
+              for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[72 + w] - y0);
+              fprintf(stderr, "\n[chol_ll back substitution, block row 5] x done (per wave, from wave 0's):");
+              for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[80 + w] - st[80]);
+              fprintf(stderr, " | barrier passed %lld | update done:", st[96] - st[80]);
+              for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[88 + w] - st[96]);
+              fprintf(stderr, " | barrier passed %lld\n", st[97] - st[96]);
+            }
+            fprintf(stderr, "[chol_ll stamps, cycles] setup %lld  chol0 %lld |", st[1] - st[0], st[2] - st[1]);
+            for (int j = 0; j < nb; ++j) fprintf(stderr, " X%d %lld Y%d %lld |", j, st[3 + 2 * j] - st[2 + 2 * j], j, st[4 + 2 * j] - st[3 + 2 * j]);
+            fprintf(stderr, " backsub %lld  epilogue %lld  total %lld\n", st[3 + 2 * nb] - st[2 + 2 * nb], st[4 + 2 * nb] - st[3 + 2 * nb], st[4 + 2 * nb] - st[0]);
+            chol_debug = false;
           }
-          fprintf(stderr, "[chol_ll stamps, cycles] setup %lld  chol0 %lld |", st[1] - st[0], st[2] - st[1]);
-          for (int j = 0; j < nb; ++j) fprintf(stderr, " X%d %lld Y%d %lld |", j, st[3 + 2 * j] - st[2 + 2 * j], j, st[4 + 2 * j] - st[3 + 2 * j]);
-          fprintf(stderr, " backsub %lld  epilogue %lld  total %lld\n", st[3 + 2 * nb] - st[2 + 2 * nb], st[4 + 2 * nb] - st[3 + 2 * nb], st[4 + 2 * nb] - st[0]);
-          chol_debug = false;
+          break;
         }
-      } else if (n_sys <= CHOL_LDS_MAX_N && !chol_old && C * NCP <= CHOLB_LDS_THREADS) {
-        const int nb = (n_sys + CB - 1) / CB;
-        const size_t lds = ((size_t)(nb * (nb + 1) / 2) * CBS + 2 * (size_t)nb * CB) * sizeof(double);
-        if (chol_debug && chol_dbg.n == 0) { chol_dbg.alloc(64); }
-        hipLaunchKernelGGL(k_cholesky_blocked<T>, dim3(1), dim3(CHOLB_LDS_THREADS), lds, stream, Esys, C, d_state.p, D2c.p,
-                           ps_lm(), delta_c.p, n_sys, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr,
-                           chol_debug ? chol_dbg.p : nullptr, (sizeof(T) == 4 && chol_f32) ? 1 : 0, chol_f32_tau);
-        if (chol_debug) {
-          std::vector<long long> st(64);
-          HIPCHK(hipMemcpyAsync(st.data(), chol_dbg.p, 64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-          sync();
-          fprintf(stderr, "[chol stamps, cycles] load %lld  chol0 %lld |", st[1] - st[0], st[2] - st[1]);
-          for (int j = 0; j < nb; ++j) fprintf(stderr, " B%d %lld C%d %lld |", j, st[3 + 2 * j] - st[2 + 2 * j], j, st[4 + 2 * j] - st[3 + 2 * j]);
-          fprintf(stderr, " backsub %lld  epilogue %lld  total %lld\n", st[3 + 2 * nb] - st[2 + 2 * nb], st[4 + 2 * nb] - st[3 + 2 * nb], st[4 + 2 * nb] - st[0]);
-          fprintf(stderr, "[chol C0, cycles after B0's barrier, per wave]");
-          for (int w = 0; w < CHOLB_LDS_THREADS / 64; ++w) fprintf(stderr, " %lld", st[40 + w] - st[3]);
-          fprintf(stderr, "\n");
-          chol_debug = false;
+        case CholRoute::BLOCKED: {
+          const size_t lds = ((size_t)(nb * (nb + 1) / 2) * CBS + 2 * (size_t)nb * CB) * sizeof(double);
+          if (chol_debug && chol_dbg.n == 0) { chol_dbg.alloc(64); }
+          hipLaunchKernelGGL(k_cholesky_blocked<T>, dim3(1), dim3(CHOLB_LDS_THREADS), lds, stream, Esys, C, d_state.p, D2c.p,
+                             ps_lm(), delta_c.p, n_sys, tie, first, chol_debug ? chol_dbg.p : nullptr, (sizeof(T) == 4 && kn.chol_f32) ? 1 : 0,
+                             kn.chol_f32_tau);
+          if (chol_debug) {
+            const std::vector<long long> st = read_stamps(chol_dbg, 64);
+            fprintf(stderr, "[chol stamps, cycles] load %lld  chol0 %lld |", st[1] - st[0], st[2] - st[1]);
+            for (int j = 0; j < nb; ++j) fprintf(stderr, " B%d %lld C%d %lld |", j, st[3 + 2 * j] - st[2 + 2 * j], j, st[4 + 2 * j] - st[3 + 2 * j]);
+            fprintf(stderr, " backsub %lld  epilogue %lld  total %lld\n", st[3 + 2 * nb] - st[2 + 2 * nb], st[4 + 2 * nb] - st[3 + 2 * nb], st[4 + 2 * nb] - st[0]);
+            fprintf(stderr, "[chol C0, cycles after B0's barrier, per wave]");
+            for (int w = 0; w < CHOLB_LDS_THREADS / 64; ++w) fprintf(stderr, " %lld", st[40 + w] - st[3]);
+            fprintf(stderr, "\n");
+            chol_debug = false;
+          }
+          break;
         }
-      } else if (n_sys <= CHOL_LDS_MAX_N) {
-        const size_t lds = (size_t)n_sys * (n_sys + 1) / 2 * sizeof(double);
-        hipLaunchKernelGGL((k_cholesky_solve<true, T>), dim3(1), dim3(CHOL_THREADS), lds, stream, Esys, C, d_state.p, D2c.p,
-                           ps_lm(), delta_c.p, n_sys, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr);
-      } else if (n_sys > chol_big_min_n && !chol_old) {
-        // 47+ cameras: multi-workgroup right-looking factorisation, one launch per 64-wide block column (sba_chol_big.hpp)
-        launch_chol_big(Esys, n_sys, tied);
-      } else if (n_sys <= CS_MAX_NB * CB && !chol_old) {
-        // 17 .. 46 cameras: one workgroup, left-looking, finished block columns streamed through L2
-        const int nb = (n_sys + CB - 1) / CB;
-        if (chol_sol.n < (size_t)n_sys) { chol_sol.alloc(n_sys); chol_info.alloc(1); }
-        if (chol_work.n < (size_t)nb * (nb + 1) / 2 * CB * CB) chol_work.alloc((size_t)nb * (nb + 1) / 2 * CB * CB);
-        // panel (nb blocks) + rhs + as much staging as the 150 KB budget leaves (fewer, larger streaming rounds)
-        const size_t fixed = ((size_t)nb * CBS + (size_t)nb * CB) * sizeof(double);
-        const int scap = std::min(64, std::max(nb, (int)((150 * 1024 - fixed) / (CBS * sizeof(double)))));
-        const size_t lds = fixed + (size_t)scap * CBS * sizeof(double);
-        hipLaunchKernelGGL(k_chol_prepare, dim3((n_sys + 255) / 256), dim3(256), 0, stream, Esys, n_sys, d_state.p, D2c.p, chol_sol.p);
-        hipLaunchKernelGGL(k_cholesky_stream, dim3(1), dim3(CHOLB_THREADS), lds, stream, Esys, n_sys, chol_work.p, chol_sol.p,
-                           chol_info.p, d_state.p, scap, chol_debug ? (chol_dbg.n ? chol_dbg.p : (chol_dbg.alloc(64), chol_dbg.p)) : nullptr);
-        if (chol_debug) {
-          std::vector<long long> st(8);
-          HIPCHK(hipMemcpyAsync(st.data(), chol_dbg.p, 8 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-          sync();
-          fprintf(stderr, "[chol_stream cycles] update %lld  factor %lld  solve %lld  write-back %lld  back-substitution %lld\n", st[0], st[1], st[2], st[3], st[4]);
-          chol_debug = false;
+        case CholRoute::STREAM: {
+          // 17 .. 46 cameras: one workgroup, left-looking, finished block columns streamed through L2
+          if (chol_sol.n < (size_t)n_sys) { chol_sol.alloc(n_sys); chol_info.alloc(1); }
+          if (chol_work.n < (size_t)nb * (nb + 1) / 2 * CB * CB) chol_work.alloc((size_t)nb * (nb + 1) / 2 * CB * CB);
+          // panel (nb blocks) + rhs + as much staging as the 150 KB budget leaves (fewer, larger streaming rounds)
+          const size_t fixed = ((size_t)nb * CBS + (size_t)nb * CB) * sizeof(double);
+          const int scap = std::min(64, std::max(nb, (int)((150 * 1024 - fixed) / (CBS * sizeof(double)))));
+          const size_t lds = fixed + (size_t)scap * CBS * sizeof(double);
+          if (chol_debug && chol_dbg.n == 0) chol_dbg.alloc(64);
+          hipLaunchKernelGGL(k_chol_prepare, dim3((n_sys + 255) / 256), dim3(256), 0, stream, Esys, n_sys, d_state.p, D2c.p, chol_sol.p);
+          hipLaunchKernelGGL(k_cholesky_stream, dim3(1), dim3(CHOLB_THREADS), lds, stream, Esys, n_sys, chol_work.p, chol_sol.p,
+                             chol_info.p, d_state.p, scap, chol_debug ? chol_dbg.p : nullptr);
+          if (chol_debug) {
+            const std::vector<long long> st = read_stamps(chol_dbg, 8);
+            fprintf(stderr, "[chol_stream cycles] update %lld  factor %lld  solve %lld  write-back %lld  back-substitution %lld\n", st[0], st[1], st[2], st[3], st[4]);
+            chol_debug = false;
+          }
+          hipLaunchKernelGGL(k_chol_epilogue<T>, dim3(1), dim3(1024), 0, stream, Esys, C, n_sys, d_state.p, D2c.p, ps_lm(), delta_c.p,
+                             chol_sol.p, chol_info.p, tie, first);
+          break;
         }
-        hipLaunchKernelGGL(k_chol_epilogue<T>, dim3(1), dim3(1024), 0, stream, Esys, C, n_sys, d_state.p, D2c.p, ps_lm(), delta_c.p,
-                           chol_sol.p, chol_info.p, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr);
-      } else {
-        hipLaunchKernelGGL((k_cholesky_solve<false, T>), dim3(1), dim3(CHOL_THREADS), 0, stream, Esys, C, d_state.p, D2c.p,
-                           ps_lm(), delta_c.p, n_sys, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr);
+        default:
+          // 24 .. 128 cameras: multi-workgroup factorisation (sba_chol_big.hpp)
+          launch_chol_big(Esys, n_sys, tied, route);
+          break;
       }
       prof_end(KP_CHOL);
     } else {
@@ -1676,23 +1670,15 @@ struct Engine : EngineBase {
     if (!lm_active) { err = "sba_lm_begin has not been called"; return SBA_ERR_STATE; }
     poll_clean = false;
     ++n_decides;
-    if (defer_decide && bf3_path()) {
+    if (!kn.decide_kernel && bf3_path()) {
       // the next k_schur_fused_bf3 takes the decision in its prologue; whatever else needs the decided record first
       // (lm_poll, another linearisation path) enqueues the kernel below through flush_decide()
       pending_decide = true; pend_scal = scal_all; pend_ranks = n_ranks;
-      pslot_advance();
       return SBA_OK;
     }
     launch_decide(scal_all, n_ranks);
-    pslot_advance();
     return SBA_OK;
   }
-  // several camera groups, fp32, indexed producers: the group pairs run on the bf16 pipe (k_schur_diag_bf3 / k_schur_offdiag_bf3)
-  bool diag_pairs_bf3() const { return sizeof(T) == 4 && ngroups > 1 && grp_indexed && !fused() && !no_bf3_pairs; }
-  bool offdiag_pairs_bf3() const { return diag_pairs_bf3() && !no_bf3_offdiag; }
-  // (the name is historical: every Schur kernel that takes the previous step's decision in its prologue -- k_schur_fused_bf3,
-  //  k_schur_fused_wide, k_schur_fused_f64)
-  bool bf3_path() const { return fused() && (sizeof(T) == 4 ? fused_bf3 : (fused_f64 || fused_wide)) && !sq_mode(); }
   const double* gmax_rd() const { return (bf3_path() && gmax_cur) ? gmax_cur : gmax_part.p; }
   void launch_decide(const double* scal_all, int n_ranks) {
     hipLaunchKernelGGL(k_decide<T>, dim3(1), dim3(DECIDE_THREADS), 0, stream, d_state.p, scal_all, n_ranks, trial_part.p,
@@ -1852,7 +1838,7 @@ struct Engine : EngineBase {
       // With a communicator the number of iterations (= collectives) enqueued per poll must not depend on anything rank-local
       // (bf3_path() follows the shard's own visibility density): a rank that enqueues one more all-reduce than its peers after
       // the device-side termination waits for it forever.
-      const int pbatch = multi() ? 2 : (bf3_path() && defer_decide ? 2 : 1);
+      const int pbatch = multi() ? 2 : (bf3_path() && !kn.decide_kernel ? 2 : 1);
       int batch = prof_on ? pbatch : BATCH;
       if (o->max_iter > 0) batch = std::min(std::max(1, o->max_iter - iters), prof_on ? pbatch : 64);
       for (int b = 0; b < batch; ++b) {
@@ -1915,7 +1901,6 @@ struct Engine : EngineBase {
   int solve(const sba_lm_opts* o, double* cams_out, double* pts_out, sba_lm_report* rep, sba_lm_iter_log* lg, int cap,
             int32_t* rows) override {
     const auto t0 = std::chrono::steady_clock::now();
-    static const bool solve_debug = getenv("SBA_SOLVE_DEBUG") != nullptr;      // host-side phase times of one solve on stderr
     auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e6; };
     int rc = lm_begin(o);
     if (rc) return rc;
@@ -1931,7 +1916,7 @@ struct Engine : EngineBase {
     HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
     rc = lm_finish(cams_out, pts_out, rep);
     if (rc) return rc;
-    if (solve_debug)
+    if (kn.solve_debug)
       fprintf(stderr, "[solve] lm_begin %.0f us | loop (enqueue + polls) %.0f us (device %.0f us) | lm_finish %.0f us | %d iterations\n",
               t_begin, t_loop - t_begin, ms * 1e3, since() - t_loop, (int)iters);
     if (rep) {

@@ -832,7 +832,7 @@ __device__ __forceinline__ bool chol3_inv_fast(const float v[6], float li[6]) {
 //   slab layout: [pair][ks][tile (121 slots)][lane 64][reg 4]   (acc type T; a lane's 4 registers are one 16-byte store)
 //   bpart layout: [ga][ks][176] doubles (only diagonal pairs contribute)
 // Flavours: k_schur (f32: 4 producer + 4 consumer waves), k_schur_sym (f64: all 8 waves produce, then all 8 consume),
-// k_schur_fused (f32, dense visibility, one group: the linearisation rides in the producers) -- see DESIGN.md 4.
+// k_schur_fused_bf3 (f32, dense visibility, one group: the linearisation rides in the producers) -- see DESIGN.md 4.
 constexpr int SCHUR_THREADS = 512;                           // 4 producer waves + 4 consumer waves
 template <typename T, bool DIAG> struct SchurCfg {
   using elem = T;
@@ -1292,7 +1292,7 @@ __global__ __launch_bounds__(SCHUR_THREADS) void k_schur_sym(
     }
   };
   // LIN (one camera group, no duplicate (point, camera) pairs): lane (q, c) = (point of the 32-point chunk, camera), as
-  // in k_schur_fused -- the point blocks V_p, g_p are DPP row sums, and scaling, damped factor and z follow in
+  // in k_schur_fused_bf3 -- the point blocks V_p, g_p are DPP row sums, and scaling, damped factor and z follow in
   // registers, so k_linearize_points and k_point_factor are not launched (f64 keeps k_linearize_cams: 77 f64
   // accumulators per lane do not fit beside the MFMA tiles).
   static_assert(!LIN || (DIAG && PTS == 32), "the fused point linearisation needs the one-group diagonal pair and 32-point chunks");
@@ -1516,253 +1516,9 @@ struct FusedDecide {
 //   * U_c = sum Jc^T Jc (66 upper-triangle entries) and g_c = sum Jc^T r (11) : per-lane register accumulators,
 //     folded over the 16 points-lanes of a camera through LDS at the end, one partial per workgroup
 //     (Upart2[wg][c][77]); k_build_exchange sums the partials in the same fixed-order loop as the slabs.
-// The two roles are split at the top level (same number of barriers on both sides), so the producers' 77 accumulators
-// and the consumers' 68 MFMA accumulator registers share the register file instead of adding up.
-template <typename T> struct SchurFusedCfg : SchurCfg<T, true> {
-  static constexpr size_t LDS_BYTES = SchurCfg<T, true>::LDS_BYTES + (size_t)SchurCfg<T, true>::NPROD * UPK * sizeof(T);
-};
-
-__global__ __launch_bounds__(SCHUR_THREADS) void k_schur_fused(
-    const ParamSets<float> ps, const LMState* __restrict__ st, int C,
-    const float2* __restrict__ uv /* observations of a point in camera order; dense rigs: (p, c) at p*C + c */,
-    const float* __restrict__ w, const int32_t* __restrict__ pt_start, const uint16_t* __restrict__ vis /* per point: bit c
-    = camera c sees it; NULL = every camera sees every point */,
-    int N, int ksplit, double* __restrict__ D2p, double* __restrict__ gp, float* __restrict__ pf, float* __restrict__ slabs,
-    double* __restrict__ bpart, double* __restrict__ gdpart /* [ksplit][2][176]: g_c and diag U_c partials */,
-    double* __restrict__ cost_part, double* __restrict__ gmax_part,
-    long long* __restrict__ dbg /* optional cycle stamps of workgroup 0: [it][producer done, consumer done] */) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  using T = float;
-  using Cfg = SchurCfg<T, true>;
-  constexpr int THREADS = Cfg::THREADS, NPROD = Cfg::NPROD, TPW = Cfg::TPW, PTS = Cfg::PTS, K = Cfg::K, BUF = Cfg::BUF;
-  static_assert(PTS == 16 && NPROD == 256, "lane = (point of the chunk, camera) needs 16 x 16 producer lanes");
-  if (st->status >= 0) return;
-  const bool stamp_wg = dbg && blockIdx.x == 0;
-  if (stamp_wg && threadIdx.x == 0) dbg[48] = clock64();         // kernel entry
-  const int cur_ = ps_cur(ps, st);
-  const T* __restrict__ campre = ps.campre[cur_];
-  const T* __restrict__ ptsT = ps.ptsT[cur_];
-  T* s_buf = reinterpret_cast<T*>(smem);                          // [2][BUF]: panel [K][176], z [K]
-  T* s_cam = s_buf + 2 * BUF;                                     // [32][CAMPRE] (first 16 used)
-  T* s_U = s_cam + 2 * GROUP_CAMS * CAMPRE;                       // [256][UPK] at the end
-  __shared__ double s_scr[2][NPROD / 64];
-  for (int i = threadIdx.x; i < 2 * BUF; i += THREADS) s_buf[i] = (T)0;
-  for (int i = threadIdx.x; i < C * CAMPRE; i += THREADS) s_cam[i] = campre[i];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const bool producer = threadIdx.x < NPROD;
-  int per = (N + ksplit - 1) / ksplit;
-  per = ((per + PTS - 1) / PTS) * PTS;
-  const int pbeg = min(N, (int)blockIdx.x * per), pend = min(N, pbeg + per);
-  const int nchunk = (pend - pbeg + PTS - 1) / PTS;
-  const T lam = (T)st->lam;
-  T* s_Ured = s_buf;                                              // [C][UPK] once the panels are done with
-  // fold the 16 point-lanes of every camera: U_c[k] = sum_q s_U[16 q + c][k]
-  auto fold_u = [&]() {
-    for (int o = threadIdx.x; o < C * UPK; o += THREADS) {
-      const int c = o / UPK, k = o - c * UPK;
-      T sum = 0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) sum += s_U[(q * 16 + c) * UPK + k];
-      s_Ured[o] = sum;
-    }
-  };
-  __syncthreads();
-
-  if (producer) {
-    const int q = threadIdx.x >> 4, c = threadIdx.x & 15;
-    const bool cam_ok = c < C;
-    const T* cp_safe = s_cam + (cam_ok ? c : 0) * CAMPRE;          // lanes beyond the last camera read camera 0's row (weight 0)
-    T Uacc[UPK];
-    static_for<0, UPK>([&](auto kc) { Uacc[decltype(kc)::value] = (T)0; });
-    T sq = 0, gmx = 0;
-    // operands of the next chunk, requested one chunk ahead; with sparse visibility the observation index of lane
-    // (q, c) is pt_start[p] + popcount(vis[p] below bit c), so the point's mask and offset travel two chunks ahead
-    float2 n_uv = make_float2(0.f, 0.f);
-    T n_w = 1, n_X[3] = {0, 0, 0};
-    double n_D[3] = {0, 0, 0};
-    bool n_valid = false, n_pt = false;
-    unsigned i_mask = 0; int i_start = 0; bool i_pt = false;      // index stage (chunk + 2)
-    auto request_index = [&](int chunk) {
-      const int p = pbeg + chunk * PTS + q;
-      i_pt = chunk < nchunk && p < pend;
-      i_mask = 0xffffu; i_start = 0;
-      if (i_pt && vis) { i_mask = vis[p]; i_start = pt_start[p]; }
-    };
-    auto request = [&](int chunk) {              // consumes the index stage of `chunk`, then refills it for chunk + 1
-      const int p = pbeg + chunk * PTS + q;
-      n_pt = i_pt;
-      n_valid = i_pt && cam_ok && ((i_mask >> c) & 1u);
-      if (n_pt) {                                // every lane of the row needs the point (row sums are taken by all 16)
-        n_X[0] = ptsT[3 * (size_t)p]; n_X[1] = ptsT[3 * (size_t)p + 1]; n_X[2] = ptsT[3 * (size_t)p + 2];
-        n_D[0] = D2p[3 * (size_t)p]; n_D[1] = D2p[3 * (size_t)p + 1]; n_D[2] = D2p[3 * (size_t)p + 2];
-      }
-      if (n_valid) {
-        const size_t o = vis ? (size_t)i_start + __builtin_popcount(i_mask & ((1u << c) - 1u)) : (size_t)p * C + c;
-        n_uv = uv[o];
-        n_w = w ? w[o] : (T)1;
-      }
-      request_index(chunk + 1);
-    };
-    request_index(0);
-    request(0);
-    if (stamp_wg && threadIdx.x == 0) dbg[49] = clock64();       // prologue done
-    for (int it = 0; it <= nchunk; ++it) {
-      if (it < nchunk) {
-        T* panel = s_buf + (it & 1) * BUF;
-        T* s_z = panel + K * GROUP_ROWS;
-        const bool valid = n_valid, have_pt = n_pt;
-        const float2 m = n_uv;
-        const T ww = n_w, X0 = n_X[0], X1 = n_X[1], X2 = n_X[2];
-        const double D0 = n_D[0], D1 = n_D[1], D2 = n_D[2];
-        const int p = pbeg + it * PTS + q;
-        request(it + 1);
-        // a lane without an observation runs the same code with weight 0 (every output carries the weight as a factor) and a
-        // harmless depth: no branch, no zero-initialised outputs
-        T r[2], Jc[2][NCP], Jp[2][3];
-        obs_resjac<T>(cp_safe, X0, X1, X2, m.x, m.y, valid ? ww : (T)0, r, Jc, Jp, valid);
-        sq += robust_apply<T>(ps.loss(), r, Jc, Jp);
-        // per-point blocks: V (6) and g_p (3), summed over the 16 cameras of the DPP row
-        T v6[6], g3[3];
-        v6[0] = row16_sum(Jp[0][0] * Jp[0][0] + Jp[1][0] * Jp[1][0]);
-        v6[1] = row16_sum(Jp[0][0] * Jp[0][1] + Jp[1][0] * Jp[1][1]);
-        v6[2] = row16_sum(Jp[0][0] * Jp[0][2] + Jp[1][0] * Jp[1][2]);
-        v6[3] = row16_sum(Jp[0][1] * Jp[0][1] + Jp[1][1] * Jp[1][1]);
-        v6[4] = row16_sum(Jp[0][1] * Jp[0][2] + Jp[1][1] * Jp[1][2]);
-        v6[5] = row16_sum(Jp[0][2] * Jp[0][2] + Jp[1][2] * Jp[1][2]);
-        g3[0] = row16_sum(Jp[0][0] * r[0] + Jp[1][0] * r[1]);
-        g3[1] = row16_sum(Jp[0][1] * r[0] + Jp[1][1] * r[1]);
-        g3[2] = row16_sum(Jp[0][2] * r[0] + Jp[1][2] * r[1]);
-        const bool fixedp = have_pt && pt_fixed(ps, (size_t)p);
-        if (!fixedp) gmx = fmaxf(gmx, fmaxf(fabsf(g3[0]), fmaxf(fabsf(g3[1]), fabsf(g3[2]))));
-        // point scaling: monotone max of the squared column norms (x_scale='jac', scipy trf.py:424,545)
-        const double E0 = fmax(D0, (double)v6[0]), E1 = fmax(D1, (double)v6[3]), E2 = fmax(D2, (double)v6[5]);
-        T f[PF];
-        T li[6];
-        T vd[6] = {v6[0] + lam * (T)fmax_pos(E0), v6[1], v6[2], v6[3] + lam * (T)fmax_pos(E1), v6[4], v6[5] + lam * (T)fmax_pos(E2)};
-        const bool okp = have_pt && !fixedp && chol3_inv_fast(vd, li);
-#pragma unroll
-        for (int k = 0; k < PF; ++k) f[k] = (T)0;
-        if (okp) {
-#pragma unroll
-          for (int k = 0; k < 6; ++k) f[k] = li[k];
-          f[6] = li[0] * g3[0];
-          f[7] = li[1] * g3[0] + li[2] * g3[1];
-          f[8] = li[3] * g3[0] + li[4] * g3[1] + li[5] * g3[2];
-          f[9] = (T)1;
-        }
-        if (have_pt && c == 0) {
-          D2p[3 * (size_t)p] = E0; D2p[3 * (size_t)p + 1] = E1; D2p[3 * (size_t)p + 2] = E2;
-          gp[3 * (size_t)p] = (double)g3[0]; gp[3 * (size_t)p + 1] = (double)g3[1]; gp[3 * (size_t)p + 2] = (double)g3[2];
-          float4* o4 = reinterpret_cast<float4*>(pf + (size_t)p * PF);
-          o4[0] = make_float4(f[0], f[1], f[2], f[3]);
-          o4[1] = make_float4(f[4], f[5], f[6], f[7]);
-          o4[2] = make_float4(f[8], f[9], f[10], f[11]);
-        }
-        if (cam_ok) {
-          schur_emit_block<T>(panel, q, c * NCP, 1, Jc, Jp, f);
-          if (c == 0) { s_z[3 * q + 0] = f[6]; s_z[3 * q + 1] = f[7]; s_z[3 * q + 2] = f[8]; }
-        }
-        // camera blocks: U_c upper triangle + g_c in registers (this lane always serves camera c)
-        static_for<0, NCP>([&](auto ac) {
-          constexpr int a = decltype(ac)::value;
-          static_for<a, NCP>([&](auto bc) {
-            constexpr int b = decltype(bc)::value;
-            constexpr int k = a * NCP - (a * (a - 1)) / 2 + (b - a);
-            Uacc[k] = __builtin_fmaf(Jc[1][a], Jc[1][b], __builtin_fmaf(Jc[0][a], Jc[0][b], Uacc[k]));   // two FMAs, no add
-          });
-          Uacc[NCP * (NCP + 1) / 2 + a] = __builtin_fmaf(Jc[1][a], r[1], __builtin_fmaf(Jc[0][a], r[0], Uacc[NCP * (NCP + 1) / 2 + a]));
-        });
-      }
-      if (dbg && blockIdx.x == 0 && threadIdx.x == 0 && it < 20) dbg[2 * it] = clock64();
-      __syncthreads();
-    }
-    if (stamp_wg && threadIdx.x == 0) dbg[50] = clock64();       // main loop done (producer side)
-    // hand the accumulators over
-    static_for<0, UPK>([&](auto kc) { constexpr int k = decltype(kc)::value; s_U[threadIdx.x * UPK + k] = Uacc[k]; });
-    const double cs = wave_sum((double)sq), gm = wave_max((double)gmx);
-    if (lane == 0) { s_scr[0][wid] = cs; s_scr[1][wid] = gm; }
-    __syncthreads();
-    fold_u();
-    __syncthreads();
-  } else {
-    const int cw = wid - NPROD / 64;
-    typename Mfma<T>::acc_t acc[TPW];
-#pragma unroll
-    for (int s = 0; s < TPW; ++s) acc[s] = typename Mfma<T>::acc_t{0, 0, 0, 0};
-    const int ct = threadIdx.x - NPROD;
-    const int lane_off = (lane >> 4) * GROUP_ROWS + (lane & 15);
-    double bacc = 0;
-    __builtin_amdgcn_s_setprio(2);
-    for (int it = 0; it <= nchunk; ++it) {
-      if (it >= 1) {
-        const T* panel = s_buf + ((it - 1) & 1) * BUF;
-        const T* s_z = panel + K * GROUP_ROWS;
-        if (ct < GROUP_ROWS) {
-          T s0 = 0, s1 = 0;
-#pragma unroll 8
-          for (int k = 0; k < K; k += 2) { s0 += panel[k * GROUP_ROWS + ct] * s_z[k]; s1 += panel[(k + 1) * GROUP_ROWS + ct] * s_z[k + 1]; }
-          bacc += (double)(s0 + s1);
-        }
-        schur_consume_v<Cfg, K>(cw, panel + lane_off, panel + lane_off, acc);
-      }
-      if (dbg && blockIdx.x == 0 && threadIdx.x == NPROD && it < 20) dbg[2 * it + 1] = clock64();
-      __syncthreads();
-    }
-    __syncthreads();
-    // wait for the camera blocks U_c of this workgroup (folded below by everybody), then take them out of the tiles:
-    // the slab then holds this workgroup's share of  sum Ytilde Ytilde^T - U,  and k_build_exchange's plain sum of the
-    // slabs is -S.  Only tiles on and next to the diagonal contain entries of an 11x11 camera block.
-    fold_u();
-    __syncthreads();
-    constexpr int LO = 0;
-    static_for<0, Cfg::NV>([&](auto vc) {
-      constexpr int V = decltype(vc)::value;
-      if (cw == V) {
-        constexpr int T0 = schur_lo(Cfg::NTILE, Cfg::NV, V), T1 = schur_lo(Cfg::NTILE, Cfg::NV, V + 1);
-        static_for<T0, T1>([&](auto tc) {
-          constexpr int t = decltype(tc)::value;
-          constexpr int R = schur_tile_R(true, t), Tc = schur_tile_T(true, t);
-          if constexpr (Tc - R <= 1) {
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-              const int i = 16 * R + Mfma<T>::row_of(lane, rg), j = 16 * Tc + (lane & 15);
-              const int ci_ = i / NCP, cj_ = j / NCP;
-              if (ci_ == cj_ && ci_ < C) {
-                const int a = min(i - ci_ * NCP, j - cj_ * NCP), b = max(i - ci_ * NCP, j - cj_ * NCP);
-                acc[t - T0][rg] -= s_Ured[ci_ * UPK + (a * NCP - (a * (a - 1)) / 2 + (b - a))];
-              }
-            }
-          }
-        });
-      }
-    });
-    (void)LO;
-    if (stamp_wg && threadIdx.x == NPROD) dbg[51] = clock64();   // U folded and taken out of the tiles
-    T* slab = slabs + (size_t)blockIdx.x * (size_t)(GROUP_TILES * GROUP_TILES) * 256;
-    schur_store_v<Cfg>(cw, slab, lane, acc);
-    if (stamp_wg && threadIdx.x == NPROD) dbg[52] = clock64();   // slab stores issued
-    if (ct < GROUP_ROWS) {
-      const int c = ct / NCP, e = ct - c * NCP;
-      const double gpart = (c < C) ? (double)s_Ured[c * UPK + NCP * (NCP + 1) / 2 + e] : 0.0;
-      const double dpart = (c < C) ? (double)s_Ured[c * UPK + (e * NCP - (e * (e - 1)) / 2)] : 0.0;
-      bpart[(size_t)blockIdx.x * GROUP_ROWS + ct] = bacc - gpart;           // rhs = sum (b - g_c) over the workgroups
-      gdpart[((size_t)blockIdx.x * 2 + 0) * GROUP_ROWS + ct] = gpart;
-      gdpart[((size_t)blockIdx.x * 2 + 1) * GROUP_ROWS + ct] = dpart;
-    }
-  }
-  if (threadIdx.x == 0) {
-    double cs = 0, gm = 0;
-    for (int wv = 0; wv < NPROD / 64; ++wv) { cs += s_scr[0][wv]; gm = fmax(gm, s_scr[1][wv]); }
-    cost_part[blockIdx.x] = 0.5 * cs;
-    gmax_part[blockIdx.x] = gm;
-    if (stamp_wg) dbg[53] = clock64();                           // kernel exit (thread 0)
-  }
-}
-
-
-// ------------------------------------------------------------------ K3+K4 fused, Schur products on the bf16 matrix pipe
-// Same kernel structure and the same producer mathematics as k_schur_fused; what changes is how panel^T panel is formed.
-// On gfx950 the f32-input MFMA runs on the SIMD's f32 FMA lanes (tools/micro/mix_waves.hip: a VALU-only wave beside a
+// The two roles are split at the top level (same number of barriers on both sides), so the producers' accumulators and
+// the consumers' MFMA accumulator registers share the register file instead of adding up.
+// The Schur products go to the bf16 matrix pipe.  On gfx950 the f32-input MFMA runs on the SIMD's f32 FMA lanes (tools/micro/mix_waves.hip: a VALU-only wave beside a
 // saturating f32-MFMA wave makes no progress at all), so the 6.3k MFMA cycles of a 16-point chunk and the ~5k cycles of
 // producer arithmetic simply add up.  The bf16 MFMA is a separate pipe.  Each f32 panel value y is therefore split EXACTLY
 // into three bf16 pieces, y = h + m + l exactly (8 + 8 + 8 mantissa bits; h = bf16(y), m = bf16(y - h), l = (y - h) - m,
@@ -1811,18 +1567,10 @@ __global__ __launch_bounds__(SCHUR_THREADS) void k_schur_fused_bf3(
     const float2* __restrict__ uv, const float* __restrict__ w, const int32_t* __restrict__ pt_start,
     const uint16_t* __restrict__ vis, int N, int ksplit, double* __restrict__ D2p, double* __restrict__ gp,
     float* __restrict__ pf, float* __restrict__ slabs, double* __restrict__ bpart, double* __restrict__ gdpart,
-    double* __restrict__ cost_part, double* __restrict__ gmax_part, long long* __restrict__ dbg,
-    int exp_arg /* timing experiments, only in a build with -DSBA_SCHUR_EXP_BUILD (make EXTRA=-DSBA_SCHUR_EXP_BUILD; SBA_SCHUR_EXP=1: no m / l planes,
-                   2: no U_c / g_c accumulation; results are WRONG when set -- docs/EXPERIMENTS.md, profiles/r4_fused_bf3_sensitivity.txt) */) {
+    double* __restrict__ cost_part, double* __restrict__ gmax_part, long long* __restrict__ dbg) {
   extern __shared__ __align__(16) unsigned char smem[];
   using T = float;
   using Cfg = SchurBf3Cfg;
-#ifdef SBA_SCHUR_EXP_BUILD
-  const int exp_flags = exp_arg;
-#else
-  constexpr int exp_flags = 0;          // the production kernel carries none of the experiment's branches
-  (void)exp_arg;
-#endif
   constexpr int THREADS = Cfg::THREADS, NPROD = Cfg::NPROD, TPW = Cfg::TPW, PTS = Cfg::PTS, UPKB = Cfg::UPKB, UPKS = Cfg::UPKS;
   const bool stamp_wg = dbg && blockIdx.x == 0;
   if (stamp_wg && threadIdx.x == 0) dbg[48] = clock64();
@@ -2019,17 +1767,14 @@ __global__ __launch_bounds__(SCHUR_THREADS) void k_schur_fused_bf3(
             const unsigned h01 = pk(y[0], y[1]), h2 = pk1(y[2]);
             unsigned char* dst = pbuf + lane_slot + e * (2 * Cfg::HALF_BYTES);
             *reinterpret_cast<uint2*>(dst) = make_uint2(h01, h2);
-            if (!(exp_flags & 1)) {
-              const float r0 = y[0] - lo_f(h01), r1 = y[1] - hi_f(h01), r2 = y[2] - lo_f(h2);
-              const unsigned m01 = pk(r0, r1), m2 = pk1(r2);
-              const float s0 = r0 - lo_f(m01), s1 = r1 - hi_f(m01), s2 = r2 - lo_f(m2);
-              const unsigned l01 = pk(s0, s1), l2 = pk1(s2);
-              *reinterpret_cast<uint2*>(dst + Cfg::PLANE * 2) = make_uint2(m01, m2);
-              *reinterpret_cast<uint2*>(dst + 2 * Cfg::PLANE * 2) = make_uint2(l01, l2);
-            }
+            const float r0 = y[0] - lo_f(h01), r1 = y[1] - hi_f(h01), r2 = y[2] - lo_f(h2);
+            const unsigned m01 = pk(r0, r1), m2 = pk1(r2);
+            const float s0 = r0 - lo_f(m01), s1 = r1 - hi_f(m01), s2 = r2 - lo_f(m2);
+            const unsigned l01 = pk(s0, s1), l2 = pk1(s2);
+            *reinterpret_cast<uint2*>(dst + Cfg::PLANE * 2) = make_uint2(m01, m2);
+            *reinterpret_cast<uint2*>(dst + 2 * Cfg::PLANE * 2) = make_uint2(l01, l2);
           });
         }
-        if (!(exp_flags & 2))
         static_for<0, NCP>([&](auto ac) {
           constexpr int a = decltype(ac)::value;
           static_for<a, NCP>([&](auto bc) {
@@ -2193,7 +1938,7 @@ struct SchurPairCfg {
 // (they involve every camera that sees the point, not just this group), U and g_c from k_linearize_cams, the decision from
 // k_decide.  Lane (q, c) = (point of the 16-point chunk, camera of the group) finds its observation through the k_group_index
 // tables; a lane without one runs the same code with weight 0 and writes zeros.  Same LDS planes, same six bf16 MFMAs per
-// tile and k-step, same parameter-major tile order (k_build_exchange: emajor = 2 undoes it for the diagonal pairs).
+// tile and k-step, same parameter-major tile order (k_build_exchange: emajor_mode 1 undoes it).
 // grid = (ksplit, ngroups).  Replaces k_schur<float, true> there: 4 x fewer matrix cycles, and they overlap with the producers.
 __global__ __launch_bounds__(SCHUR_THREADS) void k_schur_diag_bf3(
     const ParamSets<float> ps, const LMState* __restrict__ st, int C,

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(1024) void k_build_exchange(
     double* __restrict__ Pk = nullptr /* multi-rank: the same system once more, upper triangle packed row by row
                                          [S n(n+1)/2 | rhs | diagU | gc | cost] -- what travels through the all-reduce */,
     int emajor_mode = 0 /* parameter-major tiles (tile (R, Tc) holds parameters (R, Tc) of the camera pairs, row 16 e + c):
-                           1 = every pair (k_schur_fused_bf3), 2 = the diagonal pairs (k_schur_diag_bf3),
+                           1 = every pair (k_schur_fused_bf3, or k_schur_diag_bf3 + k_schur_offdiag_bf3),
                            3 = k_schur_fused_wide: one slab per workgroup, compact rows e*C + c in ceil(11 C / 16) tiles, row partials
                                (bpart / gdpart) in the exchange buffer's own order with a stride of WIDE_ROWS */,
     int nt_launch = GROUP_TILES * GROUP_TILES /* tile slots per pair the grid covers: 121 with several pairs (an off-diagonal pair has
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(1024) void k_build_exchange(
     else schur_tile_rc(diag, t, R, Tc);
     const int e = part * EPB + l16;                   // entry of the tile's register dump: lane = e>>2, reg = e&3
     const int rg = e & 3, lane = e >> 2;            // slab layout [tile][lane][reg]
-    const bool emajor = wide || emajor_mode == 1 || (emajor_mode == 2 && diag);
+    const bool emajor = wide || emajor_mode == 1;
     int i, j;
     if (wide) {                                       // compact rows: row = e C + c  ->  exchange index c * NCP + e
       const int rho = 16 * R + M_::row_of(lane, rg), kap = 16 * Tc + (lane & 15);
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(1024) void k_build_exchange(
       for (int q = 0; q < RG; ++q) { bs += s_r[0][q][lr]; gs += s_r[1][q][lr]; dsv += s_r[2][q][lr]; }
       double v_r, v_d, v_g;
       if (gdpart) {
-        v_r = bs;                      // k_schur_fused stored b - g_c
+        v_r = bs;                      // k_schur_fused_bf3 stored b - g_c
         v_d = dsv;
         v_g = gs;
       } else {
@@ -230,126 +230,6 @@ __global__ void k_tie_system(const double* __restrict__ E, int n, int n_s, const
     rhs_s[(size_t)threadIdx.x * n_s + a] = s;
   }
   if (a == 0 && threadIdx.x == 0) Es[(size_t)n_s * n_s + 3 * n_s] = E[(size_t)n * n + 3 * n];
-}
-
-// ------------------------------------------------------------------ dense Cholesky + solve of the reduced camera system
-// Single workgroup.  A = S + lam*diag(D2c) ; A = L L^T ; delta_c = A^-1 rhs.  LDSMODE keeps the packed
-// lower triangle in LDS (n <= 176); otherwise factors in place in the caller's S copy in global memory.
-struct TriLds {
-  double* a;
-  __device__ inline double& at(int i, int j) const { return a[(size_t)i * (i + 1) / 2 + j]; }   // i >= j
-};
-struct TriGlobal {
-  double* a; int n;
-  __device__ inline double& at(int i, int j) const { return a[(size_t)i * n + j]; }
-};
-
-template <bool LDSMODE, typename T>
-__global__ __launch_bounds__(CHOL_THREADS) void k_cholesky_solve(
-    double* __restrict__ E /* summed exchange buffer; S is destroyed in global mode */, int C,
-    LMState* __restrict__ st, double* __restrict__ D2c, const ParamSets<T> ps,
-    double* __restrict__ delta_c, int n_sys, const int32_t* __restrict__ tie, const int32_t* __restrict__ first) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  if (st->status >= 0) return;
-  const int cur_ = ps_cur(ps, st);
-  const double* __restrict__ cams = ps.cams[cur_];
-  double* __restrict__ cams_new = ps.cams[cur_ ^ 1];
-  T* __restrict__ campre_new = ps.campre[cur_ ^ 1];
-  __shared__ double s_y[GROUP_ROWS * 8 > 1408 ? GROUP_ROWS * 8 : 1408];   // rhs / solution, n <= 1408
-  __shared__ double s_piv;
-  __shared__ int s_fail;
-  __shared__ double s_scr[CHOL_THREADS / 64];
-  const int ncam = C * NCP;
-  const int n = n_sys;
-  const int tid = threadIdx.x;
-  double* S = E;
-  const double* rhs = E + (size_t)n * n;
-  const double* dU = rhs + n;
-  const double* gct = dU + n;
-  const double lam = st->lam;
-  // camera scaling: monotone max of the column norms (x_scale='jac', scipy trf.py:424,545)
-  const bool fresh = st->fresh != 0;
-  for (int i = tid; i < n; i += CHOL_THREADS) {
-    double d = D2c[i];
-    if (fresh) { d = fmax(d, dU[i]); D2c[i] = d; }
-    s_y[i] = rhs[i];
-  }
-  if (tid == 0) { s_fail = 0; if (tid == 0 && E) st->cost = E[(size_t)n * n + 3 * n]; }
-  __syncthreads();
-  TriLds Ll{reinterpret_cast<double*>(smem)};
-  TriGlobal Lg{S, n};
-  auto AT = [&](int i, int j) -> double& { if constexpr (LDSMODE) return Ll.at(i, j); else return Lg.at(i, j); };
-  // load (+ damping)
-  for (int idx = tid; idx < n * n; idx += CHOL_THREADS) {
-    const int i = idx / n, j = idx - i * n;
-    if (j > i) continue;
-    double v = S[idx];
-    if (i == j) v += lam * fmax_pos(D2c[i]);
-    AT(i, j) = v;
-  }
-  __syncthreads();
-  const int tx = tid & 31, ty = tid >> 5;
-  for (int k = 0; k < n; ++k) {
-    if (tid == 0) {
-      const double d = AT(k, k);
-      if (!(d > 0.0) || !isfinite(d)) { s_fail = 1; s_piv = 1.0; }
-      else s_piv = 1.0 / sqrt(d);
-    }
-    __syncthreads();
-    if (s_fail) break;
-    const double ip = s_piv;
-    for (int i = k + tid; i < n; i += CHOL_THREADS) AT(i, k) *= ip;    // includes the diagonal: L_kk = sqrt(d)
-    __syncthreads();
-    for (int i = k + 1 + ty; i < n; i += 32) {
-      const double lik = AT(i, k);
-      for (int j = k + 1 + tx; j <= i; j += 32) AT(i, j) -= lik * AT(j, k);
-    }
-    __syncthreads();
-  }
-  const bool fail = s_fail != 0;
-  // triangular solves inside wave 0 (no workgroup barriers): L y = rhs ; L^T x = y
-  if (!fail && tid < 64) {
-    for (int k = 0; k < n; ++k) {
-      const double yk = s_y[k] / AT(k, k);
-      __builtin_amdgcn_wave_barrier();
-      if (tid == 0) s_y[k] = yk;
-      for (int i = k + 1 + tid; i < n; i += 64) s_y[i] -= AT(i, k) * yk;
-      __builtin_amdgcn_wave_barrier();
-    }
-    for (int k = n - 1; k >= 0; --k) {
-      const double xk = s_y[k] / AT(k, k);
-      __builtin_amdgcn_wave_barrier();
-      if (tid == 0) s_y[k] = xk;
-      for (int i = tid; i < k; i += 64) s_y[i] -= AT(k, i) * xk;
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-  __syncthreads();
-  double pred = 0, dx2 = 0, x2 = 0, gm = 0;
-  for (int i = tid; i < ncam; i += CHOL_THREADS) {
-    const double d = fail ? 0.0 : s_y[tie ? tie[i] : i];
-    delta_c[i] = d;
-    cams_new[i] = cams[i] + d;
-  }
-  for (int i = tid; i < n; i += CHOL_THREADS) {
-    const double d = fail ? 0.0 : s_y[i];
-    const double x = cams[first ? first[i] : i];
-    pred += 0.5 * d * (lam * fmax_pos(D2c[i]) * d - gct[i]);
-    dx2 += d * d;
-    x2 += x * x;
-    gm = fmax(gm, fabs(gct[i]));
-  }
-  pred = block_sum(pred, s_scr);
-  dx2 = block_sum(dx2, s_scr);
-  x2 = block_sum(x2, s_scr);
-  gm = block_max(gm, s_scr);
-  if (tid == 0) {
-    st->pred_c = pred; st->dx2_c = dx2; st->x2_c = x2; st->gmax_c = gm;
-    st->chol_fail = fail ? 1 : 0;
-    st->fresh = 0;
-  }
-  __syncthreads();
-  if (tid < C) campre_build<T>(cams_new + (size_t)tid * NCP, campre_new + (size_t)tid * CAMPRE);
 }
 
 // points-only mode: no camera system.  Zero step for the cameras, cost from the partials.
@@ -575,7 +455,7 @@ __global__ __launch_bounds__(DECIDE_THREADS) void k_trial_scalars(const double* 
 }
 
 // ------------------------------------------------------------------ K6 for dense visibility, one camera group
-// Same arithmetic as k_backsub_trial, laid out like k_schur_fused: lane (q, c) = (point of a 16-point chunk, camera),
+// Same arithmetic as k_backsub_trial, laid out like k_schur_fused_bf3: lane (q, c) = (point of a 16-point chunk, camera),
 // so W_p^T delta_c is a DPP row sum instead of an LDS staging pass with two barriers, the workgroup is persistent
 // (camera tables staged once, chunks strided over the grid) and each partial row holds a whole workgroup's share.
 // LW = lanes per point: 16 (one DPP row: up to 16 cameras), 64 (a whole wave, two cameras per lane: 33 .. 128 cameras, round 4) or 32 (a wave half: 17 .. 32 cameras, the rigs of k_schur_fused_wide and, since round 4, 24 .. 32 --

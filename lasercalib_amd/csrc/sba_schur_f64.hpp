@@ -5,7 +5,7 @@
 // What k_schur_fused_f64 replaces (round 3): the fp64 default path ran k_linearize_cams<double> (Jacobians + U_c on the f64 MFMA,
 // 35 us at 16 x 50k), k_reduce_cams (5 us), k_schur_sym<double, LIN> (141 us: all eight waves build a 32-point panel, then all eight
 // consume it -- profiles/r3_sq_counters_16x50k_f64.json: matrix pipe 42-48 % busy, VALU and MFMA phases alternate in lockstep) and
-// k_decide (5 us).  Here the fp32 kernels' structure is used instead (k_schur_fused, sba_kernels.hpp): the previous step's LM
+// k_decide (5 us).  Here the fp32 kernels' structure is used instead (k_schur_fused_bf3, sba_kernels.hpp): the previous step's LM
 // decision in the prologue; four producer waves evaluate every observation's Jacobian ONCE per iteration (lane = (point of a
 // 16-point chunk, camera)), accumulate U_c / g_c, reduce V_p / g_p over the DPP row, factor the damped 3x3 block and write the
 // 48 x 176 panel Ytilde of the chunk into one of two LDS buffers; four consumer waves (one per SIMD, 17/17/16/16 of the 66
@@ -17,7 +17,7 @@
 // without scratch (see SchurF64Cfg::KREG).
 //   LDS: 2 x (48 x 176 + 48) doubles of panel + z (135,936 B), camera table 16 x 25 doubles, folded U_c 16 x 77 doubles, the
 //   accumulator sets 4 x 16 x 25 doubles: 161,792 B.  The register accumulators are handed over through the panel buffers.
-//   Outputs are those of k_schur_fused in T = double: slab [121 tile slots][64 lanes][4] per workgroup, bpart, gdpart, pf, gp, D2p.
+//   Outputs are those of k_schur_fused_bf3 in T = double: slab [121 tile slots][64 lanes][4] per workgroup, bpart, gdpart, pf, gp, D2p.
 #pragma once
 #include "sba_kernels.hpp"
 #include "sba_schur_wide.hpp"

@@ -56,3 +56,23 @@ def test_no_gpu_means_loud_failure(lib):
         sba.project(rig["pts0"][rig["point_ind"]], rig["cams0"][rig["camera_ind"]])
     with pytest.raises(_native.SbaError):
         sba.bundleAdjust_nocam()
+
+
+def test_environment_switches_are_read_in_one_place_and_documented():
+    """The engine reads the environment in read_knobs (csrc/sba_engine.hpp) and nowhere else, and the SBA_* names it knows
+    are exactly the ones INTEGRATION.md's table of environment switches lists."""
+    csrc = os.path.join(ROOT, "lasercalib_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip", ".h"))}
+    engine = sources["sba_engine.hpp"]
+    parser = re.search(r"\ninline Knobs read_knobs\(\) \{\n.*?\n\}\n", engine, flags=re.S)
+    assert parser, "read_knobs not found in sba_engine.hpp"
+    total = sum(text.count("getenv(") for text in sources.values())
+    assert total > 0 and parser.group(0).count("getenv(") == total, "getenv( outside read_knobs"
+    literals = set()
+    for text in sources.values():
+        literals |= set(re.findall(r'"(SBA_[A-Z0-9_]+)"', text))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = doc[doc.index("### Environment switches"):]
+    table = table[:table.index("\n## ")]
+    documented = set(re.findall(r"^\| `(SBA_[A-Z0-9_]+)` \|", table, flags=re.M))
+    assert literals == documented
