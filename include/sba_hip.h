@@ -143,6 +143,57 @@ int sba_create(const sba_problem_desc* desc, sba_handle** out);
 int sba_upload(sba_handle* h, const double* cams /*C*11*/, const double* points /*N*3*/,
                const double* uv /*M*2*/, const int64_t* cam_idx /*M*/, const int64_t* pt_idx /*M*/,
                const double* weights /*M or NULL*/);
+/* sba_upload_ex: sba_upload with options (sba_upload = sba_upload_ex with {0, SBA_LAYOUT_AUTO}).  The engine's layout -- point-major
+ * order, the camera order inside a point, visibility masks, the camera-major copy -- is built by one of three routes: the dense
+ * device kernel (M = N*C, already canonical), the general device pass (lasercalib_amd/csrc/sba_layout.hpp: sparse, shuffled or
+ * camera-descending lists) or the host pass.  All three produce the same layout bit for bit.  The device pass declines -- and
+ * the call continues on the host pass, which owns every error text -- when it meets an index out of range, a duplicate
+ * (point, camera) pair on a rig of up to 16 cameras, or a point with more than 256 observations. */
+typedef enum { SBA_LAYOUT_AUTO = 0, SBA_LAYOUT_HOST = 1, SBA_LAYOUT_DEVICE = 2 } sba_layout_route;
+typedef struct {
+  int32_t obs_on_device;   /* 1: uv, cam_idx, pt_idx, weights are DEVICE pointers on the handle's device (contiguous
+                              float64 / int64, complete before the call); cams and points stay host pointers.  When the host
+                              pass runs (SBA_LAYOUT_HOST, or the device pass declined) the library copies them to the host itself */
+  int32_t layout;          /* sba_layout_route; AUTO picks by size (dense lists: the dense kernel), DEVICE tries the device pass at any
+                              size (and still falls back to the host when it declines), HOST never launches a layout kernel */
+  int32_t reserved[6];
+} sba_upload_opts;
+typedef enum { SBA_ROUTE_HOST = 0, SBA_ROUTE_DEVICE_DENSE = 1, SBA_ROUTE_DEVICE_GENERAL = 2 } sba_upload_route;
+typedef enum {
+  SBA_DECLINE_NONE = 0,
+  SBA_DECLINE_INDEX_RANGE = 1,   /* a camera / point index out of range                       */
+  SBA_DECLINE_DUPLICATE = 2,     /* a duplicate (point, camera) pair with at most 16 cameras  */
+  SBA_DECLINE_DEGREE = 3         /* a point with more than 256 observations                   */
+} sba_layout_decline;
+typedef struct {
+  int32_t route;           /* sba_upload_route: who built the layout                                              */
+  int32_t decline_reason;  /* sba_layout_decline: why the general device pass handed over to the host, else 0    */
+  int32_t dense;           /* every camera sees every point exactly once                                          */
+  int32_t masked;          /* at most 16 cameras, no duplicate pair, not dense: per-point visibility masks        */
+  int32_t group_indexed;   /* more than 16 cameras: the per-group tables of k_group_index are in use              */
+  int32_t identity_perm;   /* the point-major order is the caller's order                                         */
+  int32_t n_blocks;        /* point-aligned blocks of at most 256 observations                                    */
+  int32_t n_chunks;        /* camera-major chunks of at most 1024 observations                                    */
+  int32_t max_degree;      /* largest number of observations of one point                                         */
+  int32_t stream_syncs;    /* stream synchronisations of the call (the parameter upload's included)               */
+  int32_t reserved[2];
+  double  seconds_total;          /* wall time of the call; the phases below are host-clock laps that add up to it  */
+  double  seconds_h2d;            /* raw arrays to the device (device routes), or device arrays to the host         */
+  double  seconds_device_layout;  /* layout kernels, their read-back and the wait for it                            */
+  double  seconds_host_layout;    /* the host pass: validation, sort, canonical order, permuted and camera-major copies */
+  double  seconds_tables;         /* block / chunk / pair tables, allocations, uploads, route plan, parameters      */
+} sba_upload_report;
+int sba_upload_ex(sba_handle* h, const double* cams /*C*11*/, const double* points /*N*3*/,
+                  const double* uv /*M*2*/, const int64_t* cam_idx /*M*/, const int64_t* pt_idx /*M*/,
+                  const double* weights /*M or NULL*/, const sba_upload_opts* opts /*NULL: defaults*/);
+/* What the last successful sba_upload / sba_upload_ex of the handle did (not defined after a failed one). */
+int sba_get_upload_report(sba_handle* h, sba_upload_report* report);
+/* The layout as it lies on the device, widened to float64; any pointer may be NULL.  perm M (point-major position -> caller's
+ * index), pt_start N+1, cam_pm / pt_pm / w_pm M and uv_pm M*2 (point-major), pt_cm / w_cm M and uv_cm M*2 (camera-major),
+ * cam_start C+1, vis_mask N (bit c: camera c sees the point; zeros when the handle keeps none: more than 16 cameras,
+ * duplicate pairs, or a dense list laid out by the dense kernel).  w_pm / w_cm are ones when no weights were given. */
+int sba_get_layout(sba_handle* h, int64_t* perm, int32_t* pt_start, int32_t* cam_pm, int32_t* pt_pm, double* uv_pm,
+                   double* w_pm, int32_t* pt_cm, double* uv_cm, double* w_cm, int32_t* cam_start, uint16_t* vis_mask);
 int sba_set_params(sba_handle* h, const double* x /*11C+3N*/);
 int sba_get_params(sba_handle* h, double* cams_out /*C*11*/, double* points_out /*N*3*/);
 int sba_destroy(sba_handle* h);

@@ -23,7 +23,7 @@ NSCALARS = 8
 # every symbol include/sba_hip.h declares (tests/test_cabi_symbols.py checks the .so exports all of them)
 EXPORTED_SYMBOLS = (
     "sba_abi_version", "sba_device_count", "sba_last_error", "sba_rotate", "sba_project", "sba_project_model",
-    "sba_create", "sba_upload", "sba_set_params", "sba_get_params", "sba_destroy",
+    "sba_create", "sba_upload", "sba_upload_ex", "sba_get_upload_report", "sba_get_layout", "sba_set_params", "sba_get_params", "sba_destroy",
     "sba_get_gradient", "sba_get_transform", "sba_lm_get_step", "sba_ipc_export", "sba_ipc_attach", "sba_residual", "sba_residual_jacobian", "sba_solve_lm",
     "sba_lm_exchange_size", "sba_lm_begin", "sba_lm_linearize", "sba_lm_form_reduced",
     "sba_lm_solve_trial", "sba_lm_decide", "sba_lm_decide_async", "sba_lm_poll", "sba_lm_run", "sba_lm_finish", "sba_lm_get_log", "sba_time_kernel", "sba_get_kernel_profile",
@@ -71,6 +71,23 @@ class CovReport(C.Structure):
                 ("info", C.c_int32), ("n_points_anchored", C.c_int32), ("gauge_residual", C.c_double),
                 ("seconds_device", C.c_double), ("seconds_form", C.c_double), ("seconds_inverse", C.c_double),
                 ("seconds_points", C.c_double), ("seconds_total", C.c_double)]
+
+
+class UploadOpts(C.Structure):
+    _fields_ = [("obs_on_device", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class UploadReport(C.Structure):
+    _fields_ = [("route", C.c_int32), ("decline_reason", C.c_int32), ("dense", C.c_int32), ("masked", C.c_int32),
+                ("group_indexed", C.c_int32), ("identity_perm", C.c_int32), ("n_blocks", C.c_int32), ("n_chunks", C.c_int32),
+                ("max_degree", C.c_int32), ("stream_syncs", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("seconds_total", C.c_double), ("seconds_h2d", C.c_double), ("seconds_device_layout", C.c_double),
+                ("seconds_host_layout", C.c_double), ("seconds_tables", C.c_double)]
+
+
+LAYOUT_ROUTES = {"auto": 0, "host": 1, "device": 2}                       # sba_layout_route
+UPLOAD_ROUTE_NAMES = ("host", "device dense", "device general")            # sba_upload_route
+DECLINE_NAMES = (None, "index out of range", "duplicate pair", "more than 256 observations of a point")   # sba_layout_decline
 
 
 class Covariance:
@@ -142,6 +159,9 @@ def load():
         "sba_project_model": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, dp, dp, dp]),
         "sba_create": (C.c_int, [C.POINTER(ProblemDesc), C.POINTER(H)]),
         "sba_upload": (C.c_int, [H, dp, dp, dp, ip, ip, dp]),
+        "sba_upload_ex": (C.c_int, [H, dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UploadOpts)]),
+        "sba_get_upload_report": (C.c_int, [H, C.POINTER(UploadReport)]),
+        "sba_get_layout": (C.c_int, [H] + [C.c_void_p] * 11),
         "sba_set_params": (C.c_int, [H, dp]),
         "sba_get_params": (C.c_int, [H, dp, dp]),
         "sba_destroy": (C.c_int, [H]),
@@ -194,6 +214,21 @@ def _iptr(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _is_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
+
+
+def _device_tensor(name, t, dtype, device):
+    """A torch tensor handed over as a device pointer: on the handle's device, float64 / int64, contiguous."""
+    if not t.is_cuda or (t.device.index or 0) != device:
+        raise ValueError(f"{name}: the tensor must live on the handle's device (cuda:{device})")
+    if str(t.dtype) != "torch." + dtype:
+        raise ValueError(f"{name}: the tensor must be {dtype}, not {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: the tensor must be contiguous")
+    return t
 
 
 def _check(rc, handle=None):
@@ -264,26 +299,40 @@ def rotate_rows(points, rot_vecs, dtype=SBA_F64, device=0):
 class Problem:
     """One device-resident bundle-adjustment problem (wraps an sba_handle)."""
 
-    def __init__(self, cams, pts, uv, cam_idx, pt_idx, weights=None, dtype=SBA_F64, device=0, stream=None):
+    def __init__(self, cams, pts, uv, cam_idx, pt_idx, weights=None, dtype=SBA_F64, device=0, stream=None, layout="auto"):
+        """uv, cam_idx, pt_idx and weights are numpy arrays (anything numpy converts), or torch tensors on the handle's
+        device (float64 / int64, contiguous): those are handed to the library as device pointers.  layout: "auto" (by size),
+        "host" (the host pass) or "device" (try the device pass at any size)."""
         lib = load()
         self._lib = lib
+        if layout not in LAYOUT_ROUTES:
+            raise ValueError("layout must be 'auto', 'host' or 'device'")
         self.cams0, self.pts0 = _f64(cams), _f64(pts)
-        uv = _f64(uv)
-        ci = np.ascontiguousarray(cam_idx, dtype=np.int64).reshape(-1)
-        pi = np.ascontiguousarray(pt_idx, dtype=np.int64).reshape(-1)
-        self.C, self.N, self.M = self.cams0.shape[0], self.pts0.shape[0], ci.shape[0]
+        named = (("points_2d", uv, "float64"), ("camera_ind", cam_idx, "int64"), ("point_ind", pt_idx, "int64"),
+                 ("weights", weights, "float64"))
+        tensors = [_is_tensor(a) for _n, a, _d in named if a is not None]
+        on_device = any(tensors)
+        if on_device and not all(tensors):
+            raise ValueError("points_2d, camera_ind, point_ind and weights must be all numpy arrays or all torch tensors")
+        if on_device:
+            uv, ci, pi, w = (None if a is None else _device_tensor(nm, a, dt, device) for nm, a, dt in named)
+            ci, pi = ci.reshape(-1), pi.reshape(-1)
+            w = None if w is None else w.reshape(-1)
+        else:
+            uv = _f64(uv)
+            ci = np.ascontiguousarray(cam_idx, dtype=np.int64).reshape(-1)
+            pi = np.ascontiguousarray(pt_idx, dtype=np.int64).reshape(-1)
+            w = None if weights is None else _f64(weights).reshape(-1)
+        self.C, self.N, self.M = self.cams0.shape[0], self.pts0.shape[0], int(ci.shape[0])
         if self.cams0.ndim != 2 or self.cams0.shape[1] not in (11, 13):
             raise ValueError("cameraArray must have shape (n_cameras, 11) (or (n_cameras, 13) with tangential distortion)")
         self.P = self.cams0.shape[1]
         if self.pts0.ndim != 2 or self.pts0.shape[1] != 3:
             raise ValueError("points3D must have shape (n_points, 3)")
-        if uv.shape != (self.M, 2) or pi.shape[0] != self.M:
+        if tuple(uv.shape) != (self.M, 2) or pi.shape[0] != self.M:
             raise ValueError("points2D must be (n_observations, 2) and index arrays (n_observations,)")
-        w = None
-        if weights is not None:
-            w = _f64(weights).reshape(-1)
-            if w.shape[0] != self.M:
-                raise ValueError("pointWeights must have one entry per observation")
+        if w is not None and w.shape[0] != self.M:
+            raise ValueError("pointWeights must have one entry per observation")
         self.dtype = dtype_code(dtype)
         # stream=None: private stream.  stream=<int handle>: run on it (0 = the legacy default stream).
         desc = ProblemDesc(self.C, self.N, self.M, self.dtype, device,
@@ -292,11 +341,42 @@ class Problem:
         h = C.c_void_p()
         _check(lib.sba_create(C.byref(desc), C.byref(h)))
         self._h = h
-        try:
-            _check(lib.sba_upload(h, _dptr(self.cams0), _dptr(self.pts0), _dptr(uv), _iptr(ci), _iptr(pi), _dptr(w)), h)
+        opts = UploadOpts(1 if on_device else 0, LAYOUT_ROUTES[layout], (C.c_int32 * 6)())
+        if on_device:
+            import torch
+            torch.cuda.current_stream(device).synchronize()      # the tensors are complete before the library reads them
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+        else:
+            ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)     # noqa: E731
+        try:        # (uv, ci, pi, w stay referenced until the upload has returned)
+            _check(lib.sba_upload_ex(h, _dptr(self.cams0), _dptr(self.pts0), ptr(uv), ptr(ci), ptr(pi), ptr(w), C.byref(opts)), h)
         except Exception:
             self.close()
             raise
+
+    # -- what sba_upload did, and the layout it left on the device (include/sba_hip.h)
+    def upload_report(self):
+        """dict: route ('host' / 'device dense' / 'device general'), decline_reason (None or a text), the layout flags, counts,
+        stream_syncs and the phase seconds of the upload."""
+        rep = UploadReport()
+        _check(self._lib.sba_get_upload_report(self._h, C.byref(rep)), self._h)
+        out = {name: getattr(rep, name) for name, _t in UploadReport._fields_ if name != "reserved"}
+        out["route"] = UPLOAD_ROUTE_NAMES[rep.route]
+        out["decline_reason"] = DECLINE_NAMES[rep.decline_reason]
+        for k in ("dense", "masked", "group_indexed", "identity_perm"):
+            out[k] = bool(out[k])
+        return out
+
+    def layout(self):
+        """The layout as it lies on the device (float data widened to float64): perm, pt_start, cam_pm, pt_pm, uv_pm, w_pm,
+        pt_cm, uv_cm, w_cm, cam_start, vis_mask."""
+        M, N = self.M, self.N
+        out = dict(perm=np.empty(M, np.int64), pt_start=np.empty(N + 1, np.int32), cam_pm=np.empty(M, np.int32),
+                   pt_pm=np.empty(M, np.int32), uv_pm=np.empty((M, 2)), w_pm=np.empty(M), pt_cm=np.empty(M, np.int32),
+                   uv_cm=np.empty((M, 2)), w_cm=np.empty(M), cam_start=np.empty(self.C + 1, np.int32),
+                   vis_mask=np.empty(N, np.uint16))
+        _check(self._lib.sba_get_layout(self._h, *[C.c_void_p(a.ctypes.data) for a in out.values()]), self._h)
+        return out
 
     # -- multi-GPU inside the library (RCCL): after this, solve_lm runs the sharded loop on all ranks together
     def comm_init(self, unique_id, rank, n_ranks):

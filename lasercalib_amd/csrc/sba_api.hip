@@ -128,9 +128,31 @@ int sba_destroy(sba_handle* h) {
 
 int sba_upload(sba_handle* h, const double* cams, const double* points, const double* uv, const int64_t* cam_idx,
                const int64_t* pt_idx, const double* weights) {
+  return sba_upload_ex(h, cams, points, uv, cam_idx, pt_idx, weights, nullptr);
+}
+
+int sba_upload_ex(sba_handle* h, const double* cams, const double* points, const double* uv, const int64_t* cam_idx,
+                  const int64_t* pt_idx, const double* weights, const sba_upload_opts* opts) {
   if (!h) return SBA_ERR_INVALID;
   if (!cams || !points || ((!uv || !cam_idx || !pt_idx))) { h->err = "null argument"; return SBA_ERR_INVALID; }
-  return guarded(h, [&] { return h->eng->upload(cams, points, uv, cam_idx, pt_idx, weights); });
+  sba_upload_opts o{};
+  if (opts) o = *opts;
+  if (o.layout != SBA_LAYOUT_AUTO && o.layout != SBA_LAYOUT_HOST && o.layout != SBA_LAYOUT_DEVICE) {
+    h->err = "unknown layout route";
+    return SBA_ERR_INVALID;
+  }
+  return guarded(h, [&] { return h->eng->upload(cams, points, uv, cam_idx, pt_idx, weights, o); });
+}
+
+int sba_get_upload_report(sba_handle* h, sba_upload_report* report) {
+  if (!h || !report) return SBA_ERR_INVALID;
+  return guarded(h, [&] { return h->eng->upload_report(report); });
+}
+
+int sba_get_layout(sba_handle* h, int64_t* perm, int32_t* pt_start, int32_t* cam_pm, int32_t* pt_pm, double* uv_pm, double* w_pm,
+                   int32_t* pt_cm, double* uv_cm, double* w_cm, int32_t* cam_start, uint16_t* vis_mask) {
+  if (!h) return SBA_ERR_INVALID;
+  return guarded(h, [&] { return h->eng->get_layout(perm, pt_start, cam_pm, pt_pm, uv_pm, w_pm, pt_cm, uv_cm, w_cm, cam_start, vis_mask); });
 }
 
 int sba_set_params(sba_handle* h, const double* x) {

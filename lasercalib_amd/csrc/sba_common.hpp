@@ -257,7 +257,11 @@ struct EngineBase {
   std::string err;
   Arena arena;       // declared in the base: outlives every DevBuf member of the engine
   virtual void init(const sba_problem_desc& d) = 0;
-  virtual int upload(const double* cams, const double* pts, const double* uv, const int64_t* ci, const int64_t* pi, const double* w) = 0;
+  virtual int upload(const double* cams, const double* pts, const double* uv, const int64_t* ci, const int64_t* pi, const double* w,
+                     const sba_upload_opts& uo) = 0;
+  virtual int upload_report(sba_upload_report* rep) = 0;
+  virtual int get_layout(int64_t* perm, int32_t* pt_start, int32_t* cam_pm, int32_t* pt_pm, double* uv_pm, double* w_pm,
+                         int32_t* pt_cm, double* uv_cm, double* w_cm, int32_t* cam_start, uint16_t* vis_mask) = 0;
   virtual int set_params_x(const double* x) = 0;
   virtual int get_params(double* cams_out, double* pts_out) = 0;
   virtual int get_gradient(double* gc_out, double* gp_out) = 0;

@@ -12,6 +12,7 @@
 #include "sba_schur_f64.hpp"
 #include "sba_ipc.hpp"
 #include "sba_covariance.hpp"
+#include "sba_layout.hpp"
 
 namespace SBA_NS {
 using namespace sba_host;
@@ -498,22 +499,76 @@ struct Engine : EngineBase {
     HIPCHK(hipStreamSynchronize(stream));
   }
 
-  // ------------------------------------------------------------------ upload + host-side layout
-  int upload(const double* cams_h, const double* pts_h, const double* uv_h, const int64_t* ci_h,
-             const int64_t* pi_h, const double* w_h) override {
+  // ------------------------------------------------------------------ upload + layout (dense kernel, general device pass, host pass)
+  // An automatic upload of a list that is not the dense canonical one takes the general device pass (sba_layout.hpp) from this
+  // many observations on; below it the host pass stays (a short list costs the host less than the pass's launches and its
+  // read-back: DESIGN.md section 3 has the measurement).
+  static constexpr int64_t LAYOUT_DEVICE_MIN_OBS = 100000;
+  sba_upload_report up_rep{};             // what the last upload did (sba_get_upload_report)
+  std::vector<int32_t> cam_start_h;       // camera starts of the camera-major copy (sba_get_layout)
+  bool has_vis_mask = false;              // vis_mask holds the one-group visibility masks of this upload
+  DevBuf<int32_t> lay_deg, lay_cursor, lay_perm, lay_counts, lay_offs, lay_tiles;     // work space of the general device pass
+  DevBuf<unsigned long long> lay_keys;
+
+  int upload(const double* cams_h, const double* pts_h, const double* uv_in, const int64_t* ci_in,
+             const int64_t* pi_in, const double* w_in, const sba_upload_opts& uo) override {
     HIPCHK(hipSetDevice(device));
     const bool up_dbg = kn.upload_debug;
-    auto up_t0 = std::chrono::steady_clock::now();
+    up_rep = sba_upload_report{};
+    const auto up_begin = std::chrono::steady_clock::now();
+    auto up_t0 = up_begin;
+    double* up_phase = &up_rep.seconds_tables;       // the phase of the report the next lap is booked to
     auto up_lap = [&](const char* what) {
-      if (!up_dbg) return;
       const auto t = std::chrono::steady_clock::now();
-      fprintf(stderr, "[upload] %-28s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(t - up_t0).count());
+      const double s = std::chrono::duration<double>(t - up_t0).count();
+      *up_phase += s;
+      if (up_dbg) fprintf(stderr, "[upload] %-28s %7.3f ms\n", what, s * 1e3);
       up_t0 = t;
     };
+    auto up_sync = [&] { sync(); ++up_rep.stream_syncs; };
     if (C <= 0 || N < 0 || M < 0) { err = "bad problem size"; return SBA_ERR_INVALID; }
     if (C > MAX_CAMS) { err = "more than 128 cameras is not supported yet"; return SBA_ERR_UNSUPPORTED; }
     if (M > (int64_t)0x7fffffff - 1024) { err = "too many observations for int32 device indices"; return SBA_ERR_UNSUPPORTED; }
-    has_w = (w_h != nullptr);
+    has_w = (w_in != nullptr);
+    // The caller's raw arrays lie on the host (uv_h ...) or, with obs_on_device, on the device (uv_d ...); a route that needs
+    // the other side fetches it once.
+    const bool on_dev = uo.obs_on_device != 0;
+    const double *uv_h = on_dev ? nullptr : uv_in, *w_h = on_dev ? nullptr : w_in;
+    const int64_t *ci_h = on_dev ? nullptr : ci_in, *pi_h = on_dev ? nullptr : pi_in;
+    const double *uv_d = on_dev ? uv_in : nullptr, *w_d = on_dev ? w_in : nullptr;
+    const long long *ci_d = on_dev ? reinterpret_cast<const long long*>(ci_in) : nullptr;
+    const long long *pi_d = on_dev ? reinterpret_cast<const long long*>(pi_in) : nullptr;
+    std::vector<double> uv_hv, w_hv;
+    std::vector<int64_t> ci_hv, pi_hv;
+    auto raw_to_device = [&] {
+      if (uv_d) return;
+      double* const phase = up_phase;
+      up_phase = &up_rep.seconds_h2d;
+      raw_uv.alloc((size_t)M * 2); raw_ci.alloc(M); raw_pi.alloc(M);
+      if (has_w) raw_w.alloc(M);
+      HIPCHK(hipMemcpyAsync(raw_uv.p, uv_h, sizeof(double) * 2 * M, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(raw_ci.p, ci_h, sizeof(int64_t) * M, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(raw_pi.p, pi_h, sizeof(int64_t) * M, hipMemcpyHostToDevice, stream));
+      if (has_w) HIPCHK(hipMemcpyAsync(raw_w.p, w_h, sizeof(double) * M, hipMemcpyHostToDevice, stream));
+      uv_d = raw_uv.p; ci_d = raw_ci.p; pi_d = raw_pi.p; w_d = has_w ? raw_w.p : nullptr;
+      up_lap("raw H2D");
+      up_phase = phase;
+    };
+    auto raw_to_host = [&] {
+      if (!on_dev || uv_h || M == 0) return;
+      double* const phase = up_phase;
+      up_phase = &up_rep.seconds_h2d;
+      uv_hv.resize((size_t)M * 2); ci_hv.resize(M); pi_hv.resize(M);
+      if (has_w) w_hv.resize(M);
+      HIPCHK(hipMemcpyAsync(uv_hv.data(), uv_d, sizeof(double) * 2 * M, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(ci_hv.data(), ci_d, sizeof(int64_t) * M, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(pi_hv.data(), pi_d, sizeof(int64_t) * M, hipMemcpyDeviceToHost, stream));
+      if (has_w) HIPCHK(hipMemcpyAsync(w_hv.data(), w_d, sizeof(double) * M, hipMemcpyDeviceToHost, stream));
+      up_sync();
+      uv_h = uv_hv.data(); ci_h = ci_hv.data(); pi_h = pi_hv.data(); w_h = has_w ? w_hv.data() : nullptr;
+      up_lap("raw D2H");
+      up_phase = phase;
+    };
     // Device-side layout: when the list can only be the canonical dense one -- M = N*C -- the caller's raw
     // float64 / int64 arrays go to the GPU as they are and ONE kernel validates them (observation i must be point i / C, camera
     // i % C: that single test implies in-range, point-major, camera-minor, no duplicates, every camera sees every point),
@@ -524,34 +579,49 @@ struct Engine : EngineBase {
     bool sorted = true, cam_sorted = true;
     std::vector<uint16_t> vmask;
     bool nodup = (C <= GROUP_CAMS);
-    if (M > 0 && M == (int64_t)N * C) {
-      raw_uv.alloc((size_t)M * 2); raw_ci.alloc(M); raw_pi.alloc(M);
-      if (has_w) raw_w.alloc(M);
+    if (M > 0 && M == (int64_t)N * C && uo.layout != SBA_LAYOUT_HOST) {
+      raw_to_device();
       uv_pm.alloc(M); ci_pm.alloc(M); pi_pm.alloc(M); uv_cm.alloc(M); pi_cm.alloc(M); pt_start.alloc((size_t)N + 1);
       if (has_w) { w_pm.alloc(M); w_cm.alloc(M); }
       if (up_flag.n == 0) up_flag.alloc(1);
       up_flag.zero(stream);
-      HIPCHK(hipMemcpyAsync(raw_uv.p, uv_h, sizeof(double) * 2 * M, hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(raw_ci.p, ci_h, sizeof(int64_t) * M, hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(raw_pi.p, pi_h, sizeof(int64_t) * M, hipMemcpyHostToDevice, stream));
-      if (has_w) HIPCHK(hipMemcpyAsync(raw_w.p, w_h, sizeof(double) * M, hipMemcpyHostToDevice, stream));
-      up_lap("raw H2D");
+      up_phase = &up_rep.seconds_device_layout;
       hipLaunchKernelGGL(k_upload_dense<T>, dim3((unsigned)((std::max<int64_t>(M, N + 1) + 255) / 256)), dim3(256), 0, stream,
-                         reinterpret_cast<const double2*>(raw_uv.p), raw_ci.p, raw_pi.p, has_w ? raw_w.p : (const double*)nullptr, C, N, (long long)M,
+                         reinterpret_cast<const double2*>(uv_d), ci_d, pi_d, has_w ? w_d : (const double*)nullptr, C, N, (long long)M,
                          uv_pm.p, ci_pm.p, pi_pm.p, has_w ? w_pm.p : (T*)nullptr, uv_cm.p, pi_cm.p, has_w ? w_cm.p : (T*)nullptr,
                          pt_start.p, up_flag.p);
       int flag = 1;
       HIPCHK(hipMemcpyAsync(&flag, up_flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-      sync();
+      up_sync();
       up_lap("device validate + layout");
       dev_dense = (flag == 0);
     }
-    if (dev_dense) {
+    // Every other list -- sparse visibility, shuffled, camera-descending -- is laid out by the kernels of sba_layout.hpp from the same
+    // raw arrays; they decline (index out of range, duplicate pair in one camera group, a point with more than 256 observations)
+    // and the host pass below, which owns the error texts, takes over.
+    bool dev_general = false;
+    std::vector<int32_t> camcount_dev;
+    if (!dev_dense && M > 0 && N > 0 &&
+        (uo.layout == SBA_LAYOUT_DEVICE || (uo.layout == SBA_LAYOUT_AUTO && M >= LAYOUT_DEVICE_MIN_OBS))) {
+      raw_to_device();
+      up_phase = &up_rep.seconds_device_layout;
+      dev_general = layout_device(uv_d, ci_d, pi_d, has_w ? w_d : (const double*)nullptr, ptstart, camcount_dev);
+      up_lap("device layout (general)");
+    }
+    const bool dev_lay = dev_dense || dev_general;
+    up_phase = &up_rep.seconds_tables;
+    if (dev_general) {
+      nodup = (C <= GROUP_CAMS);                  // (a duplicate pair in one camera group is a decline)
+      dense = nodup && M == (int64_t)N * C;       // no duplicate and N * C observations: every camera sees every point
+    } else if (dev_dense) {
       ptstart.resize((size_t)N + 1);
       for (int p = 0; p <= N; ++p) ptstart[p] = p * C;
       dense = true; identity_perm = true; perm.clear();
       if (C > PM_BLOCK) { err = "a point has more than 256 observations"; return SBA_ERR_UNSUPPORTED; }
+      up_rep.max_degree = C;
     } else {
+    raw_to_host();
+    up_phase = &up_rep.seconds_host_layout;
     // one pass: range check, point-major order, and camera order inside a point (strictly increasing cameras inside every
     // point = no duplicate (point, camera) pair and already canonical: what get_points3d.py:78-86 emits)
     {
@@ -580,6 +650,7 @@ struct Engine : EngineBase {
     dense = (M == (int64_t)N * C);
     for (int p = 0; p < N && dense; ++p) dense = (ptstart[p + 1] - ptstart[p] == C);
     if (maxdeg > PM_BLOCK) { err = "a point has more than 256 observations"; return SBA_ERR_UNSUPPORTED; }
+    up_rep.max_degree = maxdeg;
     perm.resize(M);
     identity_perm = sorted;
     if (sorted) par_for(M, [&](int64_t lo, int64_t hi, int) { for (int64_t i = lo; i < hi; ++i) perm[i] = i; });   // (the canonical pass below may still reorder)
@@ -615,10 +686,11 @@ struct Engine : EngineBase {
     up_lap("validate + sort + canonical");
     }   // host validation
     masked_ok = nodup && !dense;
-    std::vector<T2> uvp(dev_dense ? 0 : M);
-    std::vector<T> wp(has_w && !dev_dense ? M : 0);
-    std::vector<int32_t> cip(dev_dense ? 0 : M), pip(dev_dense ? 0 : M);
-    if (!dev_dense) par_for(M, [&](int64_t lo, int64_t hi, int) {
+    if (!dev_lay) up_phase = &up_rep.seconds_host_layout;
+    std::vector<T2> uvp(dev_lay ? 0 : M);
+    std::vector<T> wp(has_w && !dev_lay ? M : 0);
+    std::vector<int32_t> cip(dev_lay ? 0 : M), pip(dev_lay ? 0 : M);
+    if (!dev_lay) par_for(M, [&](int64_t lo, int64_t hi, int) {
       for (int64_t k = lo; k < hi; ++k) {
         const int64_t i = perm[k];
         uvp[k].x = (T)uv_h[2 * i]; uvp[k].y = (T)uv_h[2 * i + 1];
@@ -646,14 +718,15 @@ struct Engine : EngineBase {
     // camera-major order of the pm list (stable => points ascending inside a camera)
     std::vector<int32_t> camcount(C + 1, 0);
     if (dev_dense) { for (int c = 0; c <= C; ++c) camcount[c] = c * N; }
+    else if (dev_general) camcount = camcount_dev;
     else {
       for (int64_t k = 0; k < M; ++k) camcount[cip[k] + 1]++;
       for (int c = 0; c < C; ++c) camcount[c + 1] += camcount[c];
     }
-    std::vector<T2> uvc(dev_dense ? 0 : M);
-    std::vector<T> wc(has_w && !dev_dense ? M : 0);
-    std::vector<int32_t> pic(dev_dense ? 0 : M);
-    if (!dev_dense) {
+    std::vector<T2> uvc(dev_lay ? 0 : M);
+    std::vector<T> wc(has_w && !dev_lay ? M : 0);
+    std::vector<int32_t> pic(dev_lay ? 0 : M);
+    if (!dev_lay) {
       std::vector<int32_t> fill(camcount.begin(), camcount.end() - 1);
       for (int64_t k = 0; k < M; ++k) {
         const int32_t d = fill[cip[k]]++;
@@ -679,7 +752,9 @@ struct Engine : EngineBase {
     npairs = (int)pga.size();
 
     up_lap("blocks + camera-major copies");
-    if (!dev_dense) {
+    up_phase = &up_rep.seconds_tables;
+    cam_start_h = camcount;
+    if (!dev_lay) {
       uv_pm.upload(uvp, stream); ci_pm.upload(cip, stream); pi_pm.upload(pip, stream);
       if (has_w) { w_pm.upload(wp, stream); w_cm.upload(wc, stream); }
       pt_start.upload(ptstart, stream);
@@ -698,7 +773,7 @@ struct Engine : EngineBase {
                          grp_start.p, up_flag.p);
       int flag = 1;
       HIPCHK(hipMemcpyAsync(&flag, up_flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-      sync();
+      up_sync();
       grp_indexed = (flag == 0);     // cameras strictly ascending inside every point; otherwise the producers scan
     }
     int ncu = 256;
@@ -719,7 +794,12 @@ struct Engine : EngineBase {
     E_own.alloc((size_t)n * n + 3 * n + 1); scal_own.alloc(NSCAL); delta_c.alloc(n);
     const int nres_blocks = (int)((M + PM_BLOCK - 1) / PM_BLOCK);
     const int nlinp = rt.nlinp;
-    if (rt.vis_mask) vis_mask.upload(vmask, stream);
+    // (the one-group visibility masks are kept whenever they exist, also for routes that do not read them: sba_get_layout)
+    if (dev_general) has_vis_mask = (C <= GROUP_CAMS);
+    else {
+      has_vis_mask = nodup && !vmask.empty();
+      if (has_vis_mask) vis_mask.upload(vmask, stream);
+    }
     if (rt.fused_ok) gdpart.alloc((size_t)ksplit * 2 * (rt.fused_wide ? WIDE_ROWS : GROUP_ROWS));
     if (rt.pairs_fold_u) gdpart.alloc((size_t)ngroups * ksplit * 2 * GROUP_ROWS);
     cost_part.alloc((size_t)std::max(std::max(std::max(std::max(nblk, nres_blocks), ksplit), nlinp), 1)); gmax_part.alloc(std::max(std::max(std::max(nblk, ksplit), nlinp), 1)); gmax_alt.alloc(std::max(std::max(std::max(nblk, ksplit), nlinp), 1));
@@ -727,11 +807,114 @@ struct Engine : EngineBase {
     //  dense rigs with few cameras -- 8 x 1000: 63 vs 32; sized for nblk alone the rows used to run over into the next buffer)
     trial_part.alloc((size_t)4 * std::max(std::max(nblk, rt.nbs_dense), 1));
     up_lap("allocations + H2D enqueue");
-    sync();   // the staging vectors go out of scope now
+    up_sync();   // the staging vectors go out of scope now
     up_lap("H2D completion");
     uploaded = true;
     cur = 0;
     set_params(cams_h, pts_h);
+    ++up_rep.stream_syncs;         // (set_params waits for its copies)
+    up_lap("parameters");
+    up_rep.route = dev_dense ? SBA_ROUTE_DEVICE_DENSE : dev_general ? SBA_ROUTE_DEVICE_GENERAL : SBA_ROUTE_HOST;
+    up_rep.dense = dense; up_rep.masked = masked_ok; up_rep.group_indexed = grp_indexed; up_rep.identity_perm = identity_perm;
+    up_rep.n_blocks = nblk; up_rep.n_chunks = nchunk;
+    up_rep.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - up_begin).count();
+    return SBA_OK;
+  }
+
+  int upload_report(sba_upload_report* rep) override {
+    if (!uploaded) { err = "sba_upload has not been called"; return SBA_ERR_STATE; }
+    *rep = up_rep;
+    return SBA_OK;
+  }
+
+  // The general device pass (sba_layout.hpp).  true: the layout buffers are built, ptstart / camcount / perm / identity_perm and
+  // the report's max_degree are set; false: the pass declined (up_rep.decline_reason) and the host pass has to run.
+  // Stream synchronisations: one for the point starts, the camera starts and the flags, one more for the permutation when it
+  // is not the identity.
+  bool layout_device(const double* uv_d, const long long* ci_d, const long long* pi_d, const double* w_d,
+                     std::vector<int32_t>& ptstart, std::vector<int32_t>& camcount) {
+    static_assert(LAY_MAX_CAMS == MAX_CAMS && LAY_CAM_START + MAX_CAMS + 1 <= LAY_HEAD, "layout head record");
+    const int Mi = (int)M, gM = (Mi + 255) / 256, gN = (N + 255) / 256, nwg = gM;
+    const int ncnt = C * nwg;                     // (M < 2^31 - 1024 and C <= 128: below 2^31)
+    const int tN = (N + LAY_TILE - 1) / LAY_TILE, tC = (ncnt + LAY_TILE - 1) / LAY_TILE;
+    uv_pm.alloc(M); ci_pm.alloc(M); pi_pm.alloc(M); uv_cm.alloc(M); pi_cm.alloc(M);
+    if (has_w) { w_pm.alloc(M); w_cm.alloc(M); }
+    pt_start.alloc((size_t)N + 1 + LAY_HEAD);
+    lay_deg.alloc(N); lay_cursor.alloc(N); lay_perm.alloc(M); lay_keys.alloc(M);
+    lay_counts.alloc(ncnt); lay_offs.alloc(ncnt); lay_tiles.alloc(std::max(tN, tC));
+    if (C <= GROUP_CAMS) vis_mask.alloc(N);
+    int* head = pt_start.p + N + 1;
+    T* wpm = has_w ? w_pm.p : (T*)nullptr;
+    auto scan = [&](const int* in, int cnt, int ntiles, int* out, int want_total, int* max_out) {
+      hipLaunchKernelGGL(k_lay_tile_sums, dim3(ntiles), dim3(256), 0, stream, in, cnt, lay_tiles.p, max_out);
+      hipLaunchKernelGGL(k_lay_scan_tiles, dim3(1), dim3(256), 0, stream, lay_tiles.p, ntiles);
+      hipLaunchKernelGGL(k_lay_scan_apply, dim3(ntiles), dim3(256), 0, stream, in, cnt, (const int*)lay_tiles.p, out, want_total);
+    };
+    hipLaunchKernelGGL(k_lay_init, dim3(std::max(gN, 1)), dim3(256), 0, stream, lay_deg.p, lay_cursor.p, N, head);
+    hipLaunchKernelGGL(k_lay_scan_obs, dim3(gM), dim3(256), 0, stream, ci_d, pi_d, Mi, C, N, lay_deg.p, head);
+    scan(lay_deg.p, N, tN, pt_start.p, 1, head + LAY_MAXDEG);
+    hipLaunchKernelGGL(k_lay_scatter, dim3(gM), dim3(256), 0, stream, (const int*)head, ci_d, pi_d, Mi, C, (const int*)pt_start.p,
+                       lay_cursor.p, lay_keys.p);
+    hipLaunchKernelGGL(k_lay_rank, dim3(gM), dim3(256), 0, stream, head, (const unsigned long long*)lay_keys.p, pi_d, Mi, C,
+                       (const int*)pt_start.p, lay_perm.p);
+    hipLaunchKernelGGL(k_lay_gather<T>, dim3(gM), dim3(256), 0, stream, (const int*)head, (const int*)lay_perm.p,
+                       reinterpret_cast<const double2*>(uv_d), ci_d, pi_d, w_d, Mi, C, uv_pm.p, ci_pm.p, pi_pm.p, wpm);
+    if (C <= GROUP_CAMS)
+      hipLaunchKernelGGL(k_lay_mask, dim3(gN), dim3(256), 0, stream, (const int*)head, (const int32_t*)ci_pm.p, (const int*)pt_start.p, N,
+                         vis_mask.p);
+    hipLaunchKernelGGL(k_lay_cm_count, dim3(nwg), dim3(256), 0, stream, (const int*)head, (const int32_t*)ci_pm.p, Mi, C, nwg, lay_counts.p);
+    scan(lay_counts.p, ncnt, tC, lay_offs.p, 0, (int*)nullptr);
+    hipLaunchKernelGGL(k_lay_cm_starts, dim3(1), dim3(256), 0, stream, (const int*)lay_offs.p, Mi, C, nwg, head);
+    hipLaunchKernelGGL(k_lay_cm_scatter<T>, dim3(nwg), dim3(256), 0, stream, (const int*)head, (const int32_t*)ci_pm.p,
+                       (const int32_t*)pi_pm.p, (const T2*)uv_pm.p, (const T*)wpm, Mi, C, nwg, (const int*)lay_offs.p, uv_cm.p, pi_cm.p,
+                       has_w ? w_cm.p : (T*)nullptr);
+    std::vector<int32_t> hs((size_t)N + 1 + LAY_HEAD);
+    HIPCHK(hipMemcpyAsync(hs.data(), pt_start.p, sizeof(int32_t) * hs.size(), hipMemcpyDeviceToHost, stream));
+    sync(); ++up_rep.stream_syncs;
+    HIPCHK(hipGetLastError());
+    const int32_t* hh = hs.data() + N + 1;
+    up_rep.max_degree = hh[LAY_MAXDEG];
+    up_rep.decline_reason = hh[LAY_BAD] != 0x7fffffff ? SBA_DECLINE_INDEX_RANGE : hh[LAY_MAXDEG] > PM_BLOCK ? SBA_DECLINE_DEGREE
+                            : hh[LAY_DUP] ? SBA_DECLINE_DUPLICATE : SBA_DECLINE_NONE;
+    if (up_rep.decline_reason != SBA_DECLINE_NONE) return false;
+    identity_perm = !hh[LAY_UNSORTED] && (!hh[LAY_CAM_UNSORTED] || C > GROUP_CAMS);
+    camcount.assign(hh + LAY_CAM_START, hh + LAY_CAM_START + C + 1);
+    hs.resize((size_t)N + 1);
+    ptstart.swap(hs);
+    perm.clear();
+    if (!identity_perm) {
+      std::vector<int32_t> p32(M);
+      HIPCHK(hipMemcpyAsync(p32.data(), lay_perm.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost, stream));
+      sync(); ++up_rep.stream_syncs;
+      perm.resize(M);
+      par_for(M, [&](int64_t lo, int64_t hi, int) { for (int64_t k = lo; k < hi; ++k) perm[k] = p32[k]; });
+    }
+    return true;
+  }
+
+  int get_layout(int64_t* perm_o, int32_t* pt_start_o, int32_t* cam_pm_o, int32_t* pt_pm_o, double* uv_pm_o, double* w_pm_o,
+                 int32_t* pt_cm_o, double* uv_cm_o, double* w_cm_o, int32_t* cam_start_o, uint16_t* vis_o) override {
+    if (!uploaded) { err = "sba_upload has not been called"; return SBA_ERR_STATE; }
+    HIPCHK(hipSetDevice(device));
+    if (perm_o) for (int64_t k = 0; k < M; ++k) perm_o[k] = identity_perm ? k : perm[k];
+    auto ints = [&](const DevBuf<int32_t>& b, size_t cnt, int32_t* out) {
+      if (out && cnt) HIPCHK(hipMemcpyAsync(out, b.p, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, stream));
+    };
+    ints(pt_start, (size_t)N + 1, pt_start_o); ints(ci_pm, M, cam_pm_o); ints(pi_pm, M, pt_pm_o); ints(pi_cm, M, pt_cm_o);
+    std::vector<T2> u_pm(uv_pm_o ? M : 0), u_cm(uv_cm_o ? M : 0);
+    std::vector<T> ww_pm(w_pm_o && has_w ? M : 0), ww_cm(w_cm_o && has_w ? M : 0);
+    if (!u_pm.empty()) HIPCHK(hipMemcpyAsync(u_pm.data(), uv_pm.p, sizeof(T2) * M, hipMemcpyDeviceToHost, stream));
+    if (!u_cm.empty()) HIPCHK(hipMemcpyAsync(u_cm.data(), uv_cm.p, sizeof(T2) * M, hipMemcpyDeviceToHost, stream));
+    if (!ww_pm.empty()) HIPCHK(hipMemcpyAsync(ww_pm.data(), w_pm.p, sizeof(T) * M, hipMemcpyDeviceToHost, stream));
+    if (!ww_cm.empty()) HIPCHK(hipMemcpyAsync(ww_cm.data(), w_cm.p, sizeof(T) * M, hipMemcpyDeviceToHost, stream));
+    if (vis_o && has_vis_mask && N) HIPCHK(hipMemcpyAsync(vis_o, vis_mask.p, sizeof(uint16_t) * N, hipMemcpyDeviceToHost, stream));
+    sync();
+    for (size_t k = 0; k < u_pm.size(); ++k) { uv_pm_o[2 * k] = (double)u_pm[k].x; uv_pm_o[2 * k + 1] = (double)u_pm[k].y; }
+    for (size_t k = 0; k < u_cm.size(); ++k) { uv_cm_o[2 * k] = (double)u_cm[k].x; uv_cm_o[2 * k + 1] = (double)u_cm[k].y; }
+    if (w_pm_o) for (int64_t k = 0; k < M; ++k) w_pm_o[k] = has_w ? (double)ww_pm[k] : 1.0;
+    if (w_cm_o) for (int64_t k = 0; k < M; ++k) w_cm_o[k] = has_w ? (double)ww_cm[k] : 1.0;
+    if (cam_start_o) for (int c = 0; c <= C; ++c) cam_start_o[c] = cam_start_h[c];
+    if (vis_o && !has_vis_mask) for (int p = 0; p < N; ++p) vis_o[p] = 0;
     return SBA_OK;
   }
 

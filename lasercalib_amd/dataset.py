@@ -87,8 +87,9 @@ def concatenate_datasets(points_dataset: Sequence[Dict[str, object]], cumulative
 def is_point_major(point_ind: np.ndarray) -> bool:
     """True when observations are grouped by non-decreasing point index (what get_points3d.py:78-86 emits).
 
-    The device upload (``sba_upload``) keeps the caller's order in that case and only falls back to a counting sort
-    otherwise; either way results are reported in the caller's observation order.
+    The upload (``sba_upload``) keeps the caller's order in that case (up to the camera order inside a point on rigs of at
+    most 16 cameras) and sorts by point otherwise -- in kernels for long lists, on the host for short ones and for lists the
+    device pass declines; either way results are reported in the caller's observation order.
     """
     point_ind = np.asarray(point_ind)
     return bool(point_ind.size == 0 or np.all(point_ind[1:] >= point_ind[:-1]))

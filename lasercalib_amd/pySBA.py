@@ -194,7 +194,11 @@ class PySBA:
         self.point2DIndices = point2DIndices
         self.points3Dfixed = points3Dfixed
         if pointWeights is None:
-            pointWeights = np.full_like(point2DIndices, 1)     # integer ones (pySBA.py:57)
+            if _native._is_tensor(point2DIndices):             # device-resident observations: ones beside them
+                import torch
+                pointWeights = torch.ones_like(point2DIndices)
+            else:
+                pointWeights = np.full_like(point2DIndices, 1)     # integer ones (pySBA.py:57)
         self.pointWeights = pointWeights.reshape((-1, 1))
         self.points3Dfixed_labeled = None
 
@@ -246,6 +250,12 @@ class PySBA:
 
     # ------------------------------------------------------------------ solvers
     def _weights_or_none(self):
+        if _native._is_tensor(self.pointWeights):              # passed through to the device upload unchanged
+            w = self.pointWeights.reshape(-1)
+            if w.numel() and bool((w == 1).all()):
+                return None
+            import torch
+            return w.to(torch.float64).contiguous()
         w = np.asarray(self.pointWeights).reshape(-1)
         if w.size and np.all(w == 1):
             return None          # unit weights: the kernels skip the multiply and the 8 B/obs read
@@ -333,8 +343,11 @@ class PySBA:
             x = np.hstack((cams_opt.ravel(), pts_opt.ravel()))
         message = TERMINATION_MESSAGES[rep.status]
         _print_table(log, rep.initial_cost, rep, message, verbose)
-        ci, pi = np.asarray(self.cameraIndices), np.asarray(self.point2DIndices)
+        # (the lazy fun / jac closures assemble on the host: device-resident index tensors are fetched once for them)
+        ci, pi = (a.cpu().numpy() if _native._is_tensor(a) else np.asarray(a) for a in (self.cameraIndices, self.point2DIndices))
         uv, w = self.points2D, self._weights_or_none()
+        if _native._is_tensor(uv):
+            uv, w = uv.cpu().numpy(), (None if w is None else w.cpu().numpy())
         dt, dev = _env_dtype(), _env_device()
 
         def make_jac():
