@@ -323,6 +323,62 @@ typedef struct {
 int sba_covariance(sba_handle* h, const sba_cov_opts* opts, double* cam_full /*n*n or NULL*/,
                    double* cam_blocks /*C*P*P or NULL*/, double* pt_cov /*N*6 or NULL*/, sba_cov_report* rep);
 
+/* ---------------------------------------------------------------- triangulation (3-D points from the current cameras and the pixels)
+ * sba_triangulate: for every point the weighted least-squares point closest to the rays of its observations, at the handle's
+ * CURRENT camera rows (11 or 13 columns) -- a starting point for sba_solve_lm where no z-plane is known, and a per-observation
+ * inlier flag before the solve starts.  All arithmetic is float64, for SBA_F32 handles too (their pixels and weights are widened
+ * on load).  Per observation of camera c with pixel (u, v) and weight w (1 when the handle has none):
+ *   1. xd = (u - cx) / f, yd = (v - cy) / f.
+ *   2. (x, y) with distort(x, y) = (xd, yd), distort being the forward model (radial d = 1 + k1 n + k2 n^2, n = x^2 + y^2, plus
+ *      OpenCV's tangential terms for 13-column rows): Newton from (xd, yd) with the analytic 2 x 2 Jacobian, at most 20 steps,
+ *      stopping when the step's infinity norm is at most 1e-15 max(1, |x|, |y|).  The observation is UNUSABLE when the
+ *      iteration does not converge, meets a non-positive Jacobian determinant (the folded-back region of a non-monotone
+ *      distortion) or a non-finite value; w == 0 is unusable too.
+ *   3. ray: direction d = normalise(R^T (x, y, 1)), origin c = -R^T t, R the Rodrigues matrix of the row.
+ * Per point over its usable observations, P_o = I - d_o d_o^T, omega_o = w_o^2:
+ *   4. A = sum omega_o P_o, b = sum omega_o P_o c_o, X = A^-1 b by a 3 x 3 Cholesky factorisation; a pivot at or below 1e-12 of
+ *      its diagonal entry means the rays do not fix the point (the pivot test of sba_covariance's point blocks).
+ *   5. per used observation the pixel error e_o = ||project(X, cam_c) - (u, v)||_2 (unweighted, pixels) and the depth (R X + t)_z.
+ *   6. trimming (trim_px > 0, at most max_drop rounds): while max e_o > trim_px and more than max(min_views, 3) observations
+ *      are in use: for every used j the leave-one-out estimate X_j = (A - omega_j P_j)^-1 (b - omega_j P_j c_j) and m_j = the
+ *      largest error of the OTHER used observations at X_j (+inf when that system fails the pivot test); the observation
+ *      j* = argmin m_j (ties: the earlier position in the layout's point-major order) is dropped and the point continues from
+ *      X_j*; a point stops when every m_j is infinite.  Leave-one-out, not "drop the largest residual": at the least-squares
+ *      estimate of few views the outlier does not always have the largest error.
+ *   7. per point: X; status; n_views (observations in the final estimate); rms_px = sqrt(mean e_o^2) and max_px over them;
+ *      spread = 1 - ||mean of the used d_o||^2 (sin^2 of half the angle for two views; near 0 = no parallax).  Status, first
+ *      match wins: ANCHORED (held by sba_set_fixed_points: coordinates returned as held, observations not examined), TOO_FEW
+ *      (the usable observations come from fewer than min_views DISTINCT cameras: two pixels of one camera meet in its centre
+ *      and are one view), DEGENERATE (pivot test failed), BEHIND (some used depth <= 0; X is still reported), OK.
+ *      X is NaN for TOO_FEW and DEGENERATE; n_views is 0 and rms_px / max_px / spread are NaN for every point without estimate.
+ *   8. per observation, in the CALLER's order: inlier = 1 when the observation is in the final estimate of an OK or BEHIND
+ *      point or belongs to an anchored point, else 0 (unusable, trimmed, or its point has no estimate).
+ * Every output may be NULL.  opts NULL: {min_views 2, max_drop 1, trim_px 0 (no trimming), write_back 0}.  min_views < 2,
+ * trim_px < 0 or not finite, max_drop < 0 return SBA_ERR_INVALID.
+ * write_back = 0: the handle is left exactly as found (parameters, LM state, work buffers; private buffers freed on return).
+ * write_back = 1: the handle's current points are replaced by X where the status is OK, all others keep their coordinates,
+ * and the handle is in the state sba_set_params leaves it in: sba_solve_lm afterwards starts from the triangulated points.
+ * rep: the histogram of the status, n_obs_unusable (step 2; observations of anchored points are not examined and not counted),
+ * n_obs_trimmed, n_points_trimmed, HIP-event seconds of the kernels (seconds_linear: camera table + steps 1-5 and 7 for every
+ * point; seconds_trim: step 6; seconds_device: those plus the flag scatter and the write-back) and the wall time of the call.
+ * A handle of a multi-rank job (sba_comm_init / sba_ipc_attach) returns SBA_ERR_UNSUPPORTED. */
+typedef enum { SBA_TRI_OK = 0, SBA_TRI_ANCHORED = 1, SBA_TRI_TOO_FEW = 2, SBA_TRI_DEGENERATE = 3, SBA_TRI_BEHIND = 4 } sba_tri_status;
+typedef struct {
+  int32_t min_views;       /* distinct cameras a point needs (>= 2)                                      */
+  int32_t max_drop;        /* trimming rounds per point, i.e. observations a point may lose              */
+  double  trim_px;         /* 0: no trimming; > 0: trim while the largest pixel error exceeds it         */
+  int32_t write_back;      /* 1: X of the OK points replaces the handle's current points                 */
+  int32_t reserved[5];
+} sba_tri_opts;
+typedef struct {
+  int64_t n_ok, n_anchored, n_too_few, n_degenerate, n_behind, n_obs_unusable, n_obs_trimmed, n_points_trimmed;
+  double  seconds_device, seconds_linear, seconds_trim, seconds_total;
+} sba_tri_report;
+int sba_triangulate(sba_handle* h, const sba_tri_opts* opts /*NULL: {2, 1, 0.0, 0}*/,
+                    double* points_out /*N*3*/, int32_t* status_out /*N*/, int32_t* n_views_out /*N*/,
+                    double* rms_px_out /*N*/, double* max_px_out /*N*/, double* spread_out /*N*/,
+                    uint8_t* inlier_out /*M, caller's order*/, sba_tri_report* rep);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

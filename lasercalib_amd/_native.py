@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "sba_lm_exchange_size", "sba_lm_begin", "sba_lm_linearize", "sba_lm_form_reduced",
     "sba_lm_solve_trial", "sba_lm_decide", "sba_lm_decide_async", "sba_lm_poll", "sba_lm_run", "sba_lm_finish", "sba_lm_get_log", "sba_time_kernel", "sba_get_kernel_profile",
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
+    "sba_triangulate",
 )
 
 
@@ -73,6 +74,21 @@ class CovReport(C.Structure):
                 ("seconds_points", C.c_double), ("seconds_total", C.c_double)]
 
 
+class TriOpts(C.Structure):
+    _fields_ = [("min_views", C.c_int32), ("max_drop", C.c_int32), ("trim_px", C.c_double), ("write_back", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
+class TriReport(C.Structure):
+    _fields_ = [("n_ok", C.c_int64), ("n_anchored", C.c_int64), ("n_too_few", C.c_int64), ("n_degenerate", C.c_int64),
+                ("n_behind", C.c_int64), ("n_obs_unusable", C.c_int64), ("n_obs_trimmed", C.c_int64),
+                ("n_points_trimmed", C.c_int64), ("seconds_device", C.c_double), ("seconds_linear", C.c_double),
+                ("seconds_trim", C.c_double), ("seconds_total", C.c_double)]
+
+
+TRI_OK, TRI_ANCHORED, TRI_TOO_FEW, TRI_DEGENERATE, TRI_BEHIND = 0, 1, 2, 3, 4       # sba_tri_status
+
+
 class UploadOpts(C.Structure):
     _fields_ = [("obs_on_device", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32 * 6)]
 
@@ -109,6 +125,22 @@ class Covariance:
         if self.points is None:
             raise ValueError("the point covariance was not computed (points=False)")
         return np.sqrt(np.einsum("nii->ni", self.points))
+
+
+class Triangulation:
+    """Result of Problem.triangulate (sba_triangulate, include/sba_hip.h): ``points`` (N, 3), ``status`` (N,) of TRI_*,
+    ``n_views``, ``rms_px``, ``max_px``, ``spread`` (N,), ``inliers`` (M,) bool in the caller's observation order, the
+    report's counts and seconds as attributes, and ``ok``: the mask of the points with status TRI_OK."""
+
+    def __init__(self, points, status, n_views, rms_px, max_px, spread, inliers, rep):
+        self.points, self.status, self.n_views = points, status, n_views
+        self.rms_px, self.max_px, self.spread, self.inliers = rms_px, max_px, spread, inliers
+        for name, _t in TriReport._fields_:
+            setattr(self, name, getattr(rep, name))
+
+    @property
+    def ok(self):
+        return self.status == TRI_OK
 
 
 _lib = None
@@ -193,6 +225,8 @@ def load():
         "sba_set_fixed_points": (C.c_int, [H, C.c_void_p]),
         "sba_set_robust_loss": (C.c_int, [H, C.c_int32, C.c_double]),
         "sba_covariance": (C.c_int, [H, C.POINTER(CovOpts), dp, dp, dp, C.POINTER(CovReport)]),
+        "sba_triangulate": (C.c_int, [H, C.POINTER(TriOpts), dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, dp,
+                                      C.POINTER(C.c_uint8), C.POINTER(TriReport)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -431,6 +465,22 @@ class Problem:
         if pts is not None:
             pcov = pts[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(self.N, 3, 3)
         return Covariance(cams, cfull, pcov, rep)
+
+    # -- 3-D points from the current cameras and the pixels (sba_triangulate, include/sba_hip.h)
+    def triangulate(self, min_views=2, trim_px=None, max_drop=1, write_back=False):
+        """Least-squares intersection of the rays of every point at the handle's current cameras; trim_px: leave-one-out
+        trimming while a point's largest pixel error exceeds it (at most max_drop observations per point); write_back: the
+        estimates of the OK points become the handle's current points.  Returns a Triangulation."""
+        pts = np.empty((self.N, 3))
+        status, n_views = np.empty(self.N, np.int32), np.empty(self.N, np.int32)
+        rms, mx, spread = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        inl = np.empty(self.M, np.uint8)
+        rep = TriReport()
+        opts = TriOpts(int(min_views), int(max_drop), float(trim_px) if trim_px else 0.0, 1 if write_back else 0, (C.c_int32 * 5)())
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))      # noqa: E731
+        _check(self._lib.sba_triangulate(self._h, C.byref(opts), _dptr(pts), i32(status), i32(n_views), _dptr(rms), _dptr(mx),
+                                         _dptr(spread), inl.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rep)), self._h)
+        return Triangulation(pts, status, n_views, rms, mx, spread, inl != 0, rep)
 
     # -- lifetime
     def close(self):

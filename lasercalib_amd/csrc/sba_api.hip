@@ -289,6 +289,17 @@ int sba_covariance(sba_handle* h, const sba_cov_opts* opts, double* cam_full, do
   return guarded(h, [&] { return h->eng->covariance(&o, cam_full, cam_blocks, pt_cov, rep); });
 }
 
+int sba_triangulate(sba_handle* h, const sba_tri_opts* opts, double* points_out, int32_t* status_out, int32_t* n_views_out,
+                    double* rms_px_out, double* max_px_out, double* spread_out, uint8_t* inlier_out, sba_tri_report* rep) {
+  if (!h) return SBA_ERR_INVALID;
+  sba_tri_opts o{};
+  o.min_views = 2; o.max_drop = 1;
+  if (opts) o = *opts;
+  return guarded(h, [&] {
+    return h->eng->triangulate(&o, points_out, status_out, n_views_out, rms_px_out, max_px_out, spread_out, inlier_out, rep);
+  });
+}
+
 int sba_time_kernel(sba_handle* h, const char* name, int32_t reps, double* mean_us_out) {
   if (!h || !name || !mean_us_out) return SBA_ERR_INVALID;
   return guarded(h, [&] { return h->eng->time_kernel(name, reps, mean_us_out); });

@@ -289,6 +289,8 @@ struct EngineBase {
   virtual int set_fixed_points(const uint8_t* mask) = 0;
   virtual int set_robust_loss(int loss, double f_scale) = 0;
   virtual int covariance(const sba_cov_opts* o, double* cam_full, double* cam_blocks, double* pt_cov, sba_cov_report* rep) = 0;
+  virtual int triangulate(const sba_tri_opts* o, double* points_out, int32_t* status_out, int32_t* n_views_out, double* rms_out,
+                          double* max_out, double* spread_out, uint8_t* inlier_out, sba_tri_report* rep) = 0;
 };
 
 }  // namespace sba_host

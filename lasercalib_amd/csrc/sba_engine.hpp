@@ -12,6 +12,7 @@
 #include "sba_schur_f64.hpp"
 #include "sba_ipc.hpp"
 #include "sba_covariance.hpp"
+#include "sba_triangulate.hpp"
 #include "sba_layout.hpp"
 
 namespace SBA_NS {
@@ -2182,6 +2183,19 @@ struct Engine : EngineBase {
     CovIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
                 has_fixed ? pt_fixed_mask.p : nullptr, RLoss<double>{loss_delta, loss_kind}};
     return cov_run<T>(in, *o, cam_full, cam_blocks, pt_cov, rep, err);
+  }
+
+  // ------------------------------------------------------------------ triangulation (sba_triangulate.hpp)
+  int triangulate(const sba_tri_opts* o, double* points_out, int32_t* status_out, int32_t* n_views_out, double* rms_out,
+                  double* max_out, double* spread_out, uint8_t* inlier_out, sba_tri_report* rep) override {
+    static_assert(MAX_CAMS <= 128, "k_tri_linear keeps the camera set of a point in two 64-bit words");
+    if (!uploaded) { err = "sba_upload has not been called"; return SBA_ERR_STATE; }
+    if (multi()) { err = "sba_triangulate: a handle of a multi-rank job is not supported"; return SBA_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(device));
+    sync();
+    TriIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, ptsT[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
+                blk_desc.p, nblk, has_fixed ? pt_fixed_mask.p : nullptr, identity_perm ? nullptr : perm.data()};
+    return tri_run<T>(in, *o, points_out, status_out, n_views_out, rms_out, max_out, spread_out, inlier_out, rep, err);
   }
 
   // ------------------------------------------------------------------ small accessors of the C ABI

@@ -9,6 +9,12 @@ top-level I/O), so this module restates the array semantics, vectorised:
 * :func:`concatenate_datasets` -- calibrate_camera.py:32-44 (incl. the NON-cumulative point offset, see below)
 * :func:`is_point_major`       -- the ordering guarantee the device upload relies on to skip its counting sort
 
+Extensions (no counterpart in the reference, which needs a known z-plane and one "3-D init camera" for its starting points):
+
+* :func:`filter_points_by_views`      -- the count test of get_points3d.py:52-56 without the init-camera test
+* :func:`make_dataset_triangulated`   -- the dataset entry with ``points_3d`` triangulated on the device from all views
+* :func:`reindex_dataset`             -- its pure-numpy half: drop points / observations and renumber
+
 All arrays are numpy float64 / int64, exactly what ``PySBA.__init__`` (pySBA.py:28-59) takes.
 """
 from __future__ import annotations
@@ -17,7 +23,8 @@ from typing import Dict, List, Sequence
 
 import numpy as np
 
-__all__ = ["filter_points", "observation_list", "make_dataset", "concatenate_datasets", "is_point_major"]
+__all__ = ["filter_points", "observation_list", "make_dataset", "concatenate_datasets", "is_point_major",
+           "filter_points_by_views", "reindex_dataset", "make_dataset_triangulated"]
 
 
 def filter_points(centroids: np.ndarray, min_num_cam_per_point: int, cam_idx_3dpts: int) -> np.ndarray:
@@ -93,3 +100,54 @@ def is_point_major(point_ind: np.ndarray) -> bool:
     """
     point_ind = np.asarray(point_ind)
     return bool(point_ind.size == 0 or np.all(point_ind[1:] >= point_ind[:-1]))
+
+
+def filter_points_by_views(centroids: np.ndarray, min_num_cam_per_point: int) -> np.ndarray:
+    """Boolean keep-mask over the frames of one laser dataset: at least ``min_num_cam_per_point`` cameras saw the spot.
+
+    The count test of :func:`filter_points` (get_points3d.py:52-56) without its init-camera test: with
+    :func:`make_dataset_triangulated` no single camera has to see a frame for it to get a starting point.
+    """
+    centroids = np.asarray(centroids)
+    seen = ~np.isnan(centroids[:, 0, :])
+    return seen.sum(axis=1) >= int(min_num_cam_per_point)
+
+
+def reindex_dataset(n_cams: int, points_3d: np.ndarray, points_2d: np.ndarray, camera_ind: np.ndarray, point_ind: np.ndarray,
+                    keep_points: np.ndarray, keep_obs: np.ndarray = None) -> Dict[str, object]:
+    """Drop the points where ``keep_points`` is False (with all their observations) and the observations where ``keep_obs`` is
+    False, renumber the remaining points 0 .. n-1 in their old order and return a dataset entry (keys and dtypes of
+    :func:`make_dataset`).  The order of the remaining observations is kept, so a point-major list stays point-major."""
+    keep_points = np.asarray(keep_points, dtype=bool)
+    point_ind = np.asarray(point_ind, dtype=np.int64)
+    obs = keep_points[point_ind]
+    if keep_obs is not None:
+        obs = obs & np.asarray(keep_obs, dtype=bool)
+    new_index = np.cumsum(keep_points) - 1
+    return {
+        "n_cams": int(n_cams),
+        "n_pts": int(keep_points.sum()),
+        "points_2d": np.asarray(points_2d, dtype=np.float64)[obs].copy(),
+        "points_3d": np.asarray(points_3d, dtype=np.float64)[keep_points].copy(),
+        "camera_ind": np.asarray(camera_ind, dtype=np.int64)[obs].copy(),
+        "point_ind": new_index[point_ind[obs]].astype(np.int64),
+    }
+
+
+def make_dataset_triangulated(in_pts: np.ndarray, cameraArray: np.ndarray, min_views: int = 2, trim_px: float = None,
+                              max_drop: int = 1, dtype="f64", device: int = 0) -> Dict[str, object]:
+    """One dataset entry whose ``points_3d`` come from a device triangulation of ALL the views of a frame at ``cameraArray``
+    (``_native.Problem.triangulate``) instead of one camera un-projected onto a known z-plane (get_points3d.py:88-99).
+
+    Frames without an estimate (too few views, rays that do not fix the point, a point behind a camera) are dropped and the
+    list is re-indexed; with ``trim_px`` the observations the trimming removed are dropped too.  Same keys and dtypes as
+    :func:`make_dataset`.
+    """
+    from . import _native
+    in_pts = np.asarray(in_pts, dtype=np.float64)
+    camera_ind, point_ind, points_2d = observation_list(in_pts)
+    n_pts, n_cams = in_pts.shape[0], in_pts.shape[2]
+    with _native.Problem(cameraArray, np.zeros((n_pts, 3)), points_2d, camera_ind, point_ind, dtype=dtype, device=device) as prob:
+        tri = prob.triangulate(min_views=min_views, trim_px=trim_px, max_drop=max_drop)
+    keep_obs = tri.inliers if trim_px else None
+    return reindex_dataset(n_cams, tri.points, points_2d, camera_ind, point_ind, tri.ok, keep_obs)

@@ -333,6 +333,27 @@ class PySBA:
             self._apply_extensions(prob, pts.shape[0])
             return prob.covariance(scale=scale, full=False, points=points)
 
+    def triangulate(self, min_views=2, trim_px=None, max_drop=1, update=True):
+        """Extension: ``points3D`` from ``cameraArray`` and the pixels alone, on the device -- per point the weighted
+        least-squares intersection of the rays of its observations (``include/sba_hip.h``, sba_triangulate), a start for
+        ``bundleAdjust`` where no z-plane is known.  ``trim_px``: leave-one-out trimming of at most ``max_drop`` observations
+        of a point while its largest pixel error exceeds it.  The problem is built as ``covariance`` builds it (weights,
+        anchors, dtype, device).  ``update=True`` rebinds ``self.points3D`` to a new array holding the estimate where the
+        status is OK and the old coordinates elsewhere; the caller's array is never written.  Returns a
+        ``_native.Triangulation``: ``points``, ``status``, ``n_views``, ``rms_px``, ``max_px``, ``spread``, ``inliers`` (per
+        observation, the caller's order), ``ok``."""
+        cams = np.ascontiguousarray(self.cameraArray, dtype=np.float64)
+        pts = np.ascontiguousarray(self.points3D, dtype=np.float64)
+        with _native.Problem(cams, pts, self.points2D, self.cameraIndices, self.point2DIndices,
+                             weights=self._weights_or_none(), dtype=_env_dtype(), device=_env_device()) as prob:
+            mask = self._fixed_mask(pts.shape[0])
+            if mask is not None:
+                prob.set_fixed_points(mask)
+            tri = prob.triangulate(min_views=min_views, trim_px=trim_px, max_drop=max_drop)
+        if update:
+            self.points3D = np.where(tri.ok[:, None], tri.points, pts)
+        return tri
+
     def _package(self, mode, cams_opt, pts_opt, rep, log, fvec, verbose):
         C_, N_ = cams_opt.shape[0], pts_opt.shape[0]
         if mode == _native.MODE_POINTS_ONLY:
