@@ -379,6 +379,56 @@ int sba_triangulate(sba_handle* h, const sba_tri_opts* opts /*NULL: {2, 1, 0.0, 
                     double* rms_px_out /*N*/, double* max_px_out /*N*/, double* spread_out /*N*/,
                     uint8_t* inlier_out /*M, caller's order*/, sba_tri_report* rep);
 
+/* ---------------------------------------------------------------- similarity registration (a solution into a frame of the caller)
+ * A free bundle adjustment leaves the similarity gauge open: two solves of the same data differ by a scale, a rotation and a
+ * translation.  sba_align estimates dst ~ s R src + t from weighted correspondences and (apply = 1) moves every camera and
+ * point of the handle with it, so that every reprojection residual stays where it was.  All arrays are caller-owned host
+ * float64; all arithmetic is float64, for SBA_F32 handles too.
+ * Correspondences (either target may be NULL; both kinds go into the same sums; weights are plain w, not squared):
+ *   every point p with weight > 0:  src = the handle's current point p,                 dst = target_points[p]
+ *   every camera c with weight > 0: src = its current centre -R(rho_c)^T t_c,           dst = target_centres[c]
+ * Estimator (Umeyama / Horn):
+ *   1. W = sum w, m_s = sum w src / W, m_d = sum w dst / W.
+ *   2. a second pass over a = src - m_s, b = dst - m_d: H = sum w b a^T, v_a = sum w |a|^2, v_b = sum w |b|^2.
+ *   3. R = the rotation maximising tr(R^T H), det R = +1: the eigenvector of the largest eigenvalue of Horn's symmetric 4 x 4
+ *      matrix of H (cyclic Jacobi on the host), taken as unit quaternion with w >= 0.  With H = U S V^T and
+ *      d = sign det(U V^T) this is U diag(1, 1, d) V^T.
+ *   4. s = tr(R^T H) / v_a, or 1 when with_scale == 0; t = m_d - s R m_s.
+ *   5. a third pass: rms_before = sqrt(sum w |dst - src|^2 / W), rms_after the same with s R src + t for src, max_after the
+ *      largest unweighted distance |dst - (s R src + t)| among the used correspondences (millimetres, the points' unit).
+ * The sums are per-workgroup partials added in index order: two calls on the same values return the same bits.
+ * SBA_ERR_INVALID, with the handle left untouched: a weight that is negative or not finite; a target that is not finite where
+ * its weight is positive; fewer than 3 correspondences in use; a rotation that is not unique: with the singular values
+ * s1 >= s2 >= s3 of H, s2 + d s3 <= 1e-10 s1 (collinear or coincident correspondences).  A handle of a multi-rank job returns
+ * SBA_ERR_UNSUPPORTED, a handle between sba_lm_begin and sba_lm_finish SBA_ERR_STATE.
+ * Apply (apply = 1, and always for sba_apply_similarity): points X <- s R X + t; cameras R(rho') = R(rho) R^T,
+ * t' = s t_c - R(rho') t, all other columns unchanged.  rho' comes from the quaternion q(rho) q(R)^-1, normalised to w >= 0:
+ * theta = 2 atan2(|v|, w), rho' = v theta / |v| (2 v for |v| < 1e-12).  Anchored points move with everything else.  Afterwards
+ * the handle is in the state sba_set_params leaves for the transformed values.
+ * sba_apply_similarity refuses (SBA_ERR_INVALID) a scale that is not positive and finite, an R with max |R^T R - I| > 1e-9 or
+ * det R < 0, and a t that is not finite.
+ * rep: the estimate, the three distances, the counts of used points and cameras, the singular values of H (descending), the
+ * HIP-event seconds of the kernels and the wall time of the call. */
+typedef struct {
+  int32_t with_scale;      /* 0: scale fixed at 1                                                        */
+  int32_t apply;           /* 1: transform the handle's current cameras and points                       */
+  int32_t reserved[6];
+} sba_align_opts;
+typedef struct {
+  double  scale, R[9] /*row-major*/, t[3];
+  double  rms_before, rms_after, max_after;
+  int64_t n_points_used;
+  int32_t n_cams_used;
+  int32_t reserved;
+  double  sv[3];
+  double  seconds_device, seconds_total;
+} sba_align_report;
+int sba_align(sba_handle* h, const sba_align_opts* opts /*NULL: {1, 1}*/,
+              const double* target_points /*N*3 or NULL*/, const double* point_weights /*N or NULL = ones*/,
+              const double* target_centres /*C*3 or NULL*/, const double* centre_weights /*C or NULL = ones*/,
+              sba_align_report* rep);
+int sba_apply_similarity(sba_handle* h, double scale, const double* R /*9, row-major*/, const double* t /*3*/);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

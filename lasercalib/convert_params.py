@@ -7,7 +7,7 @@ import importlib.util as _ilu
 import os as _os
 
 from lasercalib_amd.convert_params import (  # noqa: F401
-    camera_array_to_readable, initialize_from_checkerboard, read_opencv_yaml, readable_format_to_aruco_format,
+    apply_similarity_to_camlist, camera_array_to_readable, initialize_from_checkerboard, read_opencv_yaml, readable_format_to_aruco_format,
     readable_to_red_format, save_aruco_format, sba_to_readable_format, write_opencv_yaml,
 )
 

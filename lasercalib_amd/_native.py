@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = (
     "sba_lm_exchange_size", "sba_lm_begin", "sba_lm_linearize", "sba_lm_form_reduced",
     "sba_lm_solve_trial", "sba_lm_decide", "sba_lm_decide_async", "sba_lm_poll", "sba_lm_run", "sba_lm_finish", "sba_lm_get_log", "sba_time_kernel", "sba_get_kernel_profile",
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
-    "sba_triangulate",
+    "sba_triangulate", "sba_align", "sba_apply_similarity",
 )
 
 
@@ -89,6 +89,16 @@ class TriReport(C.Structure):
 TRI_OK, TRI_ANCHORED, TRI_TOO_FEW, TRI_DEGENERATE, TRI_BEHIND = 0, 1, 2, 3, 4       # sba_tri_status
 
 
+class AlignOpts(C.Structure):
+    _fields_ = [("with_scale", C.c_int32), ("apply", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class AlignReport(C.Structure):
+    _fields_ = [("scale", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_before", C.c_double),
+                ("rms_after", C.c_double), ("max_after", C.c_double), ("n_points_used", C.c_int64), ("n_cams_used", C.c_int32),
+                ("reserved", C.c_int32), ("sv", C.c_double * 3), ("seconds_device", C.c_double), ("seconds_total", C.c_double)]
+
+
 class UploadOpts(C.Structure):
     _fields_ = [("obs_on_device", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32 * 6)]
 
@@ -141,6 +151,24 @@ class Triangulation:
     @property
     def ok(self):
         return self.status == TRI_OK
+
+
+class Alignment:
+    """Result of Problem.align (sba_align, include/sba_hip.h): the similarity dst ~ scale R src + t as ``scale``, ``R`` (3, 3),
+    ``t`` (3,), the distances ``rms_before``, ``rms_after``, ``max_after``, the counts ``n_points_used``, ``n_cams_used``, the
+    singular values ``sv`` (3,) of the correlation matrix and the report's seconds."""
+
+    def __init__(self, rep):
+        self.scale = rep.scale
+        self.R = np.array(rep.R, dtype=np.float64).reshape(3, 3)
+        self.t = np.array(rep.t, dtype=np.float64)
+        self.sv = np.array(rep.sv, dtype=np.float64)
+        for name in ("rms_before", "rms_after", "max_after", "n_points_used", "n_cams_used", "seconds_device", "seconds_total"):
+            setattr(self, name, getattr(rep, name))
+
+    def transform(self, X):
+        """scale R X + t for an (..., 3) array of points."""
+        return self.scale * (np.asarray(X, dtype=np.float64) @ self.R.T) + self.t
 
 
 _lib = None
@@ -227,6 +255,8 @@ def load():
         "sba_covariance": (C.c_int, [H, C.POINTER(CovOpts), dp, dp, dp, C.POINTER(CovReport)]),
         "sba_triangulate": (C.c_int, [H, C.POINTER(TriOpts), dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, dp,
                                       C.POINTER(C.c_uint8), C.POINTER(TriReport)]),
+        "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
+        "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -481,6 +511,36 @@ class Problem:
         _check(self._lib.sba_triangulate(self._h, C.byref(opts), _dptr(pts), i32(status), i32(n_views), _dptr(rms), _dptr(mx),
                                          _dptr(spread), inl.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rep)), self._h)
         return Triangulation(pts, status, n_views, rms, mx, spread, inl != 0, rep)
+
+    # -- similarity registration of the handle's current solution (sba_align, include/sba_hip.h)
+    def _targets(self, name, target, weights, rows):
+        if target is None:
+            return None, None
+        tgt = _f64(target)
+        if tgt.shape != (rows, 3):
+            raise ValueError(f"{name}: expected shape ({rows}, 3), got {tgt.shape}")
+        w = None if weights is None else _f64(weights)
+        if w is not None and w.shape != (rows,):
+            raise ValueError(f"{name}: expected ({rows},) weights, got {w.shape}")
+        return tgt, w
+
+    def align(self, target_points=None, point_weights=None, target_centres=None, centre_weights=None, with_scale=True, apply=True):
+        """The similarity that brings the handle's current points onto ``target_points`` (N, 3) and its camera centres onto
+        ``target_centres`` (C, 3), weighted (weight 0: not used); ``apply``: every camera and point of the handle is moved
+        with it, which leaves every residual where it was.  Returns an Alignment."""
+        tp, pw = self._targets("target_points", target_points, point_weights, self.N)
+        tc, cw = self._targets("target_centres", target_centres, centre_weights, self.C)
+        rep = AlignReport()
+        opts = AlignOpts(1 if with_scale else 0, 1 if apply else 0, (C.c_int32 * 6)())
+        _check(self._lib.sba_align(self._h, C.byref(opts), _dptr(tp), _dptr(pw), _dptr(tc), _dptr(cw), C.byref(rep)), self._h)
+        return Alignment(rep)
+
+    def apply_similarity(self, scale, R, t):
+        """Moves every camera and point of the handle by X -> scale R X + t (R: (3, 3) rotation, t: (3,))."""
+        R, t = _f64(R), _f64(t)
+        if R.shape != (3, 3) or t.shape != (3,):
+            raise ValueError("apply_similarity: R must be (3, 3) and t (3,)")
+        _check(self._lib.sba_apply_similarity(self._h, float(scale), _dptr(R), _dptr(t)), self._h)
 
     # -- lifetime
     def close(self):

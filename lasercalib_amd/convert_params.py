@@ -7,6 +7,7 @@ Mirrors the functions of the reference's ``lasercalib/convert_params.py`` that `
 * :func:`sba_to_readable_format`         -- convert_params.py:18-27   (``cameraArray`` row -> {'K','R','t','d'})
 * :func:`readable_to_red_format`         -- convert_params.py:7-16    ((C,25) table for "red")
 * :func:`readable_format_to_aruco_format`, :func:`save_aruco_format` -- convert_params.py:105-123 (-> OpenCV YAML)
+* :func:`apply_similarity_to_camlist`    -- scripts/register_world.py:90-103 (extrinsics moved into a registered frame)
 
 Differences, all deliberate:
   * the reference reads/writes the YAML through ``cv2.FileStorage``; OpenCV is not a dependency here -- the small
@@ -28,6 +29,7 @@ from scipy.spatial.transform import Rotation as R
 __all__ = [
     "read_opencv_yaml", "write_opencv_yaml", "initialize_from_checkerboard", "sba_to_readable_format",
     "readable_to_red_format", "readable_format_to_aruco_format", "save_aruco_format", "camera_array_to_readable",
+    "apply_similarity_to_camlist",
 ]
 
 _MAT_RE = re.compile(
@@ -167,3 +169,33 @@ def save_aruco_format(save_root: str, nCams: int, aruco_cam_list, cam_names: Seq
             "rc_ext": aruco_cam_list[i]["rc_ext"],
             "tc_ext": aruco_cam_list[i]["tc_ext"],
         })
+
+
+def apply_similarity_to_camlist(camList, scale, R, t):
+    """The extrinsics rewrite of scripts/register_world.py:90-103 for a registration X_new = scale R X + t obtained elsewhere
+    (ArUco markers, ``PySBA.align``): a new list of new dicts in which every camera sees the moved points where it saw the old
+    ones.  With x_cam = rc_ext X + tc_ext: rc_ext' = rc_ext R^T, tc_ext' = scale tc_ext - rc_ext' t (camera coordinates grow
+    by ``scale``, which a projection does not see).  Aruco-format dicts ('rc_ext', 'tc_ext') and readable-format dicts ('R' =
+    rc_ext^T, 't') are both accepted; all other entries are carried over; the input is not written."""
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError("scale must be positive and finite")
+    if np.abs(R.T @ R - np.eye(3)).max() > 1e-9 or np.linalg.det(R) < 0:
+        raise ValueError("R must be a rotation matrix")
+    out = []
+    for cam in camList:
+        new = dict(cam)
+        if "rc_ext" in cam:
+            rc = np.asarray(cam["rc_ext"], dtype=np.float64).reshape(3, 3) @ R.T
+            new["rc_ext"] = rc
+            new["tc_ext"] = scale * np.asarray(cam["tc_ext"], dtype=np.float64).reshape(3) - rc @ t
+        elif "R" in cam:
+            rc = np.asarray(cam["R"], dtype=np.float64).reshape(3, 3).T @ R.T
+            new["R"] = rc.T
+            new["t"] = scale * np.asarray(cam["t"], dtype=np.float64).reshape(3) - rc @ t
+        else:
+            raise KeyError("camera dict has neither 'rc_ext' / 'tc_ext' nor 'R' / 't'")
+        out.append(new)
+    return out

@@ -300,6 +300,20 @@ int sba_triangulate(sba_handle* h, const sba_tri_opts* opts, double* points_out,
   });
 }
 
+int sba_align(sba_handle* h, const sba_align_opts* opts, const double* target_points, const double* point_weights,
+              const double* target_centres, const double* centre_weights, sba_align_report* rep) {
+  if (!h) return SBA_ERR_INVALID;
+  sba_align_opts o{};
+  o.with_scale = 1; o.apply = 1;
+  if (opts) o = *opts;
+  return guarded(h, [&] { return h->eng->align(&o, target_points, point_weights, target_centres, centre_weights, rep); });
+}
+
+int sba_apply_similarity(sba_handle* h, double scale, const double* R, const double* t) {
+  if (!h) return SBA_ERR_INVALID;
+  return guarded(h, [&] { return h->eng->apply_similarity(scale, R, t); });
+}
+
 int sba_time_kernel(sba_handle* h, const char* name, int32_t reps, double* mean_us_out) {
   if (!h || !name || !mean_us_out) return SBA_ERR_INVALID;
   return guarded(h, [&] { return h->eng->time_kernel(name, reps, mean_us_out); });

@@ -13,6 +13,7 @@
 #include "sba_ipc.hpp"
 #include "sba_covariance.hpp"
 #include "sba_triangulate.hpp"
+#include "sba_align.hpp"
 #include "sba_layout.hpp"
 
 namespace SBA_NS {
@@ -2196,6 +2197,27 @@ struct Engine : EngineBase {
     TriIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, ptsT[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
                 blk_desc.p, nblk, has_fixed ? pt_fixed_mask.p : nullptr, identity_perm ? nullptr : perm.data()};
     return tri_run<T>(in, *o, points_out, status_out, n_views_out, rms_out, max_out, spread_out, inlier_out, rep, err);
+  }
+
+  // ------------------------------------------------------------------ similarity registration (sba_align.hpp)
+  int align_ready(const char* who) {
+    if (!uploaded) { err = "sba_upload has not been called"; return SBA_ERR_STATE; }
+    if (multi()) { err = std::string(who) + ": a handle of a multi-rank job is not supported"; return SBA_ERR_UNSUPPORTED; }
+    if (lm_active) { err = std::string(who) + ": the handle is between sba_lm_begin and sba_lm_finish"; return SBA_ERR_STATE; }
+    HIPCHK(hipSetDevice(device));
+    sync();
+    return SBA_OK;
+  }
+  int align(const sba_align_opts* o, const double* target_points, const double* point_weights, const double* target_centres,
+            const double* centre_weights, sba_align_report* rep) override {
+    if (int rc = align_ready("sba_align")) return rc;
+    AlignIn<T> in{stream, C, N, cams[cur].p, pts[cur].p, ptsT[cur].p, campre[cur].p};
+    return align_run<T>(in, *o, target_points, point_weights, target_centres, centre_weights, rep, err);
+  }
+  int apply_similarity(double scale, const double* R, const double* t) override {
+    if (int rc = align_ready("sba_apply_similarity")) return rc;
+    AlignIn<T> in{stream, C, N, cams[cur].p, pts[cur].p, ptsT[cur].p, campre[cur].p};
+    return align_apply_run<T>(in, scale, R, t, err);
   }
 
   // ------------------------------------------------------------------ small accessors of the C ABI

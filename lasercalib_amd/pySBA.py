@@ -354,6 +354,37 @@ class PySBA:
             self.points3D = np.where(tri.ok[:, None], tri.points, pts)
         return tri
 
+    def align(self, points=None, cameras=None, point_weights=None, camera_weights=None, with_scale=True, update=True):
+        """Extension: brings the solution into a frame of the caller's -- the similarity (scale, R, t) that carries
+        ``points3D`` onto ``points`` (N, 3) and the centres of ``cameraArray`` onto the centres of ``cameras`` (a (C, P) camera
+        array), weighted, estimated on the device (``include/sba_hip.h``, sba_align).  A free bundle adjustment leaves these
+        seven parameters open; ``sba.align(points=pts_initial)`` or ``sba.align(cameras=cams_initial)`` right after
+        ``bundleAdjust`` puts the answer back into the frame it started in.  Every camera and point moves together, so the
+        reprojection errors stay as they were.  The problem is built as ``triangulate`` builds it.  ``update=True`` rebinds
+        ``self.cameraArray`` / ``self.points3D`` to new arrays; the caller's arrays are never written.  Returns a
+        ``_native.Alignment``: ``scale``, ``R``, ``t``, ``rms_before``, ``rms_after``, ``max_after``, ``n_points_used``,
+        ``n_cams_used``, ``sv``, ``transform(X)``."""
+        cams = np.ascontiguousarray(self.cameraArray, dtype=np.float64)
+        pts = np.ascontiguousarray(self.points3D, dtype=np.float64)
+        centres = None
+        if cameras is not None:
+            tc = np.ascontiguousarray(cameras, dtype=np.float64)
+            if tc.ndim != 2 or tc.shape[0] != cams.shape[0] or tc.shape[1] < 6:
+                raise ValueError(f"cameras: expected a ({cams.shape[0]}, P) camera array, got {tc.shape}")
+            rot = _native.rotate_rows(np.tile(np.eye(3), (tc.shape[0], 1)), np.repeat(tc[:, 0:3], 3, axis=0),
+                                      dtype=_native.SBA_F64, device=_env_device()).reshape(-1, 3, 3)
+            centres = -np.einsum("cij,cj->ci", rot, tc[:, 3:6])        # rows of rot are the columns of R: rot = R^T
+        with _native.Problem(cams, pts, self.points2D, self.cameraIndices, self.point2DIndices,
+                             weights=self._weights_or_none(), dtype=_env_dtype(), device=_env_device()) as prob:
+            mask = self._fixed_mask(pts.shape[0])
+            if mask is not None:
+                prob.set_fixed_points(mask)
+            aln = prob.align(target_points=points, point_weights=point_weights, target_centres=centres,
+                             centre_weights=camera_weights, with_scale=with_scale, apply=update)
+            if update:
+                self.cameraArray, self.points3D = prob.get_params()
+        return aln
+
     def _package(self, mode, cams_opt, pts_opt, rep, log, fvec, verbose):
         C_, N_ = cams_opt.shape[0], pts_opt.shape[0]
         if mode == _native.MODE_POINTS_ONLY:
