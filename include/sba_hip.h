@@ -429,6 +429,68 @@ int sba_align(sba_handle* h, const sba_align_opts* opts /*NULL: {1, 1}*/,
               sba_align_report* rep);
 int sba_apply_similarity(sba_handle* h, double scale, const double* R /*9, row-major*/, const double* t /*3*/);
 
+/* ---------------------------------------------------------------- reprojection diagnostics (a solution's pixel errors, on the device)
+ * sba_reproj_stats: what a user looks at right after a solve (the reference prints a histogram of these errors,
+ * sba_print.py:17-21), from the observations, cameras and points the handle already holds: nothing but the results crosses the
+ * bus.  All arithmetic is float64, for SBA_F32 handles too (their pixels and weights are widened on load).  Camera rows have 11
+ * or 13 columns; cx, cy are the model's own columns.  C cameras, N points, M observations, B = hist_bins, nr = radial_bins,
+ * K = n_worst.
+ * Per observation with pixel (u, v), camera row c and point X, both at the handle's CURRENT parameters:
+ *   d = (du, dv) = project(X, c) - (u, v), unweighted, in pixels (the robust loss plays no part);  e = sqrt(du^2 + dv^2).
+ *   select picks the observations: 0 all, 1 weight > 0, 2 weight == 0 (the ones left out of the solve: the check of a
+ *   calibration that is independent of the fit).  n_selected counts them, n_unselected the rest.  A selected observation whose
+ *   d is not finite is counted in n_nonfinite and left out of every sum, histogram and list.
+ * cam_stats[c] = [n, mean du, mean dv, mean e, rms = sqrt(mean e^2), max e, q50, q95, q99] over the selected finite
+ *   observations of camera c; n = 0: n is 0 and the other eight values are NaN.
+ * cam_hist[c][k]: k = min(B - 1, floor(e * inv)), inv = 1 / hist_bin_px formed once on the host.  Bin B - 1 is the overflow
+ *   bin; n_overflow is its total over the cameras.
+ * Quantile q of a histogram h, n = sum h, m the largest e:  n = 0: NaN.  t = q n; k the first bin whose running total
+ *   cum_k = sum_{j <= k} h_j is at least t; k = B - 1: the value is m; otherwise (k + (t - cum_{k-1}) / h_k) hist_bin_px.
+ *   Computed on the host from the integer counts.  The global q50, q95, q99 use the sum of the camera histograms.
+ * cam_grid[c][iy][ix] = [n, mean du, mean dv, rms], the cell from the OBSERVED pixel: ix = clamp(floor(u (grid_x / width)), 0,
+ *   grid_x - 1), iy likewise from v, grid_y and height; the quotient is formed once on the host; negative and out-of-range
+ *   values clamp.  An empty cell has n = 0 and the other three values NaN.
+ * cam_radial[c][b] = [n, mean radial, mean tangential, rms]: dx = u - cx, dy = v - cy, r = sqrt(dx^2 + dy^2),
+ *   b = min(nr - 1, floor(r (nr / r_max))), rhat = (dx, dy) / r, radial = du rhat_x + dv rhat_y,
+ *   tangential = rhat_x dv - rhat_y du; r = 0: both components are 0.  An empty bin has n = 0 and the other three values NaN.
+ *   A radial mean that does not average to zero says that the camera model's distortion terms are not enough.
+ * pt_stats[p] = [n, rms, max] over the selected finite observations of point p; n = 0: the other two values are NaN.
+ * err_out[i] = e of observation i in the caller's order, for EVERY observation whatever select is; NaN where d is not finite.
+ * worst_idx / worst_err: the min(K, count) selected finite observations with the largest e, sorted by e descending, ties to the
+ *   smaller caller's index; indices in the caller's order; the rest is filled with -1 / NaN; rep->n_worst is the number filled.
+ * Global values (rep): each over all the selected finite observations; the sums behind them are formed from the per-camera
+ *   sums, added in camera order.
+ * Every output pointer may be NULL.  opts NULL: all defaults, grid and radial off, K = 0.
+ * Errors (a failed call leaves the outputs untouched): SBA_ERR_INVALID for an option out of its range or a missing width /
+ *   height; SBA_ERR_STATE before sba_upload and between sba_lm_begin and sba_lm_finish; SBA_ERR_UNSUPPORTED on a handle of a
+ *   multi-rank job (sba_comm_init / sba_ipc_attach).
+ * The handle is left exactly as found: parameters, LM state and work buffers (private buffers, freed on return).
+ * Determinism: no floating-point atomics anywhere (the histograms are integers).  Two calls on the same values return the same
+ *   bits in every output.  Every sum runs in the order of the canonical layout (point-major, camera-ascending), so a shuffled
+ *   observation list returns the same bits as the sorted one in cam_*, pt_stats and rep; err_out and worst_idx follow the
+ *   permutation. */
+typedef struct {
+  int32_t select;        /* 0 every observation; 1 weight > 0 (a handle without weights: all); 2 weight == 0 (without weights: none) */
+  int32_t hist_bins;     /* B; 0 -> 1024; else 2..4096                                        */
+  double  hist_bin_px;   /* 0 -> 1/16; else > 0 and finite                                    */
+  int32_t grid_x, grid_y;/* residual field: 0,0 = off; else >= 1 each and grid_x*grid_y <= 256 */
+  int32_t radial_bins;   /* nr; 0 = off; else 1..64                                           */
+  int32_t n_worst;       /* K; 0..4096                                                        */
+  double  width, height; /* image size in pixels; needed (> 0, finite) when the grid is on or r_max_px is 0 with radial bins on */
+  double  r_max_px;      /* 0 -> 0.5*sqrt(width^2+height^2)                                   */
+  int32_t reserved[6];
+} sba_reproj_opts;
+typedef struct {
+  int64_t n_selected, n_unselected, n_nonfinite, n_overflow;
+  int32_t n_worst, reserved;
+  double  mean_du, mean_dv, mean, rms, max, q50, q95, q99;
+  double  seconds_device, seconds_total;   /* HIP-event time of the kernels; wall time of the call */
+} sba_reproj_report;
+int sba_reproj_stats(sba_handle* h, const sba_reproj_opts* opts /*NULL: all defaults, grid and radial off, K = 0*/,
+                     double* cam_stats /*C*9*/, int64_t* cam_hist /*C*B*/, double* cam_grid /*C*gy*gx*4*/,
+                     double* cam_radial /*C*nr*4*/, double* pt_stats /*N*3*/, double* err_out /*M, caller's order*/,
+                     int64_t* worst_idx /*K*/, double* worst_err /*K*/, sba_reproj_report* rep);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = (
     "sba_lm_exchange_size", "sba_lm_begin", "sba_lm_linearize", "sba_lm_form_reduced",
     "sba_lm_solve_trial", "sba_lm_decide", "sba_lm_decide_async", "sba_lm_poll", "sba_lm_run", "sba_lm_finish", "sba_lm_get_log", "sba_time_kernel", "sba_get_kernel_profile",
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
-    "sba_triangulate", "sba_align", "sba_apply_similarity",
+    "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
 )
 
 
@@ -97,6 +97,23 @@ class AlignReport(C.Structure):
     _fields_ = [("scale", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_before", C.c_double),
                 ("rms_after", C.c_double), ("max_after", C.c_double), ("n_points_used", C.c_int64), ("n_cams_used", C.c_int32),
                 ("reserved", C.c_int32), ("sv", C.c_double * 3), ("seconds_device", C.c_double), ("seconds_total", C.c_double)]
+
+
+class ReprojOpts(C.Structure):
+    _fields_ = [("select", C.c_int32), ("hist_bins", C.c_int32), ("hist_bin_px", C.c_double), ("grid_x", C.c_int32),
+                ("grid_y", C.c_int32), ("radial_bins", C.c_int32), ("n_worst", C.c_int32), ("width", C.c_double),
+                ("height", C.c_double), ("r_max_px", C.c_double), ("reserved", C.c_int32 * 6)]
+
+
+class ReprojReport(C.Structure):
+    _fields_ = [("n_selected", C.c_int64), ("n_unselected", C.c_int64), ("n_nonfinite", C.c_int64), ("n_overflow", C.c_int64),
+                ("n_worst", C.c_int32), ("reserved", C.c_int32), ("mean_du", C.c_double), ("mean_dv", C.c_double),
+                ("mean", C.c_double), ("rms", C.c_double), ("max", C.c_double), ("q50", C.c_double), ("q95", C.c_double),
+                ("q99", C.c_double), ("seconds_device", C.c_double), ("seconds_total", C.c_double)]
+
+
+REPROJ_SELECT = {"all": 0, "used": 1, "held_out": 2}                      # sba_reproj_opts.select
+REPROJ_DEFAULT_BINS, REPROJ_DEFAULT_BIN_PX = 1024, 1.0 / 16
 
 
 class UploadOpts(C.Structure):
@@ -169,6 +186,37 @@ class Alignment:
     def transform(self, X):
         """scale R X + t for an (..., 3) array of points."""
         return self.scale * (np.asarray(X, dtype=np.float64) @ self.R.T) + self.t
+
+
+class ReprojStats:
+    """Result of Problem.reproj_stats (sba_reproj_stats, include/sba_hip.h).  ``cam_stats`` (C, 9): n, mean du, mean dv, mean,
+    rms, max, q50, q95, q99 per camera; ``cam_hist`` (C, B) int64 with the overflow bin last; ``cam_grid`` (C, gy, gx, 4): n,
+    mean du, mean dv, rms per image cell, or None; ``cam_radial`` (C, nr, 4): n, mean radial, mean tangential, rms per radial
+    bin, or None; ``pt_stats`` (N, 3): n, rms, max per point, or None; ``errors`` (M,) in the caller's order, or None;
+    ``worst_idx`` / ``worst_err`` (n_worst,): the worst observations, largest first.  The report's fields (``n_selected``,
+    ``n_unselected``, ``n_nonfinite``, ``n_overflow``, ``mean_du``, ``mean_dv``, ``mean``, ``rms``, ``max``, ``q50``, ``q95``,
+    ``q99``, the seconds) are attributes; ``bin_edges`` (B + 1,) are the histogram's edges in pixels (the last bin is open:
+    its upper edge is inf), ``total_hist`` (B,) the sum over the cameras, ``hist_bin_px``, ``r_max_px`` the resolved options."""
+
+    def __init__(self, cam_stats, cam_hist, cam_grid, cam_radial, pt_stats, errors, worst_idx, worst_err, rep, hist_bin_px, r_max_px):
+        self.cam_stats, self.cam_hist, self.cam_grid, self.cam_radial = cam_stats, cam_hist, cam_grid, cam_radial
+        self.pt_stats, self.errors = pt_stats, errors
+        self.worst_idx, self.worst_err = worst_idx[: rep.n_worst], worst_err[: rep.n_worst]
+        for name, _t in ReprojReport._fields_:
+            if name != "reserved":
+                setattr(self, name, getattr(rep, name))
+        self.hist_bin_px, self.r_max_px = hist_bin_px, r_max_px
+        B = cam_hist.shape[1]
+        self.bin_edges = np.append(np.arange(B) * hist_bin_px, np.inf)
+        self.total_hist = cam_hist.sum(axis=0)
+
+    @property
+    def radial_edges(self):
+        """(nr + 1,) edges of the radial bins in pixels (the last bin also takes every larger radius), or None."""
+        if self.cam_radial is None:
+            return None
+        nr = self.cam_radial.shape[1]
+        return np.arange(nr + 1) * (self.r_max_px / nr)
 
 
 _lib = None
@@ -257,6 +305,7 @@ def load():
                                       C.POINTER(C.c_uint8), C.POINTER(TriReport)]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
         "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
+        "sba_reproj_stats": (C.c_int, [H, C.POINTER(ReprojOpts), dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(ReprojReport)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -541,6 +590,41 @@ class Problem:
         if R.shape != (3, 3) or t.shape != (3,):
             raise ValueError("apply_similarity: R must be (3, 3) and t (3,)")
         _check(self._lib.sba_apply_similarity(self._h, float(scale), _dptr(R), _dptr(t)), self._h)
+
+    # -- reprojection diagnostics at the current parameters (sba_reproj_stats, include/sba_hip.h)
+    def reproj_stats(self, select="all", hist_bins=None, hist_bin_px=None, grid=None, image_size=None, radial_bins=0,
+                     r_max_px=None, n_worst=0, points=True, errors=False):
+        """Pixel-error statistics of the handle's current solution, computed on the device from the data it already holds.
+        select: "all", "used" (weight > 0) or "held_out" (weight == 0); grid: (gx, gy) cells of a residual field over an image
+        of image_size = (width, height); radial_bins: bins of the radial / tangential profile out to r_max_px (default: half
+        the image diagonal); n_worst: length of the worst-observation list; points: the per-point table; errors: the
+        per-observation errors in the caller's order.  Returns a ReprojStats."""
+        if select not in REPROJ_SELECT:
+            raise ValueError("select must be 'all', 'used' or 'held_out'")
+        B = REPROJ_DEFAULT_BINS if not hist_bins else int(hist_bins)
+        bin_px = REPROJ_DEFAULT_BIN_PX if not hist_bin_px else float(hist_bin_px)
+        gx, gy = (0, 0) if grid is None else (int(grid[0]), int(grid[1]))
+        width, height = (0.0, 0.0) if image_size is None else (float(image_size[0]), float(image_size[1]))
+        nr, K = int(radial_bins), int(n_worst)
+        opts = ReprojOpts(REPROJ_SELECT[select], int(hist_bins or 0), float(hist_bin_px or 0.0), gx, gy, nr, K, width, height,
+                          float(r_max_px or 0.0), (C.c_int32 * 6)())
+        alloc = lambda ok, shape, dt=np.float64: np.empty(shape, dt) if ok else None      # noqa: E731
+        ok_dims = 2 <= B <= 4096 and 0 <= gx * gy <= 256 and gx >= 0 and gy >= 0 and 0 <= nr <= 64 and 0 <= K <= 4096
+        if not ok_dims:        # the library owns the error text; give it nothing to write into
+            _check(self._lib.sba_reproj_stats(self._h, C.byref(opts), None, None, None, None, None, None, None, None, None), self._h)
+            raise ValueError("reproj_stats: an option is out of its range")
+        cam_stats, cam_hist = np.empty((self.C, 9)), np.empty((self.C, B), np.int64)
+        cam_grid = alloc(gx * gy > 0, (self.C, gy, gx, 4))
+        cam_radial = alloc(nr > 0, (self.C, nr, 4))
+        pt_stats = alloc(points, (self.N, 3))
+        err = alloc(errors, (self.M,))
+        worst_idx, worst_err = np.empty(K, np.int64), np.empty(K)
+        rep = ReprojReport()
+        ip = lambda a: None if a is None else _iptr(a)      # noqa: E731
+        _check(self._lib.sba_reproj_stats(self._h, C.byref(opts), _dptr(cam_stats), ip(cam_hist), _dptr(cam_grid), _dptr(cam_radial),
+                                          _dptr(pt_stats), _dptr(err), ip(worst_idx), _dptr(worst_err), C.byref(rep)), self._h)
+        r_max = float(r_max_px) if r_max_px else 0.5 * float(np.hypot(width, height))
+        return ReprojStats(cam_stats, cam_hist, cam_grid, cam_radial, pt_stats, err, worst_idx, worst_err, rep, bin_px, r_max)
 
     # -- lifetime
     def close(self):

@@ -314,6 +314,17 @@ int sba_apply_similarity(sba_handle* h, double scale, const double* R, const dou
   return guarded(h, [&] { return h->eng->apply_similarity(scale, R, t); });
 }
 
+int sba_reproj_stats(sba_handle* h, const sba_reproj_opts* opts, double* cam_stats, int64_t* cam_hist, double* cam_grid,
+                     double* cam_radial, double* pt_stats, double* err_out, int64_t* worst_idx, double* worst_err,
+                     sba_reproj_report* rep) {
+  if (!h) return SBA_ERR_INVALID;
+  sba_reproj_opts o{};
+  if (opts) o = *opts;
+  return guarded(h, [&] {
+    return h->eng->reproj_stats(&o, cam_stats, cam_hist, cam_grid, cam_radial, pt_stats, err_out, worst_idx, worst_err, rep);
+  });
+}
+
 int sba_time_kernel(sba_handle* h, const char* name, int32_t reps, double* mean_us_out) {
   if (!h || !name || !mean_us_out) return SBA_ERR_INVALID;
   return guarded(h, [&] { return h->eng->time_kernel(name, reps, mean_us_out); });

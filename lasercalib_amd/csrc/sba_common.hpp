@@ -294,6 +294,8 @@ struct EngineBase {
   virtual int align(const sba_align_opts* o, const double* target_points, const double* point_weights, const double* target_centres,
                     const double* centre_weights, sba_align_report* rep) = 0;
   virtual int apply_similarity(double scale, const double* R, const double* t) = 0;
+  virtual int reproj_stats(const sba_reproj_opts* o, double* cam_stats, int64_t* cam_hist, double* cam_grid, double* cam_radial,
+                           double* pt_stats, double* err_out, int64_t* worst_idx, double* worst_err, sba_reproj_report* rep) = 0;
 };
 
 }  // namespace sba_host

@@ -14,6 +14,7 @@
 #include "sba_covariance.hpp"
 #include "sba_triangulate.hpp"
 #include "sba_align.hpp"
+#include "sba_reproj.hpp"
 #include "sba_layout.hpp"
 
 namespace SBA_NS {
@@ -2218,6 +2219,16 @@ struct Engine : EngineBase {
     if (int rc = align_ready("sba_apply_similarity")) return rc;
     AlignIn<T> in{stream, C, N, cams[cur].p, pts[cur].p, ptsT[cur].p, campre[cur].p};
     return align_apply_run<T>(in, scale, R, t, err);
+  }
+
+  // ------------------------------------------------------------------ reprojection diagnostics (sba_reproj.hpp)
+  int reproj_stats(const sba_reproj_opts* o, double* cam_stats, int64_t* cam_hist, double* cam_grid, double* cam_radial,
+                   double* pt_stats, double* err_out, int64_t* worst_idx, double* worst_err, sba_reproj_report* rep) override {
+    if (int rc = align_ready("sba_reproj_stats")) return rc;
+    RpIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, uv_cm.p, uv_pm.p, has_w ? w_cm.p : nullptr, has_w ? w_pm.p : nullptr,
+               pi_cm.p, ci_pm.p, pi_pm.p, pt_start.p, chunk_cam.p, chunk_begin.p, chunk_end.p, cam_chunk_start.p, nchunk,
+               identity_perm ? nullptr : perm.data()};
+    return rp_run<T>(in, *o, cam_stats, cam_hist, cam_grid, cam_radial, pt_stats, err_out, worst_idx, worst_err, rep, err);
   }
 
   // ------------------------------------------------------------------ small accessors of the C ABI

@@ -385,6 +385,22 @@ class PySBA:
                 self.cameraArray, self.points3D = prob.get_params()
         return aln
 
+    def reprojection_stats(self, select="all", hist_bins=None, hist_bin_px=None, grid=None, image_size=None, radial_bins=0,
+                           r_max_px=None, n_worst=0, points=True, errors=False):
+        """Extension: the reprojection diagnostics of ``cameraArray`` / ``points3D`` as they stand, on the device
+        (``include/sba_hip.h``, sba_reproj_stats): per camera the error statistics and an integer histogram, optionally a
+        residual field over the image (``grid``, ``image_size``), a radial / tangential profile (``radial_bins``: a radial mean
+        that does not average to zero says the camera model is not enough), per point [n, rms, max], the per-observation errors
+        and the ``n_worst`` worst observations.  ``select``: "all", "used" (weight > 0) or "held_out" (weight == 0: the
+        observations the solve did not see).  The problem is built as ``covariance`` builds it.  Returns a
+        ``_native.ReprojStats``."""
+        cams = np.ascontiguousarray(self.cameraArray, dtype=np.float64)
+        pts = np.ascontiguousarray(self.points3D, dtype=np.float64)
+        with _native.Problem(cams, pts, self.points2D, self.cameraIndices, self.point2DIndices,
+                             weights=self._weights_or_none(), dtype=_env_dtype(), device=_env_device()) as prob:
+            return prob.reproj_stats(select=select, hist_bins=hist_bins, hist_bin_px=hist_bin_px, grid=grid, image_size=image_size,
+                                     radial_bins=radial_bins, r_max_px=r_max_px, n_worst=n_worst, points=points, errors=errors)
+
     def _package(self, mode, cams_opt, pts_opt, rep, log, fvec, verbose):
         C_, N_ = cams_opt.shape[0], pts_opt.shape[0]
         if mode == _native.MODE_POINTS_ONLY:

@@ -13,7 +13,8 @@ from __future__ import annotations
 import numpy as np
 from scipy.spatial.transform import Rotation as R
 
-__all__ = ["reprojection_errors", "reprojection_summary", "camera_table", "camera_extrinsics"]
+__all__ = ["reprojection_errors", "reprojection_summary", "camera_table", "camera_extrinsics",
+           "device_reprojection_summary", "per_camera_table", "radial_profile_table"]
 
 
 def reprojection_errors(sba) -> np.ndarray:
@@ -27,6 +28,44 @@ def reprojection_summary(sba) -> dict:
     e = reprojection_errors(sba)
     return {"n_obs": int(e.size), "mean": float(e.mean()), "rms": float(np.sqrt(np.mean(e ** 2))),
             "median": float(np.median(e)), "p99": float(np.percentile(e, 99)), "max": float(e.max())}
+
+
+def device_reprojection_summary(sba) -> dict:
+    """The keys of :func:`reprojection_summary` from ``PySBA.reprojection_stats`` (sba_reproj_stats): nothing but the result
+    crosses the bus.  n_obs, mean, rms and max are exact sums over the observations; median and p99 are read off the integer
+    histogram of the errors, by linear interpolation inside a bin of 1/16 px (1024 bins: errors of 64 px and more share the last
+    bin, and a quantile that falls there is reported as the largest error)."""
+    st = sba.reprojection_stats(points=False)
+    return {"n_obs": int(st.n_selected - st.n_nonfinite), "mean": float(st.mean), "rms": float(st.rms),
+            "median": float(st.q50), "p99": float(st.q99), "max": float(st.max)}
+
+
+def per_camera_table(stats) -> str:
+    """One row per camera of a ``ReprojStats``: n, mean du, mean dv, mean, rms, max, q50, q95, q99 (pixels), as fixed-width text."""
+    cols = ("n", "mean du", "mean dv", "mean", "rms", "max", "q50", "q95", "q99")
+    head = " cam " + " ".join(f"{c:>10s}" for c in cols)
+    rows = [f"{i:4d} {int(row[0]):10d} " + " ".join(f"{v:10.4g}" for v in row[1:]) for i, row in enumerate(stats.cam_stats)]
+    return "\n".join([head] + rows)
+
+
+def radial_profile_table(stats) -> str:
+    """The radial / tangential profile of a ``ReprojStats`` (``radial_bins`` > 0), pooled over the cameras: per radial bin the
+    count, the mean radial and tangential residual and the rms (pixels), then one line per camera with its mean radial
+    residual per bin.  Pooled means weight every camera's bin by its count."""
+    if stats.cam_radial is None:
+        raise ValueError("the radial profile was not computed (radial_bins=0)")
+    prof, edges = stats.cam_radial, stats.radial_edges
+    n = prof[:, :, 0]
+    tot = n.sum(axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pooled = [np.where(tot > 0, np.nansum(n * prof[:, :, k], axis=0) / tot, np.nan) for k in (1, 2)]
+        rms = np.where(tot > 0, np.sqrt(np.nansum(n * prof[:, :, 3] ** 2, axis=0) / tot), np.nan)
+    head = f"{'r from':>9s} {'r to':>9s} {'n':>10s} {'radial':>10s} {'tangential':>10s} {'rms':>10s}"
+    rows = [f"{edges[b]:9.1f} {edges[b + 1]:9.1f} {int(tot[b]):10d} {pooled[0][b]:10.4g} {pooled[1][b]:10.4g} {rms[b]:10.4g}"
+            for b in range(prof.shape[1])]
+    cam_head = " cam " + " ".join(f"{edges[b]:9.0f}+" for b in range(prof.shape[1]))
+    cam_rows = [f"{c:4d} " + " ".join(f"{v:10.4g}" for v in prof[c, :, 1]) for c in range(prof.shape[0])]
+    return "\n".join([head] + rows + ["mean radial residual per camera and bin", cam_head] + cam_rows)
 
 
 _COLS = ("rx", "ry", "rz", "tx", "ty", "tz", "f", "k1", "k2", "cx", "cy")
