@@ -133,6 +133,25 @@ int sba_project(int device, int dtype, int64_t n, const double* points /*n*3*/,
 int sba_project_model(int device, int dtype, int cam_model, int64_t n, const double* points /*n*3*/,
                       const double* cam_rows /*n*(11|13)*/, double* uv_out /*n*2*/);
 
+/* sba_unproject_rows: the inverse of sba_project_model on gathered rows -- a pixel and its camera row become a ray, and with a
+ * plane n . X = d the point where the ray meets it (cv2.undistortPoints and rigid_body.py:205-243 of the reference).  All
+ * arithmetic is float64.  Per row with pixel (u, v):
+ *   xd = (u - cx) / f, yd = (v - cy) / f;  (x, y) by the Newton inversion of steps 1-2 of sba_triangulate (20 steps at most,
+ *   the 1e-15 stopping rule, the positive-determinant test);  xn = (x, y), origin = -R^T t, dir = normalise(R^T (x, y, 1)).
+ *   With a plane (n, d): nh = n / |n|, dh = d / |n|, s = nh . dir, tau = (dh - nh . origin) / s, X = origin + tau dir,
+ *   depth = (R X + t)_z.
+ * Status, first match wins: UNUSABLE (the inversion failed or a value is not finite: every output of the row is NaN), PARALLEL
+ * (|s| <= 1e-6: X and depth are NaN), BEHIND (depth <= 0: X is still reported), OK.
+ * planes holds n_planes rows of (n_x, n_y, n_z, d): n_planes == 1 one plane for every row, n_planes == n one per row,
+ * n_planes == 0 (planes may be NULL) rays only: then only UNUSABLE and OK occur, and points_out and depth_out must be NULL.
+ * Every output pointer may be NULL.  SBA_ERR_INVALID: a plane that is not finite or whose normal is zero (checked on the host
+ * before any launch), an unknown camera model, a negative n, an n_planes that is none of 0, 1, n.  Large n runs in chunks. */
+typedef enum { SBA_UNP_ROW_OK = 0, SBA_UNP_ROW_UNUSABLE = 1, SBA_UNP_ROW_PARALLEL = 2, SBA_UNP_ROW_BEHIND = 3 } sba_unp_row_status;
+int sba_unproject_rows(int device, int cam_model, int64_t n, const double* uv /*n*2*/, const double* cam_rows /*n*(11|13)*/,
+                       const double* planes /*n_planes*4 or NULL*/, int64_t n_planes /*0, 1 or n*/,
+                       double* xn_out /*n*2*/, double* origin_out /*n*3*/, double* dir_out /*n*3*/,
+                       double* points_out /*n*3*/, double* depth_out /*n*/, int32_t* status_out /*n*/);
+
 /* ---------------------------------------------------------------- problem handle
  * sba_create/sba_upload <-> PySBA.__init__ state (pySBA.py:28-59): observation list + initial x.
  * weights may be NULL (reference default = ones, pySBA.py:56-58).
@@ -378,6 +397,55 @@ int sba_triangulate(sba_handle* h, const sba_tri_opts* opts /*NULL: {2, 1, 0.0, 
                     double* points_out /*N*3*/, int32_t* status_out /*N*/, int32_t* n_views_out /*N*/,
                     double* rms_px_out /*N*/, double* max_px_out /*N*/, double* spread_out /*N*/,
                     uint8_t* inlier_out /*M, caller's order*/, sba_tri_report* rep);
+
+/* ---------------------------------------------------------------- un-projection (3-D points on known planes from the pixels)
+ * sba_unproject: for every point the point of ITS plane n . X = d that is closest to the rays of its observations, at the
+ * handle's CURRENT camera rows -- the start the laserCalib workflow uses (every laser dot lies on a known plane, z_gt of
+ * config.json; get_points3d.py:88-99 un-projects one "3-D init camera"), from all views or from one camera.  Nothing but the
+ * planes and the results crosses the bus.  All arithmetic is float64, for SBA_F32 handles too.
+ * planes holds n_planes rows of (n_x, n_y, n_z, d): n_planes == 1 one plane for every point, n_planes == N one per point.
+ *   1. usable observations: exactly steps 1-3 of sba_triangulate (weight not 0 and finite, the inversion converged, the ray is
+ *      finite); with use_ref_cam only the observations of camera ref_cam are examined at all.  omega = w^2.
+ *   2. per point over its usable observations, in the layout's order (point-major, camera ascending):
+ *      A = sum omega (I - d d^T), b = sum omega (I - d d^T) c.
+ *   3. plane basis: nh = n / |n|, dh = d / |n|, X0 = dh nh; k the index of the smallest |nh_k| (ties: the smaller index);
+ *      e1 = normalise(e_k - nh_k nh), e2 = nh x e1, B = [e1 e2].
+ *   4. G = B^T A B, g = B^T (b - A X0), y = G^-1 g by a 2 x 2 Cholesky factorisation with the pivot test of step 4 of
+ *      sba_triangulate (G00 > 0 and G11 - G10^2 / G00 > 1e-12 G11), X = X0 + B y.  For a single ray this is the ray's
+ *      intersection with the plane (G has the eigenvalues 1 and (nh . d)^2).
+ *   5. per used observation the pixel error at X through the forward model (unweighted, pixels) and the depth (R X + t)_z.
+ * Status, first match wins: ANCHORED (held by sba_set_fixed_points: coordinates returned as held, observations not examined),
+ * NO_VIEW (the usable observations come from fewer than min_views distinct cameras), DEGENERATE (pivot test failed: the rays
+ * run along the plane), BEHIND (some used depth <= 0; X is still reported), OK.  X is NaN for NO_VIEW and DEGENERATE.
+ * n_views counts the observations in the estimate, rms_px = sqrt(mean e^2) and max_px are over them: they say how consistent
+ * the cameras are with the plane.  n_views is 0 and both errors are NaN for every point without estimate.
+ * used_out[i], in the CALLER's order: 1 when observation i is in the estimate of an OK or BEHIND point or belongs to an
+ * anchored point.
+ * opts NULL or all zero: all cameras, min_views 1, no write-back; min_views <= 0 is read as 1.
+ * write_back = 0: the handle is left exactly as found (private buffers freed on return).  write_back = 1: the handle's current
+ * points are replaced by X where the status is OK and the handle is in the state sba_set_params leaves it in.
+ * rep: the histogram of the status, n_obs_unusable (examined observations that failed step 1; those of anchored points are not
+ * examined), n_obs_used (the ones in used_out), the HIP-event seconds of the kernels and the wall time of the call.
+ * Errors (a failed call leaves the outputs untouched): SBA_ERR_INVALID for a plane that is not finite or whose normal is zero,
+ * an n_planes that is neither 1 nor N, a ref_cam out of range; SBA_ERR_STATE before sba_upload and between sba_lm_begin and
+ * sba_lm_finish; SBA_ERR_UNSUPPORTED on a handle of a multi-rank job.
+ * Determinism: no floating-point atomics; the sums run in the order of the canonical layout, so two calls on the same values
+ * return the same bits and a shuffled observation list returns the bits of the sorted one. */
+typedef enum { SBA_UNP_OK = 0, SBA_UNP_ANCHORED = 1, SBA_UNP_NO_VIEW = 2, SBA_UNP_DEGENERATE = 3, SBA_UNP_BEHIND = 4 } sba_unp_status;
+typedef struct {
+  int32_t use_ref_cam;     /* != 0: only the observations of camera ref_cam (the reference's cam_name_for_3d_init) */
+  int32_t ref_cam;
+  int32_t min_views;       /* distinct cameras a point needs; <= 0 is read as 1                          */
+  int32_t write_back;      /* 1: X of the OK points replaces the handle's current points                 */
+  int32_t reserved[4];
+} sba_unp_opts;
+typedef struct {
+  int64_t n_ok, n_anchored, n_no_view, n_degenerate, n_behind, n_obs_unusable, n_obs_used;
+  double  seconds_device, seconds_total;
+} sba_unp_report;
+int sba_unproject(sba_handle* h, const sba_unp_opts* opts /*NULL: all zero*/, const double* planes /*n_planes*4*/, int64_t n_planes /*1 or N*/,
+                  double* points_out /*N*3*/, int32_t* status_out /*N*/, int32_t* n_views_out /*N*/, double* rms_px_out /*N*/,
+                  double* max_px_out /*N*/, uint8_t* used_out /*M, caller's order*/, sba_unp_report* rep);
 
 /* ---------------------------------------------------------------- similarity registration (a solution into a frame of the caller)
  * A free bundle adjustment leaves the similarity gauge open: two solves of the same data differ by a scale, a rotation and a

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "sba_lm_solve_trial", "sba_lm_decide", "sba_lm_decide_async", "sba_lm_poll", "sba_lm_run", "sba_lm_finish", "sba_lm_get_log", "sba_time_kernel", "sba_get_kernel_profile",
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
+    "sba_unproject_rows", "sba_unproject",
 )
 
 
@@ -87,6 +88,21 @@ class TriReport(C.Structure):
 
 
 TRI_OK, TRI_ANCHORED, TRI_TOO_FEW, TRI_DEGENERATE, TRI_BEHIND = 0, 1, 2, 3, 4       # sba_tri_status
+
+
+class UnpOpts(C.Structure):
+    _fields_ = [("use_ref_cam", C.c_int32), ("ref_cam", C.c_int32), ("min_views", C.c_int32), ("write_back", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class UnpReport(C.Structure):
+    _fields_ = [("n_ok", C.c_int64), ("n_anchored", C.c_int64), ("n_no_view", C.c_int64), ("n_degenerate", C.c_int64),
+                ("n_behind", C.c_int64), ("n_obs_unusable", C.c_int64), ("n_obs_used", C.c_int64),
+                ("seconds_device", C.c_double), ("seconds_total", C.c_double)]
+
+
+UNP_OK, UNP_ANCHORED, UNP_NO_VIEW, UNP_DEGENERATE, UNP_BEHIND = 0, 1, 2, 3, 4       # sba_unp_status
+UNP_ROW_OK, UNP_ROW_UNUSABLE, UNP_ROW_PARALLEL, UNP_ROW_BEHIND = 0, 1, 2, 3        # sba_unp_row_status
 
 
 class AlignOpts(C.Structure):
@@ -168,6 +184,22 @@ class Triangulation:
     @property
     def ok(self):
         return self.status == TRI_OK
+
+
+class Unprojection:
+    """Result of Problem.unproject (sba_unproject, include/sba_hip.h): ``points`` (N, 3), ``status`` (N,) of UNP_*, ``n_views``,
+    ``rms_px``, ``max_px`` (N,), ``used`` (M,) bool in the caller's observation order, the report's counts and seconds as
+    attributes, and ``ok``: the mask of the points with status UNP_OK."""
+
+    def __init__(self, points, status, n_views, rms_px, max_px, used, rep):
+        self.points, self.status, self.n_views = points, status, n_views
+        self.rms_px, self.max_px, self.used = rms_px, max_px, used
+        for name, _t in UnpReport._fields_:
+            setattr(self, name, getattr(rep, name))
+
+    @property
+    def ok(self):
+        return self.status == UNP_OK
 
 
 class Alignment:
@@ -303,6 +335,9 @@ def load():
         "sba_covariance": (C.c_int, [H, C.POINTER(CovOpts), dp, dp, dp, C.POINTER(CovReport)]),
         "sba_triangulate": (C.c_int, [H, C.POINTER(TriOpts), dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, dp,
                                       C.POINTER(C.c_uint8), C.POINTER(TriReport)]),
+        "sba_unproject_rows": (C.c_int, [C.c_int, C.c_int, C.c_int64, dp, dp, dp, C.c_int64, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]),
+        "sba_unproject": (C.c_int, [H, C.POINTER(UnpOpts), dp, C.c_int64, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp,
+                                    C.POINTER(C.c_uint8), C.POINTER(UnpReport)]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
         "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
         "sba_reproj_stats": (C.c_int, [H, C.POINTER(ReprojOpts), dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(ReprojReport)]),
@@ -406,6 +441,47 @@ def rotate_rows(points, rot_vecs, dtype=SBA_F64, device=0):
         raise ValueError("rotate expects (M,3) points and (M,3) rotation vectors")
     out = np.empty_like(p)
     _check(lib.sba_rotate(device, dtype_code(dtype), p.shape[0], _dptr(p), _dptr(r), _dptr(out)))
+    return out
+
+
+def _planes(planes, rows, what):
+    """(1, 4) or (rows, 4) float64 plane rows (n_x, n_y, n_z, d) from a (4,), (1, 4) or (rows, 4) array."""
+    pl = _f64(planes)
+    if pl.ndim == 1:
+        pl = pl.reshape(1, -1)
+    if pl.ndim != 2 or pl.shape[1] != 4:
+        raise ValueError(f"{what}: planes must be (4,) or (n, 4) rows of (n_x, n_y, n_z, d), got {pl.shape}")
+    return np.ascontiguousarray(pl)
+
+
+def z_planes(z, n_points):
+    """(1, 4) or (n_points, 4) plane rows (0, 0, 1, z) from a scalar or an (n_points,) array of heights."""
+    z = np.asarray(z, dtype=np.float64)
+    if z.ndim > 1 or (z.ndim == 1 and z.shape[0] != n_points):
+        raise ValueError(f"z must be a scalar or have one entry per 3-D point ({n_points}), got shape {z.shape}")
+    pl = np.zeros((z.size, 4))
+    pl[:, 2] = 1.0
+    pl[:, 3] = z.reshape(-1)
+    return pl
+
+
+def unproject_rows(uv, cam_rows, planes=None, device=0):
+    """The inverse of ``project_rows`` (sba_unproject_rows, include/sba_hip.h): pixels (M, 2) and gathered camera rows (M, 11) or
+    (M, 13) become rays, and with ``planes`` -- (4,) for one plane n . X = d, or (M, 4) -- the points where the rays meet them.
+    Returns a dict: ``xn`` (M, 2) undistorted normalised coordinates, ``origin``, ``dir`` (M, 3), ``status`` (M,) of UNP_ROW_*,
+    and with planes ``points`` (M, 3) and ``depth`` (M,)."""
+    lib = load()
+    p, c = _f64(uv), _f64(cam_rows)
+    if p.ndim != 2 or p.shape[1] != 2 or c.ndim != 2 or c.shape[1] not in (11, 13) or p.shape[0] != c.shape[0]:
+        raise ValueError("unproject expects (M,2) pixels and (M,11) camera rows ((M,13) with tangential distortion)")
+    n = p.shape[0]
+    pl = None if planes is None else _planes(planes, n, "unproject_rows")
+    out = dict(xn=np.empty((n, 2)), origin=np.empty((n, 3)), dir=np.empty((n, 3)), status=np.empty(n, np.int32))
+    if pl is not None:
+        out.update(points=np.empty((n, 3)), depth=np.empty(n))
+    _check(lib.sba_unproject_rows(device, cam_model_of(c.shape[1]), n, _dptr(p), _dptr(c), _dptr(pl), 0 if pl is None else pl.shape[0],
+                                  _dptr(out["xn"]), _dptr(out["origin"]), _dptr(out["dir"]), _dptr(out.get("points")),
+                                  _dptr(out.get("depth")), out["status"].ctypes.data_as(C.POINTER(C.c_int32))))
     return out
 
 
@@ -560,6 +636,24 @@ class Problem:
         _check(self._lib.sba_triangulate(self._h, C.byref(opts), _dptr(pts), i32(status), i32(n_views), _dptr(rms), _dptr(mx),
                                          _dptr(spread), inl.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rep)), self._h)
         return Triangulation(pts, status, n_views, rms, mx, spread, inl != 0, rep)
+
+    # -- 3-D points on known planes from the current cameras and the pixels (sba_unproject, include/sba_hip.h)
+    def unproject(self, planes, ref_cam=None, min_views=1, write_back=False):
+        """Per point the point of its plane closest to the rays of its observations at the handle's current cameras.  planes:
+        (4,) for one plane n . X = d, or (N, 4); ref_cam: only the observations of that camera (the reference's 3-D init
+        camera); write_back: the estimates of the OK points become the handle's current points.  Returns an Unprojection."""
+        pl = _planes(planes, self.N, "unproject")
+        pts = np.empty((self.N, 3))
+        status, n_views = np.empty(self.N, np.int32), np.empty(self.N, np.int32)
+        rms, mx = np.empty(self.N), np.empty(self.N)
+        used = np.empty(self.M, np.uint8)
+        rep = UnpReport()
+        opts = UnpOpts(0 if ref_cam is None else 1, 0 if ref_cam is None else int(ref_cam), int(min_views), 1 if write_back else 0,
+                       (C.c_int32 * 4)())
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))      # noqa: E731
+        _check(self._lib.sba_unproject(self._h, C.byref(opts), _dptr(pl), pl.shape[0], _dptr(pts), i32(status), i32(n_views),
+                                       _dptr(rms), _dptr(mx), used.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rep)), self._h)
+        return Unprojection(pts, status, n_views, rms, mx, used != 0, rep)
 
     # -- similarity registration of the handle's current solution (sba_align, include/sba_hip.h)
     def _targets(self, name, target, weights, rows):

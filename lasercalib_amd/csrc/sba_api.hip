@@ -10,6 +10,10 @@ sba_host::EngineBase* sba_make_engine_ncp11(int dtype);
 sba_host::EngineBase* sba_make_engine_ncp13(int dtype);
 int sba_rows_call_ncp11(int dtype, bool project, int device, int64_t n, const double* pts, const double* other, double* out);
 int sba_rows_call_ncp13(int dtype, bool project, int device, int64_t n, const double* pts, const double* other, double* out);
+int sba_unproject_rows_ncp11(int device, int64_t n, const double* uv, const double* cam_rows, const double* planes, int64_t n_planes,
+                             double* xn_out, double* origin_out, double* dir_out, double* points_out, double* depth_out, int32_t* status_out);
+int sba_unproject_rows_ncp13(int device, int64_t n, const double* uv, const double* cam_rows, const double* planes, int64_t n_planes,
+                             double* xn_out, double* origin_out, double* dir_out, double* points_out, double* depth_out, int32_t* status_out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -96,6 +100,33 @@ int sba_project_model(int device, int dtype, int cam_model, int64_t n, const dou
   int rc = check_device(device);
   if (rc) return rc;
   return guarded(nullptr, [&] { return rows_dispatch(n_cam_params_of(cam_model), dtype, true, device, n, points, cam_rows, uv_out); });
+}
+
+int sba_unproject_rows(int device, int cam_model, int64_t n, const double* uv, const double* cam_rows, const double* planes,
+                       int64_t n_planes, double* xn_out, double* origin_out, double* dir_out, double* points_out, double* depth_out,
+                       int32_t* status_out) {
+  if (n < 0 || (n > 0 && (!uv || !cam_rows))) { g_last_error = "null argument"; return SBA_ERR_INVALID; }
+  if (cam_model != SBA_CAM_RADIAL && cam_model != SBA_CAM_RADIAL_TANGENTIAL) { g_last_error = "unknown camera model"; return SBA_ERR_INVALID; }
+  if (n_planes != 0 && n_planes != 1 && n_planes != n) { g_last_error = "sba_unproject_rows: n_planes must be 0, 1 or n"; return SBA_ERR_INVALID; }
+  if (n_planes == 0 && (points_out || depth_out)) { g_last_error = "sba_unproject_rows: points_out and depth_out need a plane"; return SBA_ERR_INVALID; }
+  if (n_planes > 0) {
+    if (!planes) { g_last_error = "null argument"; return SBA_ERR_INVALID; }
+    for (int64_t k = 0; k < n_planes; ++k) {
+      const double* p = planes + 4 * k;
+      const double nn = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+      if (!std::isfinite(nn) || !(nn > 0.0) || !std::isfinite(p[3])) {
+        g_last_error = "sba_unproject_rows: a plane is not finite or its normal is zero";
+        return SBA_ERR_INVALID;
+      }
+    }
+  }
+  int rc = check_device(device);
+  if (rc) return rc;
+  return guarded(nullptr, [&] {
+    return cam_model == SBA_CAM_RADIAL_TANGENTIAL
+               ? sba_unproject_rows_ncp13(device, n, uv, cam_rows, planes, n_planes, xn_out, origin_out, dir_out, points_out, depth_out, status_out)
+               : sba_unproject_rows_ncp11(device, n, uv, cam_rows, planes, n_planes, xn_out, origin_out, dir_out, points_out, depth_out, status_out);
+  });
 }
 
 int sba_create(const sba_problem_desc* desc, sba_handle** out) {
@@ -297,6 +328,16 @@ int sba_triangulate(sba_handle* h, const sba_tri_opts* opts, double* points_out,
   if (opts) o = *opts;
   return guarded(h, [&] {
     return h->eng->triangulate(&o, points_out, status_out, n_views_out, rms_px_out, max_px_out, spread_out, inlier_out, rep);
+  });
+}
+
+int sba_unproject(sba_handle* h, const sba_unp_opts* opts, const double* planes, int64_t n_planes, double* points_out, int32_t* status_out,
+                  int32_t* n_views_out, double* rms_px_out, double* max_px_out, uint8_t* used_out, sba_unp_report* rep) {
+  if (!h) return SBA_ERR_INVALID;
+  sba_unp_opts o{};
+  if (opts) o = *opts;
+  return guarded(h, [&] {
+    return h->eng->unproject(&o, planes, n_planes, points_out, status_out, n_views_out, rms_px_out, max_px_out, used_out, rep);
   });
 }
 

@@ -291,6 +291,8 @@ struct EngineBase {
   virtual int covariance(const sba_cov_opts* o, double* cam_full, double* cam_blocks, double* pt_cov, sba_cov_report* rep) = 0;
   virtual int triangulate(const sba_tri_opts* o, double* points_out, int32_t* status_out, int32_t* n_views_out, double* rms_out,
                           double* max_out, double* spread_out, uint8_t* inlier_out, sba_tri_report* rep) = 0;
+  virtual int unproject(const sba_unp_opts* o, const double* planes, int64_t n_planes, double* points_out, int32_t* status_out,
+                        int32_t* n_views_out, double* rms_out, double* max_out, uint8_t* used_out, sba_unp_report* rep) = 0;
   virtual int align(const sba_align_opts* o, const double* target_points, const double* point_weights, const double* target_centres,
                     const double* centre_weights, sba_align_report* rep) = 0;
   virtual int apply_similarity(double scale, const double* R, const double* t) = 0;

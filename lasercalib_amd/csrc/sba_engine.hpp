@@ -13,6 +13,7 @@
 #include "sba_ipc.hpp"
 #include "sba_covariance.hpp"
 #include "sba_triangulate.hpp"
+#include "sba_unproject.hpp"
 #include "sba_align.hpp"
 #include "sba_reproj.hpp"
 #include "sba_layout.hpp"
@@ -2219,6 +2220,15 @@ struct Engine : EngineBase {
     if (int rc = align_ready("sba_apply_similarity")) return rc;
     AlignIn<T> in{stream, C, N, cams[cur].p, pts[cur].p, ptsT[cur].p, campre[cur].p};
     return align_apply_run<T>(in, scale, R, t, err);
+  }
+
+  // ------------------------------------------------------------------ points on known planes (sba_unproject.hpp)
+  int unproject(const sba_unp_opts* o, const double* planes, int64_t n_planes, double* points_out, int32_t* status_out,
+                int32_t* n_views_out, double* rms_out, double* max_out, uint8_t* used_out, sba_unp_report* rep) override {
+    if (int rc = align_ready("sba_unproject")) return rc;
+    TriIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, ptsT[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
+                blk_desc.p, nblk, has_fixed ? pt_fixed_mask.p : nullptr, identity_perm ? nullptr : perm.data()};
+    return unp_run<T>(in, *o, planes, n_planes, points_out, status_out, n_views_out, rms_out, max_out, used_out, rep, err);
   }
 
   // ------------------------------------------------------------------ reprojection diagnostics (sba_reproj.hpp)

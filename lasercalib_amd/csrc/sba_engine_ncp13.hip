@@ -6,3 +6,7 @@ sba_host::EngineBase* sba_make_engine_ncp13(int dtype) { return SBA_NS::make_eng
 int sba_rows_call_ncp13(int dtype, bool project, int device, int64_t n, const double* pts, const double* other, double* out) {
   return SBA_NS::rows_call_dtype(dtype, project, device, n, pts, other, out);
 }
+int sba_unproject_rows_ncp13(int device, int64_t n, const double* uv, const double* cam_rows, const double* planes, int64_t n_planes,
+                             double* xn_out, double* origin_out, double* dir_out, double* points_out, double* depth_out, int32_t* status_out) {
+  return SBA_NS::unp_rows_call(device, n, uv, cam_rows, planes, n_planes, xn_out, origin_out, dir_out, points_out, depth_out, status_out);
+}

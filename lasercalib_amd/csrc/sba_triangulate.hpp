@@ -25,12 +25,10 @@ constexpr int TRI_TERMS = 15;        // doubles per observation row in LDS (k_tr
 constexpr int TRI_NEWTON_MAX = 20;
 constexpr unsigned char TRI_OBS_OUT = 0, TRI_OBS_IN = 1, TRI_OBS_UNUSABLE = 2, TRI_OBS_TRIMMED = 3;
 
-__global__ void __launch_bounds__(64) k_tri_cam_prep(const double* __restrict__ cams, double* __restrict__ tab, int C) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
+// one camera row (NCP columns) into its TRI_CAM table entry
+__device__ __forceinline__ void tri_cam_row(const double* __restrict__ cam, double* __restrict__ o) {
   double cp[CAMPRE];
-  campre_build<double>(cams + (size_t)c * NCP, cp);
-  double* o = tab + (size_t)c * TRI_CAM;
+  campre_build<double>(cam, cp);
 #pragma unroll
   for (int i = 0; i < 9; ++i) o[TC_R + i] = cp[CP_R + i];
   const double t0 = cp[CP_T], t1 = cp[CP_T + 1], t2 = cp[CP_T + 2];
@@ -44,6 +42,12 @@ __global__ void __launch_bounds__(64) k_tri_cam_prep(const double* __restrict__ 
   else { o[TC_P1] = 0.0; o[TC_P2] = 0.0; }
   o[TC_CX] = cp[CP_CX]; o[TC_CY] = cp[CP_CY];
   o[TRI_CAM - 1] = 0.0;
+}
+
+__global__ void __launch_bounds__(64) k_tri_cam_prep(const double* __restrict__ cams, double* __restrict__ tab, int C) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  tri_cam_row(cams + (size_t)c * NCP, tab + (size_t)c * TRI_CAM);
 }
 
 // forward distortion of sba_model.hpp on normalised coordinates and its symmetric 2 x 2 Jacobian

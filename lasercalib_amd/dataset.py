@@ -13,7 +13,8 @@ Extensions (no counterpart in the reference, which needs a known z-plane and one
 
 * :func:`filter_points_by_views`      -- the count test of get_points3d.py:52-56 without the init-camera test
 * :func:`make_dataset_triangulated`   -- the dataset entry with ``points_3d`` triangulated on the device from all views
-* :func:`reindex_dataset`             -- its pure-numpy half: drop points / observations and renumber
+* :func:`make_dataset_unprojected`    -- the dataset entry with ``points_3d`` un-projected on the device onto the known z-plane
+* :func:`reindex_dataset`             -- their pure-numpy half: drop points / observations and renumber
 
 All arrays are numpy float64 / int64, exactly what ``PySBA.__init__`` (pySBA.py:28-59) takes.
 """
@@ -24,7 +25,7 @@ from typing import Dict, List, Sequence
 import numpy as np
 
 __all__ = ["filter_points", "observation_list", "make_dataset", "concatenate_datasets", "is_point_major",
-           "filter_points_by_views", "reindex_dataset", "make_dataset_triangulated"]
+           "filter_points_by_views", "reindex_dataset", "make_dataset_triangulated", "make_dataset_unprojected"]
 
 
 def filter_points(centroids: np.ndarray, min_num_cam_per_point: int, cam_idx_3dpts: int) -> np.ndarray:
@@ -151,3 +152,22 @@ def make_dataset_triangulated(in_pts: np.ndarray, cameraArray: np.ndarray, min_v
         tri = prob.triangulate(min_views=min_views, trim_px=trim_px, max_drop=max_drop)
     keep_obs = tri.inliers if trim_px else None
     return reindex_dataset(n_cams, tri.points, points_2d, camera_ind, point_ind, tri.ok, keep_obs)
+
+
+def make_dataset_unprojected(in_pts: np.ndarray, cameraArray: np.ndarray, z, cam_idx_3dpts: int = None, min_views: int = 1,
+                             dtype="f64", device: int = 0) -> Dict[str, object]:
+    """One dataset entry whose ``points_3d`` lie on the known plane z = ``z`` (a scalar or one height per frame, ``z_gt`` of the
+    reference's config.json), un-projected on the device at ``cameraArray`` (``_native.Problem.unproject``).
+
+    With ``cam_idx_3dpts`` the pixels of that camera alone are un-projected: the reference's route (get_points3d.py:88-99).
+    Without it every frame gets the point of the plane closest to the rays of ALL its views.  Frames without an OK estimate (no
+    usable view, a ray along the plane, a point behind a camera) are dropped and the list is re-indexed.  Same keys and dtypes
+    as :func:`make_dataset`.
+    """
+    from . import _native
+    in_pts = np.asarray(in_pts, dtype=np.float64)
+    camera_ind, point_ind, points_2d = observation_list(in_pts)
+    n_pts, n_cams = in_pts.shape[0], in_pts.shape[2]
+    with _native.Problem(cameraArray, np.zeros((n_pts, 3)), points_2d, camera_ind, point_ind, dtype=dtype, device=device) as prob:
+        unp = prob.unproject(_native.z_planes(z, n_pts), ref_cam=cam_idx_3dpts, min_views=min_views)
+    return reindex_dataset(n_cams, unp.points, points_2d, camera_ind, point_ind, unp.ok)

@@ -354,6 +354,40 @@ class PySBA:
             self.points3D = np.where(tri.ok[:, None], tri.points, pts)
         return tri
 
+    def undistort(self, points2D, cameraArray):
+        """Extension: the inverse of the distortion on gathered rows, on the device -- ``points2D`` (M, 2) pixels and
+        ``cameraArray`` (M, 11) or (M, 13) rows give the ideal pixels ``f x + cx``, ``f y + cy`` of the undistorted normalised
+        coordinates (``include/sba_hip.h``, sba_unproject_rows), which is what ``cv2.undistortPoints(..., P=K)`` returns for this
+        camera model (verify_world.py:70).  NaN where the inversion fails."""
+        rows = np.ascontiguousarray(cameraArray, dtype=np.float64)
+        out = _native.unproject_rows(points2D, rows, device=_env_device())
+        return out["xn"] * rows[:, 6:7] + rows[:, -2:]
+
+    def unproject(self, z=None, planes=None, ref_cam=None, min_views=1, update=True):
+        """Extension: ``points3D`` on known planes from ``cameraArray`` and the pixels, on the device -- per point the point of
+        its plane closest to the rays of its observations (``include/sba_hip.h``, sba_unproject).  ``z``: a scalar or (N,), the
+        plane (0, 0, 1, z) of every laser dot (``z_gt`` of the reference's config.json); or ``planes``: (4,) or (N, 4) rows
+        (n_x, n_y, n_z, d) with n . X = d.  ``ref_cam``: use the observations of that camera only, the reference's route
+        (get_points3d.py:88-99, ``cam_name_for_3d_init``); default: all views.  The problem is built as ``triangulate`` builds
+        it.  ``update=True`` rebinds ``self.points3D`` to a new array holding the estimate where the status is OK and the old
+        coordinates elsewhere; the caller's array is never written.  Returns a ``_native.Unprojection``: ``points``, ``status``,
+        ``n_views``, ``rms_px``, ``max_px``, ``used`` (per observation, the caller's order), ``ok``."""
+        cams = np.ascontiguousarray(self.cameraArray, dtype=np.float64)
+        pts = np.ascontiguousarray(self.points3D, dtype=np.float64)
+        if (z is None) == (planes is None):
+            raise ValueError("unproject needs exactly one of z and planes")
+        if planes is None:
+            planes = _native.z_planes(z, pts.shape[0])
+        with _native.Problem(cams, pts, self.points2D, self.cameraIndices, self.point2DIndices,
+                             weights=self._weights_or_none(), dtype=_env_dtype(), device=_env_device()) as prob:
+            mask = self._fixed_mask(pts.shape[0])
+            if mask is not None:
+                prob.set_fixed_points(mask)
+            unp = prob.unproject(planes, ref_cam=ref_cam, min_views=min_views)
+        if update:
+            self.points3D = np.where(unp.ok[:, None], unp.points, pts)
+        return unp
+
     def align(self, points=None, cameras=None, point_weights=None, camera_weights=None, with_scale=True, update=True):
         """Extension: brings the solution into a frame of the caller's -- the similarity (scale, R, t) that carries
         ``points3D`` onto ``points`` (N, 3) and the centres of ``cameraArray`` onto the centres of ``cameras`` (a (C, P) camera
