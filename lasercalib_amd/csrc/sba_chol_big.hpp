@@ -835,9 +835,18 @@ __global__ __launch_bounds__(CHOLBIG_THREADS) void k_chol_big_dag(const double* 
 // boundary: the L(b,t) block a workgroup needs next is already in its registers when x_b arrives.  The waits are bounded
 // (CHOLBIG_WAIT_TICKS of the 100 MHz clock, then the solve is flagged as failed: a rejected LM step) and every workgroup of
 // the launch is resident at once -- the rule of sba_ipc.hpp.
+// The launch of parity p works in copy p of x (xv + p * xstride) and leaves copy 1 - p empty over its first nclear entries, the
+// workgroups sharing them block by block.  The host passes nclear = the largest extent a launch since that copy was last emptied
+// may have stored into (at least this launch's own nbx * BB = gridDim.x * BB), so the copy the NEXT launch works in is empty as a
+// whole whatever system sizes the handle has solved before: a launch never finds the x of an earlier one where it polls for its own.
+__device__ __forceinline__ void cholbig_empty_other(double* __restrict__ xv, int xstride, unsigned epoch, int nclear) {
+  double* xnext = xv + (size_t)((epoch + 1) & 1) * xstride;
+  if (threadIdx.x < BB)
+    for (int k = blockIdx.x * BB + threadIdx.x; k < nclear; k += gridDim.x * BB) xnext[k] = __longlong_as_double(CHOLBIG_X_EMPTY);
+}
 template <typename S>
 __device__ __forceinline__ void chol_big_back_all_body(const S* __restrict__ W, int npad, int n, const double* __restrict__ Ld_ws,
-                                                       const double* __restrict__ Minv_ws, double* __restrict__ xv,
+                                                       const double* __restrict__ Minv_ws, double* __restrict__ xv, int xstride, int nclear,
                                                        unsigned epoch, double* __restrict__ sol, int* __restrict__ info,
                                                        const S* __restrict__ Mimg_ws, double* __restrict__ s_y, double* __restrict__ s_x,
                                                        double (*__restrict__ s_p)[BB], double* __restrict__ s_M, int& s_late,
@@ -877,10 +886,11 @@ __device__ __forceinline__ void chol_big_back_all_body(const S* __restrict__ W, 
   if (nbx - 1 > t) fetch_L(nbx - 1);
   // x travels as its own flag: xv has one copy per parity of the epoch, filled with a NaN nobody computes (CHOLBIG_X_EMPTY) until the
   // owner of a block row stores its x there; a waiting thread polls the very word it needs -- one trip through memory per hand-over
-  // instead of two (flag, then data).  Every workgroup empties its slice of the OTHER copy for the next launch.
-  double* xcur = xv + (size_t)(epoch & 1) * npad;
-  double* xnext = xv + (size_t)((epoch + 1) & 1) * npad;
-  if (threadIdx.x < BB) xnext[t * BB + threadIdx.x] = __longlong_as_double(CHOLBIG_X_EMPTY);
+  // instead of two (flag, then data).  The two copies lie xstride apart, a distance that belongs to the buffer and not to this
+  // launch's system, and the launch as a whole empties the first nclear entries of the OTHER copy for the next launch: everything an
+  // earlier launch of ANY system size may have left there (cholbig_empty_other), not only the nbx blocks of this one.
+  double* xcur = xv + (size_t)(epoch & 1) * xstride;
+  cholbig_empty_other(xv, xstride, epoch, nclear);
   if (threadIdx.x == 0) s_late = 0;
   if (threadIdx.x < BB) s_y[threadIdx.x] = (double)yk + yk_dense;
 #pragma unroll
@@ -935,7 +945,9 @@ constexpr int CHOLBIG_MAX_NBX = 27;         // 1728 unknowns: 128 cameras x 13 p
 template <typename T>
 __global__ __launch_bounds__(256) void k_chol_big_back_all(const void* __restrict__ W, int npad, int n, const double* __restrict__ Ld_ws,
                                                            const double* __restrict__ Minv_ws,
-                                                           double* __restrict__ xv /* [2][npad], CHOLBIG_X_EMPTY before the first launch */,
+                                                           double* __restrict__ xv /* [2][xstride], CHOLBIG_X_EMPTY before the first launch */,
+                                                           int xstride /* >= npad of every launch on the buffer */,
+                                                           int nclear /* entries of the other copy to empty: nbx * BB <= nclear <= xstride */,
                                                            unsigned epoch, double* __restrict__ sol, int* __restrict__ info,
                                                            LMState* __restrict__ st,
                                                            const void* __restrict__ Mimg_ws /* k_chol_big_dag's images, or null: the dense copies */,
@@ -946,16 +958,17 @@ __global__ __launch_bounds__(256) void k_chol_big_back_all(const void* __restric
   __shared__ int s_late, s_flag;
   const int st_status = st->status, st_retry = st->chol_retry;      // (both requested at once: two dependent trips to memory otherwise)
   if (st_status >= 0) {                             // (the same record on every workgroup: nobody is left waiting)
-    // a launch that has nothing to do (the solve has ended, the iterations enqueued behind it drain) still empties its slice of the
-    // other copy of x: the next launch -- of the next solve on this handle -- counts on finding it empty
-    if (threadIdx.x < BB) xv[(size_t)((epoch + 1) & 1) * npad + blockIdx.x * BB + threadIdx.x] = __longlong_as_double(CHOLBIG_X_EMPTY);
+    // a launch that has nothing to do (the solve has ended, the iterations enqueued behind it drain) still empties the other copy
+    // of x like any other: the host counts every launch when it works out nclear for the next one, of the next solve on this
+    // handle -- which does not rely on such a launch having run (a solve may end on the last iteration that was enqueued)
+    cholbig_empty_other(xv, xstride, epoch, nclear);
     return;
   }
   if (f32_data && !st_retry)
-    chol_big_back_all_body<float>(static_cast<const float*>(W), npad, n, Ld_ws, Minv_ws, xv, epoch, sol, info,
+    chol_big_back_all_body<float>(static_cast<const float*>(W), npad, n, Ld_ws, Minv_ws, xv, xstride, nclear, epoch, sol, info,
                                   static_cast<const float*>(Mimg_ws), s_y, s_x, s_p, s_M, s_late, s_sol);
   else
-    chol_big_back_all_body<double>(static_cast<const double*>(W), npad, n, Ld_ws, Minv_ws, xv, epoch, sol, info,
+    chol_big_back_all_body<double>(static_cast<const double*>(W), npad, n, Ld_ws, Minv_ws, xv, xstride, nclear, epoch, sol, info,
                                    static_cast<const double*>(Mimg_ws), s_y, s_x, s_p, s_M, s_late, s_sol);
   if (blockIdx.x != 0) return;
   __syncthreads();                                  // (a timed-out substitution has raised info: the epilogue then rejects the step)

@@ -316,6 +316,7 @@ struct Engine : EngineBase {
   DevBuf<double> chol_sol, chol_work, chol_W, chol_Minv, chol_Ld, chol_yv;
   DevBuf<int> chol_info;
   unsigned chol_epoch = 0;              // k_chol_big_back_all: launches so far (its parity picks the copy of x the launch works in)
+  int chol_yv_ext[2] = {0, 0};          // ... entries at the front of each copy of x that a launch may have left non-empty (launch_chol_big)
   DevBuf<unsigned> chol_dag_flags;      // k_chol_big_dag: Mimg_j / W(r,c) published (value = the launch's epoch)
   DevBuf<double> chol_Mimg;             // k_chol_big_dag: the factored diagonal blocks and their inverses, as they lie in LDS
   unsigned chol_dag_epoch = 0;
@@ -1674,10 +1675,13 @@ struct Engine : EngineBase {
     const int npad = cholbig_npad(n_sys), nbr = npad / BB, nbx = (n_sys + BB - 1) / BB;
     if (chol_W.n < (size_t)npad * npad) {
       chol_W.alloc((size_t)npad * npad); chol_Minv.alloc((size_t)nbr * BB * BB); chol_Ld.alloc((size_t)nbr * BB * BB);
-      chol_yv.alloc(2 * (size_t)npad);      // k_chol_big_back_all: x, one copy per parity of its epoch, "empty" until stored
+      // k_chol_big_back_all: x, one copy per parity of its epoch, "empty" until stored.  The copies lie chol_yv.n / 2 apart, the npad
+      // of the largest system the handle has solved, whatever the system of a launch (a smaller one uses the front of each copy)
+      chol_yv.alloc(2 * (size_t)npad);
       std::vector<long long> empty(2 * (size_t)npad, CHOLBIG_X_EMPTY);
       HIPCHK(hipMemcpyAsync(chol_yv.p, empty.data(), empty.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
       sync();
+      chol_yv_ext[0] = chol_yv_ext[1] = 0;
     }
     if (chol_sol.n < (size_t)n_sys) { chol_sol.alloc(n_sys); chol_info.alloc(1); }
     const size_t lds = (size_t)CHOLBIG_LDS_BLOCKS * CBS * sizeof(double);
@@ -1717,10 +1721,17 @@ struct Engine : EngineBase {
                            chol_Minv.p, chol_Ld.p, chol_info.p, d_state.p);
       }
     }
-    // the whole back substitution in one launch: block row = workgroup, x_b handed over as its own flag; block row 0 runs the epilogue
+    // the whole back substitution in one launch: block row = workgroup, x_b handed over as its own flag; block row 0 runs the epilogue.
+    // The launch stores its x into the first nbx * BB entries of the copy of its parity and empties the other copy as far as any
+    // launch before it -- of this solve or of an earlier one with another system size -- may have stored into it: after every launch
+    // the other copy is empty as a whole, so the next launch finds nothing but its own x there, whatever its size.
+    const int par = (int)(++chol_epoch & 1), xstride = (int)(chol_yv.n / 2);
+    const int nclear = std::max(chol_yv_ext[1 - par], nbx * BB);
     hipLaunchKernelGGL(k_chol_big_back_all<T>, dim3(nbx), dim3(256), 0, stream, (const void*)chol_W.p, npad, n_sys, chol_Ld.p, chol_Minv.p,
-                       chol_yv.p, ++chol_epoch, chol_sol.p, chol_info.p, d_state.p, dag ? (const void*)chol_Mimg.p : (const void*)nullptr,
+                       chol_yv.p, xstride, nclear, chol_epoch, chol_sol.p, chol_info.p, d_state.p, dag ? (const void*)chol_Mimg.p : (const void*)nullptr,
                        dag32 ? 1 : 0, Esys, C, D2c.p, ps_lm(), delta_c.p, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr);
+    chol_yv_ext[1 - par] = 0;
+    chol_yv_ext[par] = nbx * BB;
   }
 
   // scal == nullptr: single rank, the partials are folded inside k_decide and no scalar exchange is needed

@@ -208,7 +208,11 @@ def test_second_solve_on_the_same_handle_repeats_the_first(C, dtype):
     """A solve ends in the middle of a batch of enqueued iterations: the launches behind the end return at once.  The one-launch
     factorisation and its back substitution hand data over through epoch flags and an "empty" marker per parity of the launch
     count, so launches that did nothing must leave both in order for the next solve on the handle: the same parameters set again,
-    the same solve again, the same bits."""
+    the same solve again, the same bits.
+
+    This test repeats ONE mode, and its solves end inside a batch, so launches that do nothing follow them.  Another mode (another
+    system size) on the same handle, a solve that ends on the last iteration enqueued, options set and cleared and the other calls
+    of the handle between two solves are tests/test_gpu_handle_reuse.py."""
     rig = make_rig(C, 80, seed=40 + C, visibility=0.4, min_cams_per_point=4)
     x0 = np.hstack((rig["cams0"].ravel(), rig["pts0"].ravel()))
     with _native.Problem(rig["cams0"], rig["pts0"], rig["points_2d"], rig["camera_ind"], rig["point_ind"], dtype=dtype) as prob:
