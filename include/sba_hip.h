@@ -559,6 +559,56 @@ int sba_reproj_stats(sba_handle* h, const sba_reproj_opts* opts /*NULL: all defa
                      double* cam_radial /*C*nr*4*/, double* pt_stats /*N*3*/, double* err_out /*M, caller's order*/,
                      int64_t* worst_idx /*K*/, double* worst_err /*K*/, sba_reproj_report* rep);
 
+/* ---------------------------------------------------------------- laser-dot detection (the first stage of the workflow)
+ * The reference finds the laser dot of a frame with cv.threshold + cv.moments on the green channel and keeps the centroid,
+ * truncated to whole pixels (lasercalib/feature_detection.py:44-54, green_laser_finder_faster; driven per video by
+ * scripts/detect_laser_points.py:33-59).  sba_detect_dots does this for a batch of frames in one pass over the pixels and
+ * returns the exact integer moments, so that the caller can have the reference's integers (sum m y // n, sum m x // n) or a
+ * sub-pixel centroid.  Stateless: no handle.  Video decoding is the caller's; frames are 8-bit, channels interleaved.
+ *
+ * Per frame, with m = 1 where the pixel is inside both regions and value > threshold (value = byte `channel` of the pixel),
+ * w = (value - threshold) m, x the column and y the row:
+ *   sums     = [n = sum m, sum m x, sum m y, sum m x^2, sum m y^2, sum m x y, sum w, sum w x, sum w y,
+ *               n_sat = sum m [value == 255], 0, 0]: exact unsigned 64-bit integers (width, height <= 16384:
+ *               even sum w x^2 <= 255 * 16384 * 16384^3 / 3 = 6.1e18 < 2^64)
+ *   box      = [xmin, ymin, xmax, ymax] of m; [width, height, -1, -1] when n = 0
+ *   centroid = [sum m x / n, sum m y / n, sum w x / sum w, sum w y / sum w], each ONE IEEE float64 division of the two integers
+ *              converted to float64; filled whenever n > 0, whatever the status; all NaN when n = 0
+ *   status   = the first that applies: NONE (n = 0), TOO_SMALL (n < min_area), TOO_LARGE (max_area > 0 and n > max_area),
+ *              SPREAD (max_extent > 0 and max(xmax - xmin, ymax - ymin) + 1 > max_extent), else OK.
+ * SPREAD is a one-pass stand-in for the "exactly one connected component" rule of the reference's older green_laser_finder
+ * (feature_detection.py:24-40): a second blob or a reflection elsewhere in the frame stretches the bounding box and the frame
+ * is rejected.  It is NOT connected-component labelling: two blobs closer than max_extent pass, one long streak does not.
+ * Parity: cv.threshold(green, t, 255, 0) followed by cv.moments gives m00 = 255 n, m10 = 255 sum m x, m01 = 255 sum m y,
+ * exact in float64 at these sizes, so the reference's int(m10 / m00), int(m01 / m00) are sum m x // n, sum m y // n.
+ * frames: n_frames images of height rows of width pixels of `channels` bytes; row r of frame f starts at
+ *   frames + f frame_pitch + r row_pitch.  No alignment is asked of the base or the pitches.  Host memory, or with
+ *   frames_on_device device memory of `device`, which is read in place and never copied.  Host frames are staged through two
+ *   device buffers of chunk_frames frames (the copy of one chunk runs beside the kernel of the one before): device memory
+ *   does not grow with n_frames, and the call is bound by the host-to-device copy, not by the kernel.
+ * Every output pointer is host memory and may be NULL.  n_frames = 0 returns SBA_OK and writes nothing.
+ * Errors (checked before any device work, text in sba_last_error(NULL)): SBA_ERR_INVALID for null frames with n_frames > 0,
+ *   channels not 1, 3 or 4, channel outside 0..channels-1, threshold outside 0..255, a negative size or limit, row_pitch <
+ *   width channels, frame_pitch < height row_pitch; SBA_ERR_UNSUPPORTED for width or height above 16384.
+ * Determinism: the partial sums of the workgroups are merged with integer atomics; two calls return the same bits. */
+typedef enum { SBA_DOT_OK = 0, SBA_DOT_NONE = 1, SBA_DOT_TOO_SMALL = 2, SBA_DOT_TOO_LARGE = 3, SBA_DOT_SPREAD = 4 } sba_dot_status;
+typedef struct {
+  int32_t channel;          /* interleaved channel that is thresholded; the reference: 1 (green of BGR) */
+  int32_t threshold;        /* 0..255; a pixel counts when value > threshold; the reference: 50          */
+  int32_t frames_on_device; /* 1: `frames` is a device pointer on `device`                               */
+  int32_t min_area, max_area;   /* on n; 0 = no limit                                                    */
+  int32_t max_extent;       /* on max(xmax-xmin, ymax-ymin)+1; 0 = no limit                              */
+  int32_t roi_rect[4];      /* x0, y0, x1, y1 half-open, clipped to the frame; all 0 = whole frame       */
+  int32_t roi_circle[3];    /* cx, cy, r: keeps (x-cx)^2+(y-cy)^2 <= r^2 in integers; r <= 0 = off       */
+  int32_t chunk_frames;     /* host frames: frames per staged chunk; <= 0 = library default              */
+  int32_t reserved[2];
+} sba_dot_opts;
+int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels /*1, 3 or 4*/,
+                    int64_t row_pitch /*bytes, >= width*channels*/, int64_t frame_pitch /*bytes, >= height*row_pitch*/,
+                    const sba_dot_opts* opts /*NULL: {1, 50, 0, ...0}*/,
+                    uint64_t* sums /*n_frames*12 or NULL*/, int32_t* box /*n_frames*4 or NULL*/,
+                    double* centroid /*n_frames*4 or NULL*/, int32_t* status /*n_frames or NULL*/);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = (
     "sba_lm_solve_trial", "sba_lm_decide", "sba_lm_decide_async", "sba_lm_poll", "sba_lm_run", "sba_lm_finish", "sba_lm_get_log", "sba_time_kernel", "sba_get_kernel_profile",
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
-    "sba_unproject_rows", "sba_unproject",
+    "sba_unproject_rows", "sba_unproject", "sba_detect_dots",
 )
 
 
@@ -103,6 +103,16 @@ class UnpReport(C.Structure):
 
 UNP_OK, UNP_ANCHORED, UNP_NO_VIEW, UNP_DEGENERATE, UNP_BEHIND = 0, 1, 2, 3, 4       # sba_unp_status
 UNP_ROW_OK, UNP_ROW_UNUSABLE, UNP_ROW_PARALLEL, UNP_ROW_BEHIND = 0, 1, 2, 3        # sba_unp_row_status
+
+
+class DotOpts(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("threshold", C.c_int32), ("frames_on_device", C.c_int32), ("min_area", C.c_int32),
+                ("max_area", C.c_int32), ("max_extent", C.c_int32), ("roi_rect", C.c_int32 * 4), ("roi_circle", C.c_int32 * 3),
+                ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+DOT_OK, DOT_NONE, DOT_TOO_SMALL, DOT_TOO_LARGE, DOT_SPREAD = 0, 1, 2, 3, 4       # sba_dot_status
+DOT_MAX_DIM = 16384
 
 
 class AlignOpts(C.Structure):
@@ -200,6 +210,33 @@ class Unprojection:
     @property
     def ok(self):
         return self.status == UNP_OK
+
+
+class LaserDots:
+    """Result of detect_dots (sba_detect_dots, include/sba_hip.h), one row per frame: ``sums`` (B, 12) uint64 -- n, sum m x,
+    sum m y, sum m x^2, sum m y^2, sum m x y, sum w, sum w x, sum w y, n_sat, 0, 0; ``box`` (B, 4) int32 -- xmin, ymin, xmax, ymax;
+    ``centroid`` (B, 4) float64 -- binary x, y, then weighted x, y (columns first: x is the column, y the row); ``status`` (B,)
+    int32 of DOT_*; ``n`` (B,) the number of pixels above the threshold; ``ok`` the mask of the frames with status DOT_OK."""
+
+    def __init__(self, sums, box, centroid, status):
+        self.sums, self.box, self.centroid, self.status = sums, box, centroid, status
+
+    @property
+    def n(self):
+        return self.sums[:, 0]
+
+    @property
+    def ok(self):
+        return self.status == DOT_OK
+
+    @property
+    def spread_px(self):
+        """(B,) RMS distance of the pixels above the threshold from their binary centroid,
+        sqrt(sum m x^2 / n - cx^2 + sum m y^2 / n - cy^2), computed on the host; NaN where n = 0."""
+        n = self.sums[:, 0].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            var = (self.sums[:, 3] / n - self.centroid[:, 0] ** 2) + (self.sums[:, 4] / n - self.centroid[:, 1] ** 2)
+            return np.sqrt(np.maximum(var, 0.0))
 
 
 class Alignment:
@@ -338,6 +375,8 @@ def load():
         "sba_unproject_rows": (C.c_int, [C.c_int, C.c_int, C.c_int64, dp, dp, dp, C.c_int64, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]),
         "sba_unproject": (C.c_int, [H, C.POINTER(UnpOpts), dp, C.c_int64, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp,
                                     C.POINTER(C.c_uint8), C.POINTER(UnpReport)]),
+        "sba_detect_dots": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                      C.POINTER(DotOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
         "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
         "sba_reproj_stats": (C.c_int, [H, C.POINTER(ReprojOpts), dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(ReprojReport)]),
@@ -483,6 +522,64 @@ def unproject_rows(uv, cam_rows, planes=None, device=0):
                                   _dptr(out["xn"]), _dptr(out["origin"]), _dptr(out["dir"]), _dptr(out.get("points")),
                                   _dptr(out.get("depth")), out["status"].ctypes.data_as(C.POINTER(C.c_int32))))
     return out
+
+
+def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_extent=0, roi_rect=None, roi_circle=None,
+                chunk_frames=0, device=0):
+    """Thresholded image moments of a batch of frames (sba_detect_dots, include/sba_hip.h) -> LaserDots.
+
+    ``frames``: uint8, (B, H, W, C) with C in (1, 3, 4) or (B, H, W).  A numpy array is read where it is, in any layout whose
+    pixels are contiguous (channel stride 1, pixel stride C) and whose row and frame strides are large enough: the pitches are
+    its strides, nothing is copied on the host.  A torch tensor on ``device`` is handed over as a device pointer and read in
+    place.  ``channel`` is the thresholded byte of a pixel (the reference: 1, green of BGR), a pixel counts when its value is
+    above ``threshold``; ``roi_rect`` = (x0, y0, x1, y1) half-open, ``roi_circle`` = (cx, cy, r); ``min_area``, ``max_area``,
+    ``max_extent``: the status rules, 0 = no limit; ``chunk_frames``: host frames staged per copy, 0 = the library's default."""
+    lib = load()
+    tensor = _is_tensor(frames)
+    if tensor:
+        if not frames.is_cuda or (frames.device.index or 0) != device:
+            raise ValueError(f"frames: the tensor must live on cuda:{device}")
+        if str(frames.dtype) != "torch.uint8":
+            raise ValueError(f"frames: the tensor must be uint8, not {frames.dtype}")
+        shape, strides = tuple(frames.shape), tuple(frames.stride())
+    else:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8:
+            raise ValueError(f"frames must be uint8, not {frames.dtype}")
+        shape, strides = frames.shape, frames.strides
+    if len(shape) == 3:
+        shape, strides = shape + (1,), strides + (1,)
+    if len(shape) != 4 or shape[3] not in (1, 3, 4):
+        raise ValueError(f"frames must be (B, H, W, C) with C in (1, 3, 4) or (B, H, W), got {tuple(shape[:len(frames.shape)])}")
+    B, H, W, Cn = (int(v) for v in shape)
+    sf, sr, sp, sc = (int(v) for v in strides)
+    # the strides of an axis of length 1, and all strides of an empty array, say nothing: take those of a packed array
+    empty = B * H * W == 0
+    sc = 1 if Cn == 1 or empty else sc
+    sp = Cn if W == 1 or empty else sp
+    sr = W * Cn if H == 1 or empty else sr
+    sf = H * sr if B == 1 or empty else sf
+    if (sc, sp) != (1, Cn) or sr < W * Cn or sf < H * sr:
+        raise ValueError("frames: pixels must be contiguous (channel stride 1, pixel stride C), rows and frames in ascending order; "
+                         f"got strides {tuple(strides)} for shape {tuple(shape)}")
+    opts = DotOpts()
+    opts.channel, opts.threshold, opts.frames_on_device = int(channel), int(threshold), 1 if tensor else 0
+    opts.min_area, opts.max_area, opts.max_extent, opts.chunk_frames = int(min_area), int(max_area), int(max_extent), int(chunk_frames)
+    if roi_rect is not None:
+        opts.roi_rect = (C.c_int32 * 4)(*(int(v) for v in roi_rect))
+    if roi_circle is not None:
+        opts.roi_circle = (C.c_int32 * 3)(*(int(v) for v in roi_circle))
+    sums, box = np.zeros((B, 12), np.uint64), np.zeros((B, 4), np.int32)
+    centroid, status = np.full((B, 4), np.nan), np.full(B, DOT_NONE, np.int32)
+    if tensor:
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # the frames are complete before the library reads them
+        ptr = frames.data_ptr()
+    else:
+        ptr = frames.ctypes.data
+    _check(lib.sba_detect_dots(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts), sums.ctypes.data, box.ctypes.data,
+                               centroid.ctypes.data, status.ctypes.data))
+    return LaserDots(sums, box, centroid, status)
 
 
 class Problem:

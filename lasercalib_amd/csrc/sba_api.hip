@@ -14,6 +14,9 @@ int sba_unproject_rows_ncp11(int device, int64_t n, const double* uv, const doub
                              double* xn_out, double* origin_out, double* dir_out, double* points_out, double* depth_out, int32_t* status_out);
 int sba_unproject_rows_ncp13(int device, int64_t n, const double* uv, const double* cam_rows, const double* planes, int64_t n_planes,
                              double* xn_out, double* origin_out, double* dir_out, double* points_out, double* depth_out, int32_t* status_out);
+int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                    int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
+                    int32_t* status);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -363,6 +366,36 @@ int sba_reproj_stats(sba_handle* h, const sba_reproj_opts* opts, double* cam_sta
   if (opts) o = *opts;
   return guarded(h, [&] {
     return h->eng->reproj_stats(&o, cam_stats, cam_hist, cam_grid, cam_radial, pt_stats, err_out, worst_idx, worst_err, rep);
+  });
+}
+
+int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                    int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts* opts, uint64_t* sums, int32_t* box, double* centroid,
+                    int32_t* status) {
+  sba_dot_opts o{};
+  o.channel = 1; o.threshold = 50;
+  if (opts) o = *opts;
+  auto invalid = [](const char* what) { g_last_error = std::string("sba_detect_dots: ") + what; return (int)SBA_ERR_INVALID; };
+  if (n_frames < 0 || height < 0 || width < 0) return invalid("negative size");
+  if (n_frames > 0 && !frames) return invalid("null frames");
+  if (channels != 1 && channels != 3 && channels != 4) return invalid("channels must be 1, 3 or 4");
+  if (o.channel < 0 || o.channel >= channels) return invalid("channel out of range");
+  if (o.threshold < 0 || o.threshold > 255) return invalid("threshold must be in 0..255");
+  if (o.min_area < 0 || o.max_area < 0 || o.max_extent < 0) return invalid("negative area or extent limit");
+  if (row_pitch < (int64_t)width * channels) return invalid("row_pitch is smaller than width * channels");
+  if ((__int128)height * row_pitch > frame_pitch) return invalid("frame_pitch is smaller than height * row_pitch");
+  if ((__int128)n_frames * frame_pitch > INT64_MAX) return invalid("n_frames * frame_pitch overflows");
+  // up to 16384 x 16384 every sum fits 64 bits: the largest a frame could ask for, sum w x^2 <= 255 * 16384 * 16384^3 / 3 = 6.1e18
+  // < 2^64 = 1.8e19 (the sums actually returned are far smaller: sba_detect.hpp)
+  if (height > 16384 || width > 16384) {
+    g_last_error = "sba_detect_dots: width and height are limited to 16384 (the bound under which every sum fits 64 bits)";
+    return SBA_ERR_UNSUPPORTED;
+  }
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (n_frames == 0) return SBA_OK;
+  return guarded(nullptr, [&] {
+    return sba_detect_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, sums, box, centroid, status);
   });
 }
 
