@@ -316,13 +316,45 @@ template <int MAXNB> struct CholbPre {
                                                                            // the blocks beyond them are fetched after the prefetched ones are in LDS
 };
 
+// workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt (its release fence cannot tell loads
+// from stores on gfx9), which would expose the latency of the global loads deliberately left in flight across it
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// The f32 image of the system (fp32 engine, the library's own single-rank loop): k_build_exchange stores every entry of the lower
+// block triangle once more as a float at the place the entry has in this kernel's LDS (CholLay<float, LD>), so the load phase is
+// a copy of 16-byte pieces in LDS order: first the pieces of the first block column (all threads, R0 rounds), then the other
+// blocks behind them (waves 1..7, R1 rounds), all requested in the kernel's first instructions.
+template <int MAXNB, int LD> struct CholbImg {
+  static_assert((CB * LD) % 4 == 0, "a block is a whole number of 16-byte pieces");
+  static constexpr int NBE = (MAXNB > CHOLB_MAX_NB && LD == 20) ? 14 : MAXNB;      // block rows the instance meets (20-float rows: up to 14)
+  static constexpr int F4B = CB * LD / 4;                                           // 16-byte pieces per block
+  static constexpr int R0 = (NBE * F4B + CHOLB_LDS_THREADS - 1) / CHOLB_LDS_THREADS;
+  static constexpr int TREM = CHOLB_LDS_THREADS - 64;
+  static constexpr int R1 = (NBE * (NBE - 1) / 2 * F4B + TREM - 1) / TREM;
+};
+template <int MAXNB, int LD> struct CholbImgRegs {
+  float4 q0[CholbImg<MAXNB, LD>::R0];
+  float4 q1[CholbImg<MAXNB, LD>::R1];
+  int m1[CholbImg<MAXNB, LD>::R1];     // piece index in the image (= in LDS) | (system row + 1) << 16 | component << 28 when the piece holds a diagonal entry
+};
+// piece w of a diagonal block: (row + 1) | component << 8 when it holds the block's diagonal entry of that row, else 0
+template <int LD> __device__ __forceinline__ int cholb_img_diag(int w) {
+  const int p0 = 4 * w, row = (p0 + 3) / (LD + 1), pd = row * (LD + 1);
+  return (pd >= p0 && row < CB) ? ((row + 1) | ((pd - p0) << 8)) : 0;
+}
+__device__ __forceinline__ void cholb_img_patch(float4& v, int comp, float d) {
+  v.x = comp == 0 ? d : v.x; v.y = comp == 1 ? d : v.y; v.z = comp == 2 ? d : v.z; v.w = comp == 3 ? d : v.w;
+}
+
 // Factorisation + both substitutions in scalar type S on the block triangle in dynamic LDS.  PREFETCHED: the system's entries are in
 // the c0 / c1 registers the kernel requested in its first instructions; otherwise (second attempt after a refused f32 factorisation)
-// they are read from E here.  Returns the failure flag; the solution is left in sh.x.
-template <typename S, bool NEWTON, bool PREFETCHED, int MAXNB, typename L = CholLay<S>>
+// they are read from E here.  LOAD: 1 = prefetched (above), 0 = from E, 2 = the f32 image, whose pieces are in img's registers and
+// whose damped diagonal the kernel has left in s_a0.  Returns the failure flag; the solution is left in sh.x.
+template <typename S, bool NEWTON, int LOAD, int MAXNB, typename L = CholLay<S>>
 __device__ __forceinline__ bool cholb_core(unsigned char* __restrict__ smem, CholbShared<MAXNB>& sh, const double* __restrict__ E, const int n,
                                            double (&c0)[CholbPre<MAXNB>::U0][2], double (&c1)[CholbPre<MAXNB>::U1][2], const int (&rc1)[CholbPre<MAXNB>::U1],
-                                           const S tau, long long* __restrict__ dbg, int& nstamp) {
+                                           const S tau, long long* __restrict__ dbg, int& nstamp,
+                                           CholbImgRegs<MAXNB, L::LD>* __restrict__ img = nullptr) {
 #define CHOL_STAMP() do { if (dbg && threadIdx.x == 0) dbg[nstamp] = clock64(); ++nstamp; } while (0)
   using Pre = CholbPre<MAXNB>;
   constexpr int BPR = Pre::BPR, U0 = Pre::U0, TREM = Pre::TREM, U1 = Pre::U1;
@@ -340,7 +372,35 @@ __device__ __forceinline__ bool cholb_core(unsigned char* __restrict__ smem, Cho
     if (I >= n || J + 1 >= n) v1 = (I == J + 1) ? 1.0 : 0.0;
   };
   if (tid < n16) s_y[tid] = (S)sh.x[tid];
-  if constexpr (PREFETCHED) {
+  if constexpr (LOAD == 2) {
+    using Im = CholbImg<MAXNB, L::LD>;
+    float4* Lb4 = reinterpret_cast<float4*>(smem);
+#pragma unroll
+    for (int u = 0; u < Im::R0; ++u) {
+      const int e = tid + CHOLB_LDS_THREADS * u;
+      if (e < nb * Im::F4B) {
+        const int r = e / Im::F4B, w = e - r * Im::F4B;
+        float4 v = img->q0[u];
+        const int dg = (r == 0) ? cholb_img_diag<L::LD>(w) : 0;
+        if (dg) cholb_img_patch(v, dg >> 8, s_a0[(dg & 255) - 1]);
+        Lb4[(r * (r + 1) / 2) * Im::F4B + w] = v;
+      }
+    }
+    lds_barrier();                 // (LDS only: the other blocks' loads stay in flight behind the first tile's factorisation)
+    CHOL_STAMP();
+    if (wid > 0) {
+#pragma unroll
+      for (int u = 0; u < Im::R1; ++u) {
+        const int e = (tid - 64) + Im::TREM * u;
+        if (e < (nblk - nb) * Im::F4B) {
+          const int m = img->m1[u], g = (m >> 16) & 0x1ff;
+          float4 v = img->q1[u];
+          if (g) cholb_img_patch(v, (m >> 28) & 3, s_a0[g - 1]);
+          Lb4[m & 0xffff] = v;
+        }
+      }
+    }
+  } else if constexpr (LOAD == 1) {
 #pragma unroll
     for (int u = 0; u < U0; ++u) fix((BPR * u + s4) * CB + ii0, 2 * jp0, c0[u][0], c0[u][1]);
     {
@@ -570,15 +630,20 @@ __device__ __forceinline__ bool cholb_core(unsigned char* __restrict__ smem, Cho
 // factorisation is almost always followed by a refused f64 one (S carries the 1e-7 rounding of its f32 products either way,
 // tools/chol_f32_model.py), so the repeat costs little; for a caller that hands sba_lm_solve_trial an arbitrary system it is what
 // keeps the answer right (tests/test_gpu_cholesky.py: condition 1e9).
-template <typename T, int MAXNB = CHOLB_MAX_NB, int LD32 = 20>
+// IMG (fp32 engine with use_f32, the library's own single-rank loop): the f32 attempt copies k_build_exchange's image `img` of the
+// undamped system instead of narrowing E's doubles; the damped diagonal comes from E in f64 as before, one entry per thread, so
+// every float that reaches the LDS is the one the other instance puts there.  The f64 repeat still reads E.
+template <typename T, int MAXNB = CHOLB_MAX_NB, int LD32 = 20, bool IMG = false>
 __global__ __launch_bounds__(CHOLB_LDS_THREADS) void k_cholesky_blocked(
     const double* __restrict__ E /* summed exchange buffer [S | rhs | diagU | gc | cost] */, int C,
     LMState* __restrict__ st, double* __restrict__ D2c, const ParamSets<T> ps,
     double* __restrict__ delta_c, int n_sys /* size of the system in E: 11*C, or fewer when cameras share parameters */,
     const int32_t* __restrict__ tie /* [11*C] camera parameter -> system row, or NULL = identity */,
     const int32_t* __restrict__ first /* [n_sys] system row -> one camera parameter mapped to it, or NULL */,
-    long long* __restrict__ dbg /* optional cycle stamps (diagnostic runs only) */, int use_f32, float tau32) {
+    long long* __restrict__ dbg /* optional cycle stamps (diagnostic runs only) */, int use_f32, float tau32,
+    const float* __restrict__ img /* IMG: [block triangle as CholLay<float, LD32> lays it out], else unused */) {
   extern __shared__ __align__(16) unsigned char smem[];
+  static_assert(!IMG || std::is_same<T, float>::value, "the f32 image exists for the fp32 engine only");
   // fp32 engine, f64 factorisation: the pivot 1/sqrt(a_kk) is the hardware estimate (5e-8 relative) without the Newton step.  L_kk = a_kk piv
   // and the column scaled by the same piv factor a matrix whose row/column k differ from A's by 1e-7 relative -- the size
   // of the rounding error every entry of S already carries there -- and four dependent f64 operations leave each of the
@@ -601,7 +666,19 @@ __global__ __launch_bounds__(CHOLB_LDS_THREADS) void k_cholesky_blocked(
   auto addr = [&](int I, int J) { return E + (size_t)min(I, nlast) * n + min(J, nlast - 1 + (pair_ok ? 0 : 1)); };
   const int s4 = tid >> 7, ii0 = (tid >> 3) & 15, jp0 = tid & 7;
   const int tclamp = min(tid, nlast);
-  if (pair_ok) {
+  using Im = CholbImg<MAXNB, LD32>;
+  CholbImgRegs<MAXNB, LD32> ir;
+  const float4* img4 = reinterpret_cast<const float4*>(img);
+  const int nb_ = (n + CB - 1) / CB;
+  if constexpr (IMG) {
+    // the image's pieces of the first block column (all loads unconditional, clamped to the last piece there is)
+#pragma unroll
+    for (int u = 0; u < Im::R0; ++u) {
+      const int e = min(tid + CHOLB_LDS_THREADS * u, nb_ * Im::F4B - 1);
+      const int r = e / Im::F4B;
+      ir.q0[u] = img4[(r * (r + 1) / 2) * Im::F4B + (e - r * Im::F4B)];
+    }
+  } else if (pair_ok) {
 #pragma unroll
     for (int u = 0; u < U0; ++u) {
       const double2 t = *reinterpret_cast<const double2*>(addr((BPR * u + s4) * CB + ii0, 2 * jp0));
@@ -616,12 +693,27 @@ __global__ __launch_bounds__(CHOLB_LDS_THREADS) void k_cholesky_blocked(
   }
   double in_d = D2c[tclamp], in_u = dU[tclamp], in_r = rhs[tclamp];
   const double my_g = (tid < n) ? gct[tid] : 0.0;
+  double in_e = 0.0;                                               // IMG: the thread's diagonal entry of S, in f64
+  if constexpr (IMG) in_e = E[(size_t)tclamp * n + tclamp];
   // ... and so are the other 55 blocks, column by column (waves 1..7; the factorisation of the first tile does not wait for them).
   // Block k of that list sits in column cc, row cc + (k - base); k grows with the load round, so the search continues where it was.
   double c1[U1][2];
   int rc1[U1];                     // (row << 8) | column of the round's block: the LDS stores use it without a table lookup
-  {
-    const int nb_ = (n + CB - 1) / CB;
+  if constexpr (IMG) {
+    // the other blocks in LDS order: the k-th of them is block (rr, k - base + 1), base = rr (rr - 1) / 2, k + rr + 1 blocks into the triangle
+    const int last = max((nb_ * (nb_ + 1) / 2 - nb_) * Im::F4B - 1, 0);
+    int rr = 1, base = 0;
+#pragma unroll
+    for (int u = 0; u < Im::R1; ++u) {
+      const int e = min(max(tid - 64, 0) + Im::TREM * u, last);
+      const int k = e / Im::F4B, w = e - k * Im::F4B;
+      while (k >= base + rr && rr < nb_) { base += rr; ++rr; }
+      const int f = (k + rr + 1) * Im::F4B + w;
+      const int dg = (k - base + 1 == rr) ? cholb_img_diag<LD32>(w) : 0;
+      ir.m1[u] = f | (dg ? (((rr * CB + (dg & 255)) << 16) | ((dg >> 8) << 28)) : 0);
+      ir.q1[u] = img4[f];
+    }
+  } else {
     const int last = (nb_ * (nb_ + 1) / 2 - nb_) * 128 - 1;
     int cc = 1, base = 0;
 #pragma unroll
@@ -658,7 +750,9 @@ __global__ __launch_bounds__(CHOLB_LDS_THREADS) void k_cholesky_blocked(
   const bool fresh = st->fresh != 0;
   // operands of the epilogue, requested now so that their latency is hidden behind the factorisation
   const double my_cam = (tid < ncam) ? cams[tid] : 0.0;                       // camera parameter tid
-  const double my_xs = (tid < n) ? cams[first ? first[tid] : tid] : 0.0;      // system unknown tid (a shared one counts once)
+  // (IMG: never a tied system, so no tie / first maps -- a load of first[tid] here would have to be waited for with vmcnt(0), the
+  //  image's loads in flight behind it included, before the first barrier)
+  const double my_xs = (tid < n) ? cams[(!IMG && first) ? first[tid] : tid] : 0.0;      // system unknown tid (a shared one counts once)
 
   if (tid < nblk) {
     int r = 0;
@@ -684,19 +778,22 @@ __global__ __launch_bounds__(CHOLB_LDS_THREADS) void k_cholesky_blocked(
     }
     sh.x[tid] = in_r;
     sh.dd[tid] = dd;
+    // IMG: the damped diagonal as the f32 attempt wants it (cholb_core's s_a0), formed as the narrowing load forms it
+    if constexpr (IMG) (reinterpret_cast<float*>(smem) + nblk * L32::BS + n16)[tid] = (float)((tid < n ? in_e : 1.0) + dd);
   }
-  __syncthreads();
+  if constexpr (IMG) lds_barrier();          // (not __syncthreads: it would wait for the image's loads)
+  else __syncthreads();
   bool fail;
   if constexpr (MAXNB > CHOLB_MAX_NB) {
     // more than 176 unknowns: only the f32 triangle fits the LDS.  A refused factorisation raises LMState::chol_retry and leaves the
     // step to the f64 kernel launched behind this one (k_cholesky_ll with only_if_retry), which otherwise returns at once.
     static_assert(std::is_same<T, float>::value, "the 16-block-row kernel exists for the fp32 engine only");
-    fail = cholb_core<float, false, true, MAXNB, L32>(smem, sh, E, n, c0, c1, rc1, tau32, dbg, nstamp);
+    fail = cholb_core<float, false, IMG ? 2 : 1, MAXNB, L32>(smem, sh, E, n, c0, c1, rc1, tau32, dbg, nstamp, &ir);
     if (tid == 0) { st->chol_retry = fail ? 1 : 0; if (fail) st->chol_f64_retries += 1; }
     if (fail) return;                     // (block-uniform) nothing of the step has been written
   } else if constexpr (std::is_same<T, float>::value) {
-    if (use_f32) {
-      fail = cholb_core<float, false, true, MAXNB, L32>(smem, sh, E, n, c0, c1, rc1, tau32, dbg, nstamp);
+    if (use_f32 || IMG) {
+      fail = cholb_core<float, false, IMG ? 2 : 1, MAXNB, L32>(smem, sh, E, n, c0, c1, rc1, tau32, dbg, nstamp, &ir);
       if (fail) {                                 // refused: once more in f64, from E (sh.x still holds the right-hand side)
         __syncthreads();
         if (tid == 0) sh.fail = 0;
@@ -704,7 +801,7 @@ __global__ __launch_bounds__(CHOLB_LDS_THREADS) void k_cholesky_blocked(
         fail = cholb_core<double, true, false, MAXNB>(smem, sh, E, n, c0, c1, rc1, 0.0, dbg, nstamp);      // (refined pivots: this pass is about the answer, not the time)
         if (tid == 0) atomicAdd(&st->chol_f64_retries, 1);
       }
-    } else {
+    } else if constexpr (!IMG) {
       fail = cholb_core<double, PIV_NEWTON, true, MAXNB>(smem, sh, E, n, c0, c1, rc1, 0.0, dbg, nstamp);
     }
   } else {
@@ -714,7 +811,7 @@ __global__ __launch_bounds__(CHOLB_LDS_THREADS) void k_cholesky_blocked(
   __shared__ double s_cnew[CHOLB_LDS_THREADS]; // the trial cameras once more in LDS (one per thread: with shared intrinsics there are more camera
                                                // parameters than system rows -- 24 cameras tie to 195 unknowns but keep 264 parameters): the CamPre rebuild below reads them
   if (tid < ncam) {                                  // from there instead of waiting for its own global stores to come back
-    const double d = fail ? 0.0 : sh.x[tie ? tie[tid] : tid];
+    const double d = fail ? 0.0 : sh.x[(!IMG && tie) ? tie[tid] : tid];
     delta_c[tid] = d;
     cams_new[tid] = my_cam + d;
     s_cnew[tid] = my_cam + d;
@@ -749,9 +846,6 @@ __global__ __launch_bounds__(CHOLB_LDS_THREADS) void k_cholesky_blocked(
 // holds, to downdate the next panel.  A = damped matrix prepared by k_chol_prepare (full, symmetric, row-major),
 // sol = rhs in / solution out, so the kernel sits between the same prepare / epilogue kernels as the library path.
 constexpr int CS_MAX_NB = 32;
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt (its release fence cannot tell loads
-// from stores on gfx9), which would expose the latency of the global loads deliberately left in flight across it
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ inline size_t cs_blk(int r, int c) { return ((size_t)r * (r + 1) / 2 + c) * (CB * CB); }
 
 __global__ __launch_bounds__(CHOLB_THREADS) void k_cholesky_stream(

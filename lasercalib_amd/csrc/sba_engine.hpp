@@ -319,6 +319,12 @@ struct Engine : EngineBase {
   int chol_yv_ext[2] = {0, 0};          // ... entries at the front of each copy of x that a launch may have left non-empty (launch_chol_big)
   DevBuf<unsigned> chol_dag_flags;      // k_chol_big_dag: Mimg_j / W(r,c) published (value = the launch's epoch)
   DevBuf<double> chol_Mimg;             // k_chol_big_dag: the factored diagonal blocks and their inverses, as they lie in LDS
+  // fp32 engine: f32 image of the reduced system in k_cholesky_blocked's LDS layout, written by k_build_exchange beside E_own in the
+  // library's own single-rank loop (row stride: chol_img_ld_of_route).  chol_img_ok: the image is the system in E_own -- form_reduced raises it when it
+  // passes the image and lowers it on every other call, which covers all other writers of E_own (the phase API, the multi-rank
+  // exchanges); a tied solve (k_tie_system) never uses it.
+  DevBuf<float> chol_img;
+  bool chol_img_ok = false;
   unsigned chol_dag_epoch = 0;
   bool card_shared = false;             // sba_ipc_attach found a peer rank's exchange area on THIS device (a rehearsal of N ranks on one card):
                                         // kernels whose workgroups wait for each other are then not used where a launch-per-step form exists
@@ -467,6 +473,9 @@ struct Engine : EngineBase {
     if constexpr (sizeof(T) == 4) {
       set_lds(&k_cholesky_blocked<T, 16, 20>, (14 * 15 / 2 * CB * 20 + 2 * 14 * CB) * sizeof(float));
       set_lds(&k_cholesky_blocked<T, 16, 17>, (16 * 17 / 2 * CB * 17 + 2 * 16 * CB) * sizeof(float));
+      set_lds(&k_cholesky_blocked<T, CHOLB_MAX_NB, 20, true>, (CHOLB_MAX_NB * (CHOLB_MAX_NB + 1) / 2 * CBS + 2 * CHOLB_MAX_NB * CB) * sizeof(double));
+      set_lds(&k_cholesky_blocked<T, 16, 20, true>, (14 * 15 / 2 * CB * 20 + 2 * 14 * CB) * sizeof(float));
+      set_lds(&k_cholesky_blocked<T, 16, 17, true>, (16 * 17 / 2 * CB * 17 + 2 * 16 * CB) * sizeof(float));
     }
     set_lds(&k_cholesky_stream, 150 * 1024);
     set_lds(&k_cholesky_ll<T>, CLL_LDS_BYTES);
@@ -797,6 +806,13 @@ struct Engine : EngineBase {
     bpart.alloc(std::max((size_t)ngroups * ksplit * GROUP_ROWS, rt.fused_wide ? (size_t)ksplit * WIDE_ROWS : (size_t)0));
     slabs.alloc(std::max((size_t)npairs * ksplit * GROUP_TILES * GROUP_TILES * 256, rt.fused_wide ? (size_t)ksplit * WIDE_SLOTS * 256 : (size_t)0));
     E_own.alloc((size_t)n * n + 3 * n + 1); scal_own.alloc(NSCAL); delta_c.alloc(n);
+    if constexpr (sizeof(T) == 4) {
+      // the largest triangle a one-workgroup f32 factorisation takes (16 block rows of 17-float rows; 14 of 20-float rows are fewer),
+      // whatever this upload's system: zero once -- n and the route, hence the layout, stay what they are until the next upload
+      chol_img.alloc((size_t)CLL_MAX_NB * (CLL_MAX_NB + 1) / 2 * CB * 17);
+      chol_img.zero(stream);
+    }
+    chol_img_ok = false;
     const int nres_blocks = (int)((M + PM_BLOCK - 1) / PM_BLOCK);
     const int nlinp = rt.nlinp;
     // (the one-group visibility masks are kept whenever they exist, also for routes that do not read them: sba_get_layout)
@@ -1635,9 +1651,18 @@ struct Engine : EngineBase {
   }
 
   int lm_form_reduced(double* E) override { return form_reduced(E, nullptr); }
-  int form_reduced(double* E, double* Pk) {
+  // row stride of the f32 image the untied system's factorisation would copy, 0 = that route takes none
+  int chol_img_ld_of_route() const {
+    if (sizeof(T) != 4 || !kn.chol_f32 || chol_img.n == 0) return 0;
+    const CholRoute route = chol_route<T>(n, n, kn, card_shared);
+    if (route == CholRoute::BLOCKED) return 20;
+    if (route == CholRoute::LL_F32) return (n + CB - 1) / CB <= 14 ? 20 : 17;
+    return 0;
+  }
+  int form_reduced(double* E, double* Pk, bool own_loop = false /* run_loop's single-rank iteration: E is E_own */) {
     if (!lm_active) { err = "sba_lm_begin has not been called"; return SBA_ERR_STATE; }
     poll_clean = false;
+    chol_img_ok = false;
     if (!bf3_path()) flush_decide();
     if (sq_mode()) {
       if (opts.mode == SBA_MODE_CAMS_ONLY_SQ)
@@ -1661,9 +1686,13 @@ struct Engine : EngineBase {
       const int nblocks = (fc ? 4 * nt_launch * np_arg + (n + 15) / 16 : 0) + 1;
       // slab tiles: 3 = the wide kernels' compact rows, 1 = parameter-major (the bf16 kernels), 0 = camera-major
       const int emajor_mode = wide ? 3 : ((fused() && sizeof(T) == 4) || pairs_bf3()) ? 1 : 0;
+      // the f32 image for the factorisation: the library's own single-rank loop only, and not for a tied solve
+      const int img_ld = (own_loop && !multi() && !Pk && E == E_own.p && fc && opts.mode != SBA_MODE_SHARED_INTR) ? chol_img_ld_of_route() : 0;
       hipLaunchKernelGGL(k_build_exchange<T>, dim3(nblocks), dim3(1024), 0, stream, slabs.p, bpart.p, rt.ksplit, pair_ga.p,
                          pair_gb.p, np_arg, U.p, gc.p, cost_part.p, n_lin_parts(), C, fc, E, d_state.p,
-                         (fused() || rt.pairs_fold_u) ? gdpart.p : (const double*)nullptr, Pk, emajor_mode, nt_launch);
+                         (fused() || rt.pairs_fold_u) ? gdpart.p : (const double*)nullptr, Pk, emajor_mode, nt_launch,
+                         img_ld ? chol_img.p : (float*)nullptr, img_ld);
+      chol_img_ok = img_ld != 0;
     }
     prof_end(KP_REDUCE);
     return SBA_OK;
@@ -1757,6 +1786,9 @@ struct Engine : EngineBase {
       const int32_t* first = tied ? tie_first.p : nullptr;
       const int nb = (n_sys + CB - 1) / CB;
       const CholRoute route = chol_route<T>(n_sys, n, kn, card_shared);
+      // the f32 image k_build_exchange left beside E_own (chol_img_ok: nothing has written E_own since)
+      const float* img = (chol_img_ok && !tied && E == E_own.p && chol_img_ld_of_route() != 0) ? chol_img.p : nullptr;
+      (void)img;
       switch (route) {
         case CholRoute::LL:
         case CholRoute::LL_F32: {
@@ -1770,12 +1802,20 @@ struct Engine : EngineBase {
             if (route == CholRoute::LL_F32) {
               if (nb <= 14) {
                 const size_t lds32 = ((size_t)(nb * (nb + 1) / 2) * CB * 20 + 2 * (size_t)nb * CB) * sizeof(float);
-                hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 20>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
-                                   ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau);
+                if (img)
+                  hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 20, true>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
+                                     ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau, img);
+                else
+                  hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 20>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
+                                     ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau, (const float*)nullptr);
               } else {
                 const size_t lds32 = ((size_t)(nb * (nb + 1) / 2) * CB * 17 + 2 * (size_t)nb * CB) * sizeof(float);
-                hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 17>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
-                                   ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau);
+                if (img)
+                  hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 17, true>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
+                                     ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau, img);
+                else
+                  hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 17>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
+                                     ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau, (const float*)nullptr);
               }
             }
           }
@@ -1806,9 +1846,18 @@ struct Engine : EngineBase {
         case CholRoute::BLOCKED: {
           const size_t lds = ((size_t)(nb * (nb + 1) / 2) * CBS + 2 * (size_t)nb * CB) * sizeof(double);
           if (chol_debug && chol_dbg.n == 0) { chol_dbg.alloc(64); }
-          hipLaunchKernelGGL(k_cholesky_blocked<T>, dim3(1), dim3(CHOLB_LDS_THREADS), lds, stream, Esys, C, d_state.p, D2c.p,
-                             ps_lm(), delta_c.p, n_sys, tie, first, chol_debug ? chol_dbg.p : nullptr, (sizeof(T) == 4 && kn.chol_f32) ? 1 : 0,
-                             kn.chol_f32_tau);
+          bool with_img = false;
+          if constexpr (sizeof(T) == 4) {
+            if (img) {
+              with_img = true;
+              hipLaunchKernelGGL((k_cholesky_blocked<T, CHOLB_MAX_NB, 20, true>), dim3(1), dim3(CHOLB_LDS_THREADS), lds, stream, Esys, C, d_state.p,
+                                 D2c.p, ps_lm(), delta_c.p, n_sys, tie, first, chol_debug ? chol_dbg.p : nullptr, 1, kn.chol_f32_tau, img);
+            }
+          }
+          if (!with_img)
+            hipLaunchKernelGGL(k_cholesky_blocked<T>, dim3(1), dim3(CHOLB_LDS_THREADS), lds, stream, Esys, C, d_state.p, D2c.p,
+                               ps_lm(), delta_c.p, n_sys, tie, first, chol_debug ? chol_dbg.p : nullptr, (sizeof(T) == 4 && kn.chol_f32) ? 1 : 0,
+                               kn.chol_f32_tau, (const float*)nullptr);
           if (chol_debug) {
             const std::vector<long long> st = read_stamps(chol_dbg, 64);
             fprintf(stderr, "[chol stamps, cycles] load %lld  chol0 %lld |", st[1] - st[0], st[2] - st[1]);
@@ -2042,7 +2091,7 @@ struct Engine : EngineBase {
       for (int b = 0; b < batch; ++b) {
         lm_linearize();
         if (!multi()) {
-          lm_form_reduced(E_own.p);
+          form_reduced(E_own.p, nullptr, true);
           lm_solve_trial(E_own.p, nullptr);
           lm_decide_async(nullptr, 1);
         } else if (ipc_on) {

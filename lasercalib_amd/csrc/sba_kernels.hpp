@@ -949,14 +949,27 @@ __device__ inline void schur_consume(const typename Cfg::elem* __restrict__ pla 
   }
 }
 
-template <typename Cfg, int V>
+// 16-byte write-through store (sc1): the line does not stay dirty in the L2 of the storing XCD, so the write-back of a kernel's
+// last megabytes happens while its other waves still compute instead of at the kernel boundary behind it.  (The trailing s_nop
+// keeps the next instruction off the data registers until the store has read them.)
+typedef float slab_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_wt_f4(float* p, float a, float b, float c, float d) {
+  const slab_f4 v = {a, b, c, d};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+}
+
+template <typename Cfg, int V, bool WT = false>
 __device__ inline void schur_store(typename Cfg::elem* __restrict__ slab, int lane,
                                    const typename Mfma<typename Cfg::elem>::acc_t (&acc)[Cfg::TPW]) {
   constexpr int LO = schur_lo(Cfg::NTILE, Cfg::NV, V), HI = schur_lo(Cfg::NTILE, Cfg::NV, V + 1);
 #pragma unroll
   for (int t = LO; t < HI; ++t) {
+    if constexpr (WT) {
+      store_wt_f4(slab + (size_t)t * 256 + lane * 4, acc[t - LO][0], acc[t - LO][1], acc[t - LO][2], acc[t - LO][3]);
+    } else {
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg) slab[(size_t)t * 256 + lane * 4 + rg] = acc[t - LO][rg];      // one dwordx4 store per tile (f32)
+      for (int rg = 0; rg < 4; ++rg) slab[(size_t)t * 256 + lane * 4 + rg] = acc[t - LO][rg];      // one dwordx4 store per tile (f32)
+    }
   }
 }
 
@@ -970,12 +983,12 @@ __device__ inline void schur_consume_v(int v, const typename Cfg::elem* pla, con
     else schur_consume_v<Cfg, K, PARTIAL, V + 1>(v, pla, plb, acc, usedA, usedB);
   }
 }
-template <typename Cfg, int V = 0>
+template <typename Cfg, int V = 0, bool WT = false /* write-through stores (f32 slabs of the one-launch kernels) */>
 __device__ inline void schur_store_v(int v, typename Cfg::elem* slab, int lane,
                                      const typename Mfma<typename Cfg::elem>::acc_t (&acc)[Cfg::TPW]) {
   if constexpr (V < Cfg::NV) {
-    if (v == V) schur_store<Cfg, V>(slab, lane, acc);
-    else schur_store_v<Cfg, V + 1>(v, slab, lane, acc);
+    if (v == V) schur_store<Cfg, V, WT>(slab, lane, acc);
+    else schur_store_v<Cfg, V + 1, WT>(v, slab, lane, acc);
   }
 }
 
@@ -1893,7 +1906,7 @@ __global__ __launch_bounds__(SCHUR_THREADS) void k_schur_fused_bf3(
     });
     if (stamp_wg && threadIdx.x == NPROD) dbg[51] = clock64();
     T* slab = slabs + (size_t)blockIdx.x * (size_t)(GROUP_TILES * GROUP_TILES) * 256;
-    schur_store_v<Cfg>(cw, slab, lane, acc);
+    schur_store_v<Cfg, 0, true>(cw, slab, lane, acc);
     if (stamp_wg && threadIdx.x == NPROD) dbg[52] = clock64();
     if (ct < GROUP_ROWS) {
       const int c = ct / NCP, e = ct - c * NCP;

@@ -39,7 +39,13 @@ __global__ __launch_bounds__(1024) void k_build_exchange(
                                (bpart / gdpart) in the exchange buffer's own order with a stride of WIDE_ROWS */,
     int nt_launch = GROUP_TILES * GROUP_TILES /* tile slots per pair the grid covers: 121 with several pairs (an off-diagonal pair has
                            that many), the pair's own count -- 66, or the wide kernel's ntw (ntw + 1) / 2 -- when there is one pair: the
-                           220 workgroups of 16 waves that returned at once cost a third of the launch */) {
+                           220 workgroups of 16 waves that returned at once cost a third of the launch */,
+    float* __restrict__ img = nullptr /* fp32 engine, the library's own single-rank loop: the lower block triangle of S once more, as
+                           floats at the places k_cholesky_blocked's LDS layout gives them -- 16 x 16 blocks, block (r, c) at
+                           (r (r + 1) / 2 + c) * 16 * img_ld, rows img_ld floats apart (CholLay<float, img_ld>) -- so that kernel's load
+                           phase is a 16-byte copy.  Undamped; pad floats and the padded tail are never written (the buffer is
+                           zeroed when it is allocated) */,
+    int img_ld = 0) {
   using M_ = Mfma<T>;
   // tiles: 64 entries x 16 k-split groups per block (256-byte segments per group load; 16 entries x 64 groups was
   // measured slower: 64-byte segments, four times the blocks).  Rows: 16 rows x 64 groups, see below.
@@ -112,6 +118,17 @@ __global__ __launch_bounds__(1024) void k_build_exchange(
       double v = -s;                 // fused linearisation: the slabs already hold (Schur partials - U)
       if (!gdpart && ci_ == cj_) v += U[(size_t)ci_ * NCP * NCP + (i - ci_ * NCP) * NCP + (j - cj_ * NCP)];
       const bool sym_tile = diag && R == Tc;          // the tile holds both (i, j) and (j, i)
+      // (v + 0.0: the factorisation's narrowing load adds the entry's damping, 0.0 off the diagonal, before it narrows -- a -0.0,
+      //  which is what an entry without observations is here, becomes +0.0 on that way, and the image holds the same float)
+      const float vf = (float)(v + 0.0);
+      auto img_put = [&](int I, int J) {
+        const int br = I >> 4, bc = J >> 4;
+        if (br >= bc) img[((size_t)(br * (br + 1) / 2 + bc) * 16 + (I & 15)) * img_ld + (J & 15)] = vf;
+      };
+      if (img && (!emajor || !sym_tile || i <= j)) {
+        img_put(i, j);
+        if (emajor || !sym_tile) img_put(j, i);
+      }
       if (!emajor) {
         // camera-major tiles: a symmetric tile is panel^T panel with the SAME fragments on both sides, bitwise symmetric by itself
         E[(size_t)i * n + j] = v;

@@ -448,7 +448,7 @@ __global__ __launch_bounds__(SCHUR_THREADS) void k_schur_fused_wide(
         float4* pt = slab4 + LO * 64;
         static_for<LO, HI>([&](auto tc) {
           constexpr int t = decltype(tc)::value;
-          *pt = make_float4(acc[t - LO][0], acc[t - LO][1], acc[t - LO][2], acc[t - LO][3]);     // [tile][lane][reg]
+          store_wt_f4(reinterpret_cast<float*>(pt), acc[t - LO][0], acc[t - LO][1], acc[t - LO][2], acc[t - LO][3]);     // [tile][lane][reg], write-through
           pt += 64;
           asm volatile("" : "+v"(pt));
         });
