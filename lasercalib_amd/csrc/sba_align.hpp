@@ -372,9 +372,7 @@ int align_run(const AlignIn<T>& in, const sba_align_opts& opt, const double* tar
   const int nbc = target_centres ? (C + ALN_BLOCK - 1) / ALN_BLOCK : 0;
   const int nb = nbp + nbc;
   if (nb == 0) { err = "sba_align: fewer than 3 correspondences are in use (no targets given)"; return SBA_ERR_INVALID; }
-  hipEvent_t ev[4] = {};
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 4; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } evg{ev};
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  DevEvents<4> ev;
   DevBuf<double> d_tp, d_pw, d_tc, d_cw, part, tot;
   auto up = [&](DevBuf<double>& b, const double* src, size_t cnt) {
     if (!src || !cnt) return;
@@ -414,9 +412,7 @@ int align_run(const AlignIn<T>& in, const sba_align_opts& opt, const double* tar
   HIPCHK(hipMemcpyAsync(h + ALN_TOT3, tot.p + ALN_TOT3, sizeof(double) * (ALN_TOT - ALN_TOT3), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (rep) {
-    float m0 = 0.f, m1 = 0.f;
-    HIPCHK(hipEventElapsedTime(&m0, ev[0], ev[1]));
-    HIPCHK(hipEventElapsedTime(&m1, ev[2], ev[3]));
+    const float m0 = ev.ms(0, 1), m1 = ev.ms(2, 3);
     *rep = sba_align_report{};
     rep->scale = sim.s;
     for (int k = 0; k < 9; ++k) rep->R[k] = sim.R[k];

@@ -180,6 +180,22 @@ struct DevBuf {
   void zero(hipStream_t s) { if (n) HIPCHK(hipMemsetAsync(p, 0, n * sizeof(U), s)); }
 };
 
+// N timing events of one call: created together, the created ones destroyed with the scope (a HIPCHK that throws included)
+template <int N>
+struct DevEvents {
+  hipEvent_t e[N] = {};
+  DevEvents() {
+    try { for (auto& x : e) HIPCHK(hipEventCreate(&x)); }
+    catch (...) { release(); throw; }
+  }
+  ~DevEvents() { release(); }
+  DevEvents(const DevEvents&) = delete;
+  DevEvents& operator=(const DevEvents&) = delete;
+  void release() { for (auto& x : e) if (x) { (void)hipEventDestroy(x); x = nullptr; } }
+  hipEvent_t operator[](int i) const { return e[i]; }
+  float ms(int i, int j) const { float m = 0.f; HIPCHK(hipEventElapsedTime(&m, e[i], e[j])); return m; }     // after a synchronisation
+};
+
 // host-side layout loops over the observation list: a handful of threads once the list is long enough to pay for them
 template <typename F>
 void par_for(int64_t n, F&& f /* (lo, hi, thread) */) {

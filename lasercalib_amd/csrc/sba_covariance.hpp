@@ -589,9 +589,7 @@ int cov_run(const CovIn<T>& in, const sba_cov_opts& opt, double* cam_full, doubl
   const int npad = (n + COV_NB - 1) / COV_NB * COV_NB, nt = npad / COV_NB, ld = npad;
   const bool need_cams = !cams_fixed && (cam_full || cam_blocks || pt_cov);
   if (need_cams && npad > 256 * COV_INV_Q) { err = "sba_covariance: too many camera parameters"; return SBA_ERR_UNSUPPORTED; }
-  hipEvent_t ev[4];
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 4; ++k) (void)hipEventDestroy(e[k]); } } evg{ev};
+  DevEvents<4> ev;
   // ---- host prelude (part of seconds_total, not of the device phases): the layout, the anchors and the gauge basis
   std::vector<int32_t> ci((size_t)M), ps((size_t)N + 1);
   std::vector<unsigned char> fx(in.fixed ? N : 0);
@@ -716,8 +714,7 @@ int cov_run(const CovIn<T>& in, const sba_cov_opts& opt, double* cam_full, doubl
   if (need_cams && cam_full)        // X is symmetric: its column-major rows are the row-major rows
     HIPCHK(hipMemcpy2DAsync(cam_full, sizeof(double) * n, X.p, sizeof(double) * ld, sizeof(double) * n, n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  float ms[3] = {0.f, 0.f, 0.f};
-  for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+  const float ms[3] = {ev.ms(0, 1), ev.ms(1, 2), ev.ms(2, 3)};
   // the counts and sigma^2 decide the scale of every output
   int n_deg = 0;
   int64_t m_used = 0;

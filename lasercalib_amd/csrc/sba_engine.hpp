@@ -2237,12 +2237,24 @@ struct Engine : EngineBase {
     return SBA_OK;
   }
 
-  // ------------------------------------------------------------------ parameter covariance (sba_covariance.hpp)
-  int covariance(const sba_cov_opts* o, double* cam_full, double* cam_blocks, double* pt_cov, sba_cov_report* rep) override {
+  // ------------------------------------------------------------------ calls beside the LM loop, on the current parameters
+  // uploaded, single-rank and (refuse_lm_active) not between sba_lm_begin and sba_lm_finish; then the device is set and the stream idle
+  int aux_ready(const char* who, bool refuse_lm_active, const char* multi_note = "") {
     if (!uploaded) { err = "sba_upload has not been called"; return SBA_ERR_STATE; }
-    if (multi()) { err = "sba_covariance: a handle of a multi-rank job is not supported (sharded covariance)"; return SBA_ERR_UNSUPPORTED; }
+    if (multi()) { err = std::string(who) + ": a handle of a multi-rank job is not supported" + multi_note; return SBA_ERR_UNSUPPORTED; }
+    if (refuse_lm_active && lm_active) { err = std::string(who) + ": the handle is between sba_lm_begin and sba_lm_finish"; return SBA_ERR_STATE; }
     HIPCHK(hipSetDevice(device));
     sync();
+    return SBA_OK;
+  }
+  TriIn<T> tri_in() {          // what sba_triangulate.hpp and sba_unproject.hpp work on
+    return {stream, C, N, M, cams[cur].p, pts[cur].p, ptsT[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
+            blk_desc.p, nblk, has_fixed ? pt_fixed_mask.p : nullptr, identity_perm ? nullptr : perm.data()};
+  }
+
+  // ------------------------------------------------------------------ parameter covariance (sba_covariance.hpp)
+  int covariance(const sba_cov_opts* o, double* cam_full, double* cam_blocks, double* pt_cov, sba_cov_report* rep) override {
+    if (int rc = aux_ready("sba_covariance", false, " (sharded covariance)")) return rc;
     CovIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
                 has_fixed ? pt_fixed_mask.p : nullptr, RLoss<double>{loss_delta, loss_kind}};
     return cov_run<T>(in, *o, cam_full, cam_blocks, pt_cov, rep, err);
@@ -2251,33 +2263,19 @@ struct Engine : EngineBase {
   // ------------------------------------------------------------------ triangulation (sba_triangulate.hpp)
   int triangulate(const sba_tri_opts* o, double* points_out, int32_t* status_out, int32_t* n_views_out, double* rms_out,
                   double* max_out, double* spread_out, uint8_t* inlier_out, sba_tri_report* rep) override {
-    static_assert(MAX_CAMS <= 128, "k_tri_linear keeps the camera set of a point in two 64-bit words");
-    if (!uploaded) { err = "sba_upload has not been called"; return SBA_ERR_STATE; }
-    if (multi()) { err = "sba_triangulate: a handle of a multi-rank job is not supported"; return SBA_ERR_UNSUPPORTED; }
-    HIPCHK(hipSetDevice(device));
-    sync();
-    TriIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, ptsT[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
-                blk_desc.p, nblk, has_fixed ? pt_fixed_mask.p : nullptr, identity_perm ? nullptr : perm.data()};
-    return tri_run<T>(in, *o, points_out, status_out, n_views_out, rms_out, max_out, spread_out, inlier_out, rep, err);
+    if (int rc = aux_ready("sba_triangulate", false)) return rc;
+    return tri_run<T>(tri_in(), *o, points_out, status_out, n_views_out, rms_out, max_out, spread_out, inlier_out, rep, err);
   }
 
   // ------------------------------------------------------------------ similarity registration (sba_align.hpp)
-  int align_ready(const char* who) {
-    if (!uploaded) { err = "sba_upload has not been called"; return SBA_ERR_STATE; }
-    if (multi()) { err = std::string(who) + ": a handle of a multi-rank job is not supported"; return SBA_ERR_UNSUPPORTED; }
-    if (lm_active) { err = std::string(who) + ": the handle is between sba_lm_begin and sba_lm_finish"; return SBA_ERR_STATE; }
-    HIPCHK(hipSetDevice(device));
-    sync();
-    return SBA_OK;
-  }
   int align(const sba_align_opts* o, const double* target_points, const double* point_weights, const double* target_centres,
             const double* centre_weights, sba_align_report* rep) override {
-    if (int rc = align_ready("sba_align")) return rc;
+    if (int rc = aux_ready("sba_align", true)) return rc;
     AlignIn<T> in{stream, C, N, cams[cur].p, pts[cur].p, ptsT[cur].p, campre[cur].p};
     return align_run<T>(in, *o, target_points, point_weights, target_centres, centre_weights, rep, err);
   }
   int apply_similarity(double scale, const double* R, const double* t) override {
-    if (int rc = align_ready("sba_apply_similarity")) return rc;
+    if (int rc = aux_ready("sba_apply_similarity", true)) return rc;
     AlignIn<T> in{stream, C, N, cams[cur].p, pts[cur].p, ptsT[cur].p, campre[cur].p};
     return align_apply_run<T>(in, scale, R, t, err);
   }
@@ -2285,16 +2283,14 @@ struct Engine : EngineBase {
   // ------------------------------------------------------------------ points on known planes (sba_unproject.hpp)
   int unproject(const sba_unp_opts* o, const double* planes, int64_t n_planes, double* points_out, int32_t* status_out,
                 int32_t* n_views_out, double* rms_out, double* max_out, uint8_t* used_out, sba_unp_report* rep) override {
-    if (int rc = align_ready("sba_unproject")) return rc;
-    TriIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, ptsT[cur].p, uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pt_start.p,
-                blk_desc.p, nblk, has_fixed ? pt_fixed_mask.p : nullptr, identity_perm ? nullptr : perm.data()};
-    return unp_run<T>(in, *o, planes, n_planes, points_out, status_out, n_views_out, rms_out, max_out, used_out, rep, err);
+    if (int rc = aux_ready("sba_unproject", true)) return rc;
+    return unp_run<T>(tri_in(), *o, planes, n_planes, points_out, status_out, n_views_out, rms_out, max_out, used_out, rep, err);
   }
 
   // ------------------------------------------------------------------ reprojection diagnostics (sba_reproj.hpp)
   int reproj_stats(const sba_reproj_opts* o, double* cam_stats, int64_t* cam_hist, double* cam_grid, double* cam_radial,
                    double* pt_stats, double* err_out, int64_t* worst_idx, double* worst_err, sba_reproj_report* rep) override {
-    if (int rc = align_ready("sba_reproj_stats")) return rc;
+    if (int rc = aux_ready("sba_reproj_stats", true)) return rc;
     RpIn<T> in{stream, C, N, M, cams[cur].p, pts[cur].p, uv_cm.p, uv_pm.p, has_w ? w_cm.p : nullptr, has_w ? w_pm.p : nullptr,
                pi_cm.p, ci_pm.p, pi_pm.p, pt_start.p, chunk_cam.p, chunk_begin.p, chunk_end.p, cam_chunk_start.p, nchunk,
                identity_perm ? nullptr : perm.data()};

@@ -335,9 +335,7 @@ int rp_run(const RpIn<T>& in, const sba_reproj_opts& opt, double* cam_stats, int
   const int C = in.C, N = in.N, nchunk = in.nchunk;
   const int64_t M = in.M;
   const bool need_e = M > 0 && (err_out || pt_stats || want_worst);
-  hipEvent_t ev[4] = {};
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 4; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } evg{ev};
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  DevEvents<4> ev;
   DevBuf<double> campre, part, tot, grid_part, grid_tot, rad_part, rad_tot, e_pm, ptst, wval;
   DevBuf<unsigned long long> hist;
   DevBuf<int32_t> wpos;
@@ -424,7 +422,7 @@ int rp_run(const RpIn<T>& in, const sba_reproj_opts& opt, double* cam_stats, int
     fetch(h_val.data(), wval.p, sizeof(double) * h_val.size());
     fetch(&h_cnt, counter.p, sizeof h_cnt);
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&ms_worst, ev[2], ev[3]));
+    ms_worst = ev.ms(2, 3);
     if ((int64_t)h_cnt != cnt) { err = "sba_reproj_stats: the compaction disagrees with the histogram"; return SBA_ERR_HIP; }
     std::vector<int64_t> order((size_t)cnt);
     std::vector<int64_t> idx((size_t)cnt);
@@ -433,8 +431,7 @@ int rp_run(const RpIn<T>& in, const sba_reproj_opts& opt, double* cam_stats, int
     const int64_t keep = std::min<int64_t>(K, cnt);
     for (int64_t j = 0; j < keep; ++j) { w_idx.push_back(idx[order[j]]); w_err.push_back(h_val[order[j]]); }
   }
-  float ms_main = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms_main, ev[0], ev[1]));
+  const float ms_main = ev.ms(0, 1);
   // ---- outputs
   for (int c = 0; c < C; ++c) {
     const double* r = h_tot.data() + (size_t)c * RP_REC;

@@ -6,13 +6,16 @@
 //
 // Pipeline (one stream, one synchronisation at the end):
 //   k_tri_cam_prep    one thread per camera: R, centre -R^T t, t and the intrinsics into a table of TRI_CAM doubles per camera
-//   k_tri_linear      workgroup b owns the whole points of blk_desc[b] and their observations (<= 256, one per thread: the reads
+//   k_ray_fit<TriFit> workgroup b owns the whole points of blk_desc[b] and their observations (<= 256, one per thread: the reads
 //                     of uv_pm / ci_pm / w_pm are coalesced): ray terms into LDS, segmented sums per point, one thread per point
 //                     solves the 3 x 3 system, the observation threads project the estimate back, a second per-point pass
 //                     takes max / sum of squares / minimum depth; points whose largest error exceeds trim_px go on a work list
 //   k_tri_trim        one wave per listed point, lanes over the leave-one-out candidates
 //   k_tri_scatter     per-observation flags from the layout's order to the caller's
 //   k_tri_write_back  opts->write_back: the estimates of the OK points into the handle's current points
+// k_ray_fit is the kernel of every per-point ray fit: the skeleton holds the summation order, the shuffled-equals-sorted rule and
+// the duplicate-camera pass, a small policy struct what the fit does with the sums (TriFit here, UnpFit in sba_unproject.hpp).
+// RayFitJob is the host side the entries share; an entry point is a policy plus its own *_run.
 #pragma once
 #include "sba_kernels.hpp"
 
@@ -21,7 +24,7 @@ using namespace sba_host;
 
 constexpr int TRI_CAM = 23;          // doubles per camera in the table (odd stride: rows of different cameras spread over the LDS banks)
 constexpr int TC_R = 0, TC_C = 9, TC_T = 12, TC_F = 15, TC_K1 = 16, TC_K2 = 17, TC_P1 = 18, TC_P2 = 19, TC_CX = 20, TC_CY = 21;
-constexpr int TRI_TERMS = 15;        // doubles per observation row in LDS (k_tri_linear lists the columns); odd stride
+constexpr int TRI_TERMS = 15;        // doubles per observation row in LDS (k_ray_fit lists the columns); odd stride
 constexpr int TRI_NEWTON_MAX = 20;
 constexpr unsigned char TRI_OBS_OUT = 0, TRI_OBS_IN = 1, TRI_OBS_UNUSABLE = 2, TRI_OBS_TRIMMED = 3;
 
@@ -144,16 +147,20 @@ __device__ __forceinline__ double tri_err(const double* __restrict__ cp, double 
   return sqrt(eu * eu + ev * ev);
 }
 
-struct TriOut {          // per-point outputs and the per-observation states (layout order), device pointers
+// the status values every fit shares (the other two are the fit's: ST_TOO_FEW, ST_DEGENERATE)
+constexpr int RAY_OK = SBA_TRI_OK, RAY_ANCHORED = SBA_TRI_ANCHORED, RAY_BEHIND = SBA_TRI_BEHIND;
+
+struct RayOut {          // per-point outputs and the per-observation states (layout order), device pointers
   double* X;             // N x 3
   int32_t *status, *n_views;
-  double *rms, *mx, *spread;
+  double *rms, *mx;
+  double* spread;        // NULL for a fit without it
   unsigned char* state;  // M, TRI_OBS_*
-  int32_t* list;         // points to trim
-  int32_t* cnt;          // [0] entries of list, [1] points that lost an observation
+  int32_t* list;         // points to trim, or NULL
+  int32_t* cnt;          // [0] entries of list, [1] points that lost an observation; NULL without list
 };
 
-// ------------------------------------------------------------------ steps 1-5 and 7 for every point, one launch
+// ------------------------------------------------------------------ steps 1-5 and 7 for every point, one launch (k_ray_fit)
 // Segmented reduction over the observations of every point of the workgroup: entry e (of ne) of point q is reduced over the
 // point's observations in the order s_ord and lands in s_term[row of the point's first observation][col0 + e].  One thread per
 // (point, entry) walks the point when the workgroup holds many points; with few points of many views H threads share a walk
@@ -196,15 +203,44 @@ __device__ __forceinline__ void tri_segmented(int tid, int npts, int ne, const s
   }
 }
 
-// columns of an observation's row in LDS: 0-5 A, 6-8 b, 9-11 direction, 12 usable (0 / 1), 13 first usable view of its camera
-// (0 / 1); after the solve columns 0, 1 of every row take the observation's error and depth, columns 2-4 of a point's first row
-// its estimate, columns 5-7 of that row the sum of squares, the maximum and the minimum depth
-template <typename T>
-__global__ void __launch_bounds__(PM_BLOCK) k_tri_linear(const double* __restrict__ tab, int C, const typename Vec2<T>::type* __restrict__ uv,
-                                                          const T* __restrict__ w, const int32_t* __restrict__ ci,
-                                                          const int32_t* __restrict__ pt_start, const int4* __restrict__ blk_desc,
-                                                          const unsigned char* __restrict__ fixed, const double* __restrict__ pts_held,
-                                                          int min_views, double trim_px, TriOut out) {
+// The fit of the triangulation: the point closest to the rays by tri_solve, the spread of the ray directions, and the work list
+// of the trimming.  A policy of k_ray_fit carries exactly these members (UnpFit of sba_unproject.hpp is the other one):
+//   NE, COL_USABLE, COL_FIRST   the summed columns of an observation's row and where the two flags sit among them
+//   DIRS                        the ray directions are stored (columns 9-11) and summed
+//   ST_TOO_FEW, ST_DEGENERATE   the status of a point seen by fewer than min_views cameras / whose solve fails
+//   examined(c)                 the observations of camera c take part at all
+//   solve(p, t, X0, X1, X2)     the estimate of point p from the sums t[0..5] = A, t[6..8] = b
+//   finish(p, solved, nuse, mx, t, out)   outputs of its own; solved: the point has an estimate (OK or BEHIND)
+struct TriFit {
+  static constexpr int NE = 14, COL_USABLE = 12, COL_FIRST = 13;
+  static constexpr bool DIRS = true;
+  static constexpr int ST_TOO_FEW = SBA_TRI_TOO_FEW, ST_DEGENERATE = SBA_TRI_DEGENERATE;
+  double trim_px;        // > 0: points whose largest error exceeds it go on out.list
+  __device__ __forceinline__ bool examined(int) const { return true; }
+  __device__ __forceinline__ bool solve(int, const double* __restrict__ t, double& X0, double& X1, double& X2) const {
+    return tri_solve(t, t + 6, X0, X1, X2);
+  }
+  __device__ __forceinline__ void finish(int p, bool solved, int nuse, double mx, const double* __restrict__ t, const RayOut& out) const {
+    double spread = __builtin_nan("");
+    if (solved) {
+      const double m0 = t[9] / nuse, m1 = t[10] / nuse, m2 = t[11] / nuse;
+      spread = 1.0 - (m0 * m0 + m1 * m1 + m2 * m2);
+      if (trim_px > 0.0 && !(mx <= trim_px)) out.list[atomicAdd(out.cnt, 1)] = p;
+    }
+    out.spread[p] = spread;
+  }
+};
+
+// columns of an observation's row in LDS: 0-5 A, 6-8 b, with Fit::DIRS 9-11 direction, Fit::COL_USABLE usable (0 / 1),
+// Fit::COL_FIRST first usable view of its camera (0 / 1); after the solve columns 0, 1 of every row take the observation's error
+// and depth, columns 2-4 of a point's first row its estimate, columns 5-7 of that row the sum of squares, the maximum and the
+// minimum depth (the sums of columns 9 and up stay: TriFit::finish reads the direction sum there)
+template <typename T, typename Fit>
+__global__ void __launch_bounds__(PM_BLOCK) k_ray_fit(const double* __restrict__ tab, int C, const typename Vec2<T>::type* __restrict__ uv,
+                                                       const T* __restrict__ w, const int32_t* __restrict__ ci,
+                                                       const int32_t* __restrict__ pt_start, const int4* __restrict__ blk_desc,
+                                                       const unsigned char* __restrict__ fixed, const double* __restrict__ pts_held,
+                                                       int min_views, Fit fit, RayOut out) {
   extern __shared__ __align__(16) unsigned char smem[];
   double* s_cam = reinterpret_cast<double*>(smem);                 // [C][TRI_CAM]
   __shared__ double s_term[PM_BLOCK * TRI_TERMS];
@@ -217,8 +253,9 @@ __global__ void __launch_bounds__(PM_BLOCK) k_tri_linear(const double* __restric
   for (int i = tid; i < C * TRI_CAM; i += PM_BLOCK) s_cam[i] = tab[i];
   for (int i = tid; i <= npts; i += PM_BLOCK) s_ps[i] = (short)(pt_start[p_lo + i] - o_lo);
   __syncthreads();
-  // ---- one observation per thread: its point (binary search in the point starts), its ray and the ray's terms
-  bool usable = false;
+  // ---- one observation per thread: its point (binary search in the point starts), its ray and the ray's terms; observations
+  // the fit does not examine (the other cameras of a reference-camera call) get no ray
+  bool usable = false, examined = false;
   double u = 0.0, v = 0.0;
   const double* cp = s_cam;
   int q = 0, qa = 0, qb = 0;
@@ -235,13 +272,14 @@ __global__ void __launch_bounds__(PM_BLOCK) k_tri_linear(const double* __restric
     qa = s_ps[q]; qb = s_ps[q + 1];
     u = (double)m.x; v = (double)m.y;
     cp = s_cam + c * TRI_CAM;
-    double d0, d1, d2;
-    usable = tri_ray(cp, u, v, d0, d1, d2) && ww != 0.0 && isfinite(ww);
+    examined = fit.examined(c);
+    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+    if (examined) usable = tri_ray(cp, u, v, d0, d1, d2) && ww != 0.0 && isfinite(ww);
     if (!usable) { d0 = 0.0; d1 = 0.0; d2 = 0.0; }
     double* t = s_term + tid * TRI_TERMS;
     tri_terms(cp, usable ? ww * ww : 0.0, d0, d1, d2, t);
-    t[9] = d0; t[10] = d1; t[11] = d2;
-    t[12] = usable ? 1.0 : 0.0;
+    if constexpr (Fit::DIRS) { t[9] = d0; t[10] = d1; t[11] = d2; }
+    t[Fit::COL_USABLE] = usable ? 1.0 : 0.0;
     s_cid[tid] = (short)c;
     s_use[tid] = usable ? 1 : 0;
   }
@@ -266,47 +304,48 @@ __global__ void __launch_bounds__(PM_BLOCK) k_tri_linear(const double* __restric
     const int c = s_cid[k];
     bool first = s_use[k] != 0;
     for (int j = tid - 1; first && j >= qa && s_cid[s_ord[j]] == c; --j) first = s_use[s_ord[j]] == 0;
-    s_term[k * TRI_TERMS + 13] = first ? 1.0 : 0.0;
+    s_term[k * TRI_TERMS + Fit::COL_FIRST] = first ? 1.0 : 0.0;
   }
   __syncthreads();
-  // ---- per point: the nine sums of A and b, the direction sum, the usable views and the distinct cameras
-  tri_segmented(tid, npts, 14, s_ps, s_ord, s_part, s_term, 0,
+  // ---- per point: the nine sums of A and b, the direction sum if there is one, the usable views and the distinct cameras
+  tri_segmented(tid, npts, Fit::NE, s_ps, s_ord, s_part, s_term, 0,
                 [&](int k, int e) { return s_term[k * TRI_TERMS + e]; }, [](int, double s, double x) { return s + x; },
                 [](int) { return 0.0; });
   __syncthreads();
-  // ---- one thread per point: the 3 x 3 solve
-  int st = SBA_TRI_TOO_FEW, nuse = 0;
-  double X0 = 0.0, X1 = 0.0, X2 = 0.0, ds0 = 0.0, ds1 = 0.0, ds2 = 0.0;
+  // ---- one thread per point: the fit's solve
+  int st = Fit::ST_TOO_FEW, nuse = 0;
+  double X0 = 0.0, X1 = 0.0, X2 = 0.0;
   const int p = p_lo + tid;
   const int pa = tid < npts ? (int)s_ps[tid] : 0, pb = tid < npts ? (int)s_ps[tid + 1] : 0;
   if (tid < npts) {
     const double nan = __builtin_nan("");
     double* t = s_term + pa * TRI_TERMS;
     int ncam = 0;
-    if (pb > pa) { nuse = (int)t[12]; ncam = (int)t[13]; }
+    if (pb > pa) { nuse = (int)t[Fit::COL_USABLE]; ncam = (int)t[Fit::COL_FIRST]; }
     if (fixed != nullptr && fixed[p] != 0) {
-      st = SBA_TRI_ANCHORED;
+      st = RAY_ANCHORED;
       X0 = pts_held[3 * (size_t)p]; X1 = pts_held[3 * (size_t)p + 1]; X2 = pts_held[3 * (size_t)p + 2];
     } else if (ncam < min_views) {
-      st = SBA_TRI_TOO_FEW; X0 = nan; X1 = nan; X2 = nan;
+      st = Fit::ST_TOO_FEW; X0 = nan; X1 = nan; X2 = nan;
     } else {
-      ds0 = t[9]; ds1 = t[10]; ds2 = t[11];
-      if (tri_solve(t, t + 6, X0, X1, X2)) st = SBA_TRI_OK;
-      else { st = SBA_TRI_DEGENERATE; X0 = nan; X1 = nan; X2 = nan; }
+      if (fit.solve(p, t, X0, X1, X2)) st = RAY_OK;
+      else { st = Fit::ST_DEGENERATE; X0 = nan; X1 = nan; X2 = nan; }
     }
     if (pb > pa) { t[2] = X0; t[3] = X1; t[4] = X2; }
     s_pst[tid] = (unsigned char)st;
   }
   __syncthreads();
-  // ---- observation threads: error and depth at the estimate, and the observation's state
+  // ---- observation threads: error and depth at the estimate, and the observation's state (one rule for every fit: an
+  // observation that was not examined is OUT, not UNUSABLE)
   if (tid < nobs) {
     const int pst = s_pst[q];
     const double* x = s_term + qa * TRI_TERMS + 2;
     double e = 0.0, z = __builtin_inf();
-    if (usable && pst == SBA_TRI_OK) e = tri_err(cp, x[0], x[1], x[2], u, v, z);
+    if (usable && pst == RAY_OK) e = tri_err(cp, x[0], x[1], x[2], u, v, z);
     s_term[tid * TRI_TERMS] = e;
     s_term[tid * TRI_TERMS + 1] = z;
-    out.state[o_lo + tid] = pst == SBA_TRI_ANCHORED ? TRI_OBS_IN : !usable ? TRI_OBS_UNUSABLE : pst == SBA_TRI_OK ? TRI_OBS_IN : TRI_OBS_OUT;
+    out.state[o_lo + tid] = pst == RAY_ANCHORED ? TRI_OBS_IN : (examined && !usable) ? TRI_OBS_UNUSABLE
+                            : (usable && pst == RAY_OK) ? TRI_OBS_IN : TRI_OBS_OUT;
   }
   __syncthreads();
   // ---- per point: sum of squares, maximum (NaN sticks) and minimum depth over the used observations
@@ -315,25 +354,24 @@ __global__ void __launch_bounds__(PM_BLOCK) k_tri_linear(const double* __restric
                 [](int f, double s, double x) { return f == 0 ? s + x : f == 1 ? ((s != s || x != x) ? __builtin_nan("") : fmax(s, x)) : fmin(s, x); },
                 [](int f) { return f == 2 ? __builtin_inf() : 0.0; });
   __syncthreads();
-  // ---- outputs; the work list of the trimming
+  // ---- outputs
   if (tid < npts) {
     const double nan = __builtin_nan("");
-    double rms = nan, mx = nan, spread = nan;
+    const double* t = s_term + pa * TRI_TERMS;
+    const bool solved = st == RAY_OK;
+    double rms = nan, mx = nan;
     int nv = 0;
-    if (st == SBA_TRI_OK) {
-      const double* t = s_term + pa * TRI_TERMS;
+    if (solved) {
       const double sq = t[5], zmin = t[7];
       mx = t[6];
       nv = nuse;
       rms = sqrt(sq / nuse);
-      const double m0 = ds0 / nuse, m1 = ds1 / nuse, m2 = ds2 / nuse;
-      spread = 1.0 - (m0 * m0 + m1 * m1 + m2 * m2);
-      if (zmin <= 0.0) st = SBA_TRI_BEHIND;
-      if (trim_px > 0.0 && !(mx <= trim_px)) out.list[atomicAdd(out.cnt, 1)] = p;
+      if (zmin <= 0.0) st = RAY_BEHIND;
     }
+    fit.finish(p, solved, nuse, mx, t, out);
     out.X[3 * (size_t)p] = X0; out.X[3 * (size_t)p + 1] = X1; out.X[3 * (size_t)p + 2] = X2;
     out.status[p] = st; out.n_views[p] = nv;
-    out.rms[p] = rms; out.mx[p] = mx; out.spread[p] = spread;
+    out.rms[p] = rms; out.mx[p] = mx;
   }
 }
 
@@ -360,7 +398,7 @@ template <typename T>
 __global__ void __launch_bounds__(64) k_tri_trim(const double* __restrict__ tab, const typename Vec2<T>::type* __restrict__ uv,
                                                   const T* __restrict__ w, const int32_t* __restrict__ ci,
                                                   const int32_t* __restrict__ pt_start, int min_views, int max_drop, double trim_px,
-                                                  TriOut out) {
+                                                  RayOut out) {
   __shared__ double s_d[PM_BLOCK * 3], s_om[PM_BLOCK], s_u[PM_BLOCK], s_v[PM_BLOCK], s_e[PM_BLOCK], s_z[PM_BLOCK];
   __shared__ short s_c[PM_BLOCK];
   __shared__ unsigned char s_use[PM_BLOCK];
@@ -519,6 +557,63 @@ struct TriIn {
   const int64_t* perm;            // host: layout position -> caller's index, or NULL for the identity
 };
 
+// The part of a ray-fit call that does not depend on the fit (tri_run and unp_run each hold one): the private buffers, the
+// permutation as int32, the launches either side of the entry's own work, and the status / state read-back with its counts.
+// The order of a call: fit(), [the entry's own launches], flags_and_write_back(), read_back() and the entry's own fetch()es,
+// hipStreamSynchronize, deliver().
+template <typename T>
+struct RayFitJob {
+  ArenaScope own{nullptr};          // private buffers: hipMalloc'd here, freed on return (the handle's arena stays as it was)
+  const TriIn<T>& in;
+  DevBuf<double> tab, X, rms, mx;
+  DevBuf<int32_t> status, nviews, perm32;
+  DevBuf<unsigned char> state, state_out;
+  std::vector<int32_t> p32, h_stat;                  // (p32: staging of the permutation, lives until the synchronisation at the end)
+  std::vector<unsigned char> h_state;
+  int64_t n_status[5] = {}, n_state[4] = {};         // deliver(): points per status (RAY_* / Fit::ST_*), observations per TRI_OBS_*
+  explicit RayFitJob(const TriIn<T>& in_) : in(in_) {
+    const int N = in.N;
+    const int64_t M = in.M;
+    tab.alloc((size_t)in.C * TRI_CAM);
+    X.alloc((size_t)N * 3); rms.alloc(N); mx.alloc(N); status.alloc(N); nviews.alloc(N); state.alloc(M);
+    if (in.perm && M) {
+      p32.resize((size_t)M);
+      for (int64_t k = 0; k < M; ++k) p32[k] = (int32_t)in.perm[k];
+      perm32.upload(p32, in.stream);
+      state_out.alloc(M);
+    }
+  }
+  RayOut out(double* spread, int32_t* list, int32_t* cnt) const { return {X.p, status.p, nviews.p, rms.p, mx.p, spread, state.p, list, cnt}; }
+  template <typename Fit>
+  void fit(int min_views, const Fit& f, const RayOut& o) {           // the camera table and every point
+    hipLaunchKernelGGL(k_tri_cam_prep, dim3((in.C + 63) / 64), dim3(64), 0, in.stream, in.cams, tab.p, in.C);
+    if (in.nblk > 0)
+      hipLaunchKernelGGL((k_ray_fit<T, Fit>), dim3(in.nblk), dim3(PM_BLOCK), (size_t)in.C * TRI_CAM * sizeof(double), in.stream, tab.p, in.C,
+                         in.uv, in.w, in.ci, in.pt_start, in.blk_desc, in.fixed, (const double*)in.pts, min_views, f, o);
+    HIPCHK(hipGetLastError());
+  }
+  void flags_and_write_back(bool write_back) {
+    if (state_out.n)
+      hipLaunchKernelGGL(k_tri_scatter, dim3((unsigned)((in.M + 255) / 256)), dim3(256), 0, in.stream, state.p, perm32.p, in.M, state_out.p);
+    if (write_back && in.N > 0)
+      hipLaunchKernelGGL(k_tri_write_back<T>, dim3((3 * in.N + 255) / 256), dim3(256), 0, in.stream, X.p, status.p, in.N, in.pts, in.ptsT);
+    HIPCHK(hipGetLastError());
+  }
+  void fetch(void* dst, const void* src, size_t bytes) { if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, in.stream)); }
+  void read_back() {
+    h_stat.resize(in.N); h_state.resize((size_t)in.M);
+    fetch(h_stat.data(), status.p, sizeof(int32_t) * h_stat.size());
+    fetch(h_state.data(), state_out.n ? state_out.p : state.p, h_state.size());
+  }
+  // after the synchronisation: the counts, and the caller's status and in-the-estimate flags (either may be NULL)
+  void deliver(int32_t* status_out, uint8_t* in_out) {
+    for (int32_t s : h_stat) n_status[(uint32_t)s < 4 ? s : 4]++;
+    for (unsigned char s : h_state) if (s < 4) n_state[s]++;
+    if (status_out) std::copy(h_stat.begin(), h_stat.end(), status_out);
+    if (in_out) for (int64_t k = 0; k < in.M; ++k) in_out[k] = h_state[k] == TRI_OBS_IN ? 1 : 0;
+  }
+};
+
 template <typename T>
 int tri_run(const TriIn<T>& in, const sba_tri_opts& opt, double* points_out, int32_t* status_out, int32_t* n_views_out, double* rms_out,
             double* max_out, double* spread_out, uint8_t* inlier_out, sba_tri_report* rep, std::string& err) {
@@ -526,74 +621,44 @@ int tri_run(const TriIn<T>& in, const sba_tri_opts& opt, double* points_out, int
   if (opt.min_views < 2) { err = "sba_triangulate: min_views must be at least 2"; return SBA_ERR_INVALID; }
   if (!(opt.trim_px >= 0.0) || !std::isfinite(opt.trim_px)) { err = "sba_triangulate: trim_px must be finite and not negative"; return SBA_ERR_INVALID; }
   if (opt.max_drop < 0) { err = "sba_triangulate: max_drop must not be negative"; return SBA_ERR_INVALID; }
-  ArenaScope own(nullptr);          // private buffers: hipMalloc'd here, freed on return (the handle's arena stays as it was)
   hipStream_t st = in.stream;
-  const int C = in.C, N = in.N;
-  const int64_t M = in.M;
+  const int N = in.N;
   const bool trim = opt.trim_px > 0.0 && opt.max_drop > 0;
-  hipEvent_t ev[4];
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 4; ++k) (void)hipEventDestroy(e[k]); } } evg{ev};
-  DevBuf<double> tab, X, rms, mx, spread;
-  DevBuf<int32_t> status, nviews, list, cnt, perm32;
-  DevBuf<unsigned char> state, state_out;
-  tab.alloc((size_t)C * TRI_CAM);
-  X.alloc((size_t)N * 3); rms.alloc(N); mx.alloc(N); spread.alloc(N); status.alloc(N); nviews.alloc(N);
-  list.alloc(std::max(N, 1)); cnt.alloc(2); state.alloc(M);
+  RayFitJob<T> job(in);
+  DevEvents<4> ev;
+  DevBuf<double> spread;
+  DevBuf<int32_t> list, cnt;
+  spread.alloc(N); list.alloc(std::max(N, 1)); cnt.alloc(2);
   cnt.zero(st);
-  std::vector<int32_t> p32;                     // (staging of the permutation: lives until the synchronisation at the end)
-  if (in.perm && M) {
-    p32.resize((size_t)M);
-    for (int64_t k = 0; k < M; ++k) p32[k] = (int32_t)in.perm[k];
-    perm32.upload(p32, st);
-    state_out.alloc(M);
-  }
-  TriOut out{X.p, status.p, nviews.p, rms.p, mx.p, spread.p, state.p, list.p, cnt.p};
+  const RayOut out = job.out(spread.p, list.p, cnt.p);
   // ---- device phases: [ev0, ev1) camera table + every point, [ev1, ev2) trimming, [ev2, ev3) flags / write-back
   HIPCHK(hipEventRecord(ev[0], st));
-  hipLaunchKernelGGL(k_tri_cam_prep, dim3((C + 63) / 64), dim3(64), 0, st, in.cams, tab.p, C);
-  if (in.nblk > 0)
-    hipLaunchKernelGGL(k_tri_linear<T>, dim3(in.nblk), dim3(PM_BLOCK), (size_t)C * TRI_CAM * sizeof(double), st, tab.p, C, in.uv, in.w,
-                       in.ci, in.pt_start, in.blk_desc, in.fixed, (const double*)in.pts, (int)opt.min_views, trim ? opt.trim_px : 0.0, out);
-  HIPCHK(hipGetLastError());
+  job.fit((int)opt.min_views, TriFit{trim ? opt.trim_px : 0.0}, out);
   HIPCHK(hipEventRecord(ev[1], st));
   if (trim && N > 0)      // the length of the list stays on the device: a fixed grid strides over it
-    hipLaunchKernelGGL(k_tri_trim<T>, dim3(std::min(N, 2048)), dim3(64), 0, st, tab.p, in.uv, in.w, in.ci, in.pt_start,
+    hipLaunchKernelGGL(k_tri_trim<T>, dim3(std::min(N, 2048)), dim3(64), 0, st, job.tab.p, in.uv, in.w, in.ci, in.pt_start,
                        (int)opt.min_views, (int)opt.max_drop, opt.trim_px, out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ev[2], st));
-  if (state_out.n)
-    hipLaunchKernelGGL(k_tri_scatter, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, state.p, perm32.p, M, state_out.p);
-  if (opt.write_back && N > 0)
-    hipLaunchKernelGGL(k_tri_write_back<T>, dim3((3 * N + 255) / 256), dim3(256), 0, st, X.p, status.p, N, in.pts, in.ptsT);
-  HIPCHK(hipGetLastError());
+  job.flags_and_write_back(opt.write_back != 0);
   HIPCHK(hipEventRecord(ev[3], st));
-  // ---- read-back
-  std::vector<int32_t> h_stat(N);
-  std::vector<unsigned char> h_state((size_t)M);
+  // ---- read-back: the per-point arrays go straight into the caller's
   int32_t h_cnt[2] = {0, 0};
-  auto fetch = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); };
-  fetch(h_stat.data(), status.p, sizeof(int32_t) * N);
-  fetch(h_state.data(), state_out.n ? state_out.p : state.p, (size_t)M);
-  fetch(h_cnt, cnt.p, sizeof h_cnt);
-  fetch(points_out, X.p, sizeof(double) * 3 * N);
-  fetch(n_views_out, nviews.p, sizeof(int32_t) * N);
-  fetch(rms_out, rms.p, sizeof(double) * N);
-  fetch(max_out, mx.p, sizeof(double) * N);
-  fetch(spread_out, spread.p, sizeof(double) * N);
+  job.read_back();
+  job.fetch(h_cnt, cnt.p, sizeof h_cnt);
+  job.fetch(points_out, job.X.p, sizeof(double) * 3 * N);
+  job.fetch(n_views_out, job.nviews.p, sizeof(int32_t) * N);
+  job.fetch(rms_out, job.rms.p, sizeof(double) * N);
+  job.fetch(max_out, job.mx.p, sizeof(double) * N);
+  job.fetch(spread_out, spread.p, sizeof(double) * N);
   HIPCHK(hipStreamSynchronize(st));
-  float ms[3] = {0.f, 0.f, 0.f};
-  for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-  if (status_out) std::copy(h_stat.begin(), h_stat.end(), status_out);
-  if (inlier_out) for (int64_t k = 0; k < M; ++k) inlier_out[k] = h_state[k] == TRI_OBS_IN ? 1 : 0;
+  job.deliver(status_out, inlier_out);
   if (rep) {
+    const float ms[3] = {ev.ms(0, 1), ev.ms(1, 2), ev.ms(2, 3)};
     *rep = sba_tri_report{};
-    for (int p = 0; p < N; ++p) {
-      const int s = h_stat[p];
-      (s == SBA_TRI_OK ? rep->n_ok : s == SBA_TRI_ANCHORED ? rep->n_anchored : s == SBA_TRI_TOO_FEW ? rep->n_too_few
-       : s == SBA_TRI_DEGENERATE ? rep->n_degenerate : rep->n_behind)++;
-    }
-    for (int64_t k = 0; k < M; ++k) { rep->n_obs_unusable += h_state[k] == TRI_OBS_UNUSABLE; rep->n_obs_trimmed += h_state[k] == TRI_OBS_TRIMMED; }
+    rep->n_ok = job.n_status[SBA_TRI_OK]; rep->n_anchored = job.n_status[SBA_TRI_ANCHORED]; rep->n_too_few = job.n_status[SBA_TRI_TOO_FEW];
+    rep->n_degenerate = job.n_status[SBA_TRI_DEGENERATE]; rep->n_behind = job.n_status[SBA_TRI_BEHIND];
+    rep->n_obs_unusable = job.n_state[TRI_OBS_UNUSABLE]; rep->n_obs_trimmed = job.n_state[TRI_OBS_TRIMMED];
     rep->n_points_trimmed = h_cnt[1];
     rep->seconds_linear = ms[0] * 1e-3;
     rep->seconds_trim = ms[1] * 1e-3;

@@ -6,7 +6,7 @@ A rig is CxN:dtype[:visibility[:min_cams_per_point]]; every rig runs twice, as i
 1 % of its points and trim_px = 3.  linear_ms / trim_ms / device_ms: HIP-event times of the call's kernels (camera table + every
 point; the trimming of the listed points; both plus the flag scatter), taken after a warm-up call; wall_ms: the whole call
 (private buffers, read-back); residual_us: sba_time_kernel("residual") on the same handle, the existing streaming kernel with
-the same reads.  bytes: the algorithmic traffic of k_tri_linear from the shapes alone -- per observation 2 s + 4 read (+ s with
+the same reads.  bytes: the algorithmic traffic of k_ray_fit from the shapes alone -- per observation 2 s + 4 read (+ s with
 weights; s = 4 or 8, the handle's dtype) and 1 written (the flag), per point 24 written for X and 28 for the diagnostics -- and
 hbm_share: bytes / linear time as a share of the 8.0 TB/s HBM3E peak of the MI355X.
 """
