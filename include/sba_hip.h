@@ -578,7 +578,8 @@ int sba_reproj_stats(sba_handle* h, const sba_reproj_opts* opts /*NULL: all defa
  *              SPREAD (max_extent > 0 and max(xmax - xmin, ymax - ymin) + 1 > max_extent), else OK.
  * SPREAD is a one-pass stand-in for the "exactly one connected component" rule of the reference's older green_laser_finder
  * (feature_detection.py:24-40): a second blob or a reflection elsewhere in the frame stretches the bounding box and the frame
- * is rejected.  It is NOT connected-component labelling: two blobs closer than max_extent pass, one long streak does not.
+ * is rejected.  Two blobs closer than max_extent pass, one long streak does not: where that matters, sba_detect_blobs below
+ * applies the rule itself, with the reference's morphology and connected-component labelling.
  * Parity: cv.threshold(green, t, 255, 0) followed by cv.moments gives m00 = 255 n, m10 = 255 sum m x, m01 = 255 sum m y,
  * exact in float64 at these sizes, so the reference's int(m10 / m00), int(m01 / m00) are sum m x // n, sum m y // n.
  * frames: n_frames images of height rows of width pixels of `channels` bytes; row r of frame f starts at
@@ -608,6 +609,73 @@ int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t
                     const sba_dot_opts* opts /*NULL: {1, 50, 0, ...0}*/,
                     uint64_t* sums /*n_frames*12 or NULL*/, int32_t* box /*n_frames*4 or NULL*/,
                     double* centroid /*n_frames*4 or NULL*/, int32_t* status /*n_frames or NULL*/);
+
+/* ---------------------------------------------------------------- laser-dot detection by connected components
+ * The reference's careful detector, green_laser_finder (lasercalib/feature_detection.py:6-40, run per camera by
+ * lasercalib/centroid_finder.py): threshold the green channel, binary_dilation with disk(1), binary_closing with disk(4),
+ * measure.label, regionprops, and the centroid only when there is EXACTLY ONE connected component -- the rule that keeps
+ * reflections and second dots out of the calibration.  sba_detect_blobs does this for a batch of frames.  Stateless; frames are
+ * described as for sba_detect_dots (any pitch, any base, host memory or with frames_on_device device memory read in place).
+ * Per frame:
+ *   raw mask   raw = inside both regions and value > threshold (value = byte `channel` of the pixel), w = value - threshold.
+ *              The rectangle and the circle are those of sba_dot_opts, same clipping, same integer circle test.  They limit
+ *              the raw mask only: morphology and labelling run over the whole frame.
+ *   morphology dilation by disk(dilate_radius), then closing (dilation, then erosion) by disk(close_radius), with
+ *              disk(r) = {(dx, dy): dx^2 + dy^2 <= r^2} (skimage.morphology.disk).  A radius is 0..8; 0 skips its stage.
+ *              Outside the frame a dilation sees 0 and the erosion sees 1, so the closing is extensive and a dot at the image
+ *              border survives: skimage >= 0.23's default mode='ignore'.  Older skimage and scipy.ndimage.binary_closing
+ *              erode with a 0 border and wipe a dot within close_radius pixels of the edge; away from the border they agree.
+ *   components 8-connected components of the morphed mask (measure.label's default in 2-D), numbered 1, 2, ... in raster
+ *              order of their first pixel (the smallest y width + x): the numbering of measure.label and scipy.ndimage.label.
+ *   blobs      per component 12 exact unsigned 64-bit integers
+ *                [n, sum x, sum y, n_raw, sum w, sum w x, sum w y, n_sat, xmin, ymin, xmax, ymax]:
+ *              n, sum x, sum y and the box over the pixels of the MORPHED component (what regionprops(...).centroid averages);
+ *              n_raw, the w sums and n_sat (value == 255) over the RAW pixels inside it.  Every raw pixel lies in the morphed
+ *              mask, but a closing can create an island that holds no raw pixel: n_raw and sum w may be 0.
+ *              blobs[f] holds the first min(n_components[f], max_blobs) components in label order, the rest is zero;
+ *              n_components[f] is the true count.
+ *   accepted   a listed component is accepted when n >= min_area, (max_area == 0 or n <= max_area) and, with max_centre_dist > 0,
+ *              its centroid lies within that distance of (centre_x, centre_y), tested in exact integers:
+ *              (sum x - centre_x n)^2 + (sum y - centre_y n)^2 <= (max_centre_dist n)^2 -- the filter the reference carries
+ *              commented out (feature_detection.py:32-34, centroid_dist_thresh).
+ *   status     the first that applies: NONE (no component), OVERFLOW (n_components > max_blobs: the table is truncated and the
+ *              frame cannot be judged), REJECTED (no component accepted), MULTIPLE (two or more accepted), OK (exactly one).
+ *              With every filter off, OK is exactly when the reference returns a centroid.
+ *   accepted[f] = the 0-based table index of the single accepted component, or -1
+ *   centroid[f] = [sum x / n, sum y / n, sum w x / sum w, sum w y / sum w] of it, each ONE IEEE float64 division of the two
+ *              integers; NaN where the status is not OK, and in the last two where sum w == 0
+ *   mask_out   (diagnostic) n_frames * height * width bytes, 0 / 1: the morphed mask
+ *   labels_out (diagnostic) n_frames * height * width int32: 0 for background, else the component's number -- measure.label's
+ *              array; every component is numbered, those beyond max_blobs too
+ * Every output pointer is host memory and may be NULL.  n_frames = 0 returns SBA_OK and writes nothing.
+ * Frames are processed in chunks whose device scratch stays within a fixed budget (one frame is always allowed), host frames
+ * through two staging buffers as for sba_detect_dots; chunk_frames > 0 caps the frames of a chunk, host or device.
+ * Errors (checked before any device work, text in sba_last_error(NULL)): those of sba_detect_dots, and SBA_ERR_INVALID for a
+ *   radius outside 0..8, max_blobs outside 0..64, a negative area or distance limit.
+ * Determinism: every stored value is an integer merged with integer atomics; two calls return the same bits, and so does any
+ *   chunk_frames. */
+typedef enum { SBA_BLOB_OK = 0, SBA_BLOB_NONE = 1, SBA_BLOB_OVERFLOW = 2, SBA_BLOB_REJECTED = 3, SBA_BLOB_MULTIPLE = 4 } sba_blob_status;
+typedef struct {
+  int32_t channel;          /* interleaved channel that is thresholded; the reference: 1 (green of BGR)  */
+  int32_t threshold;        /* 0..255; a pixel counts when value > threshold; the reference: 70          */
+  int32_t frames_on_device; /* 1: `frames` is a device pointer on `device`                               */
+  int32_t dilate_radius;    /* 0..8; the reference: 1                                                    */
+  int32_t close_radius;     /* 0..8; the reference: 4                                                    */
+  int32_t max_blobs;        /* rows of a frame's table, 1..64; 0 = 8                                     */
+  int32_t min_area, max_area;   /* on n of a component; 0 = no limit                                     */
+  int32_t centre_x, centre_y, max_centre_dist;   /* pixels; max_centre_dist 0 = no limit                 */
+  int32_t roi_rect[4];      /* as sba_dot_opts; limits the raw mask only                                 */
+  int32_t roi_circle[3];    /* as sba_dot_opts; limits the raw mask only                                 */
+  int32_t chunk_frames;     /* frames per chunk at most; <= 0 = library default                          */
+  int32_t reserved[5];
+} sba_blob_opts;
+int sba_detect_blobs(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels /*1, 3 or 4*/,
+                     int64_t row_pitch /*bytes, >= width*channels*/, int64_t frame_pitch /*bytes, >= height*row_pitch*/,
+                     const sba_blob_opts* opts /*NULL: {1, 70, 0, 1, 4, 0...}*/,
+                     int32_t* n_components /*n_frames or NULL*/, uint64_t* blobs /*n_frames*max_blobs*12 or NULL*/,
+                     int32_t* accepted /*n_frames or NULL*/, double* centroid /*n_frames*4 or NULL*/,
+                     int32_t* status /*n_frames or NULL*/, uint8_t* mask_out /*n_frames*height*width or NULL*/,
+                     int32_t* labels_out /*n_frames*height*width or NULL*/);
 
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations

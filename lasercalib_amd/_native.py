@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = (
     "sba_lm_solve_trial", "sba_lm_decide", "sba_lm_decide_async", "sba_lm_poll", "sba_lm_run", "sba_lm_finish", "sba_lm_get_log", "sba_time_kernel", "sba_get_kernel_profile",
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
-    "sba_unproject_rows", "sba_unproject", "sba_detect_dots",
+    "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
 )
 
 
@@ -113,6 +113,20 @@ class DotOpts(C.Structure):
 
 DOT_OK, DOT_NONE, DOT_TOO_SMALL, DOT_TOO_LARGE, DOT_SPREAD = 0, 1, 2, 3, 4       # sba_dot_status
 DOT_MAX_DIM = 16384
+
+
+class BlobOpts(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("threshold", C.c_int32), ("frames_on_device", C.c_int32), ("dilate_radius", C.c_int32),
+                ("close_radius", C.c_int32), ("max_blobs", C.c_int32), ("min_area", C.c_int32), ("max_area", C.c_int32),
+                ("centre_x", C.c_int32), ("centre_y", C.c_int32), ("max_centre_dist", C.c_int32), ("roi_rect", C.c_int32 * 4),
+                ("roi_circle", C.c_int32 * 3), ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+BLOB_OK, BLOB_NONE, BLOB_OVERFLOW, BLOB_REJECTED, BLOB_MULTIPLE = 0, 1, 2, 3, 4       # sba_blob_status
+BLOB_NREC, BLOB_DEFAULT_BLOBS, BLOB_MAX_BLOBS, BLOB_MAX_RADIUS = 12, 8, 64, 8
+# geometry of the kernels (csrc/sba_blobs.hpp), for the tests that straddle it: rows of a morphology band, rows of a labelling
+# tile (a tile is one 64-pixel word wide), words of a morphology band
+BLOB_MORPH_ROWS, BLOB_TILE_ROWS, BLOB_MORPH_WORDS = 32, 32, 8
 
 
 class AlignOpts(C.Structure):
@@ -237,6 +251,23 @@ class LaserDots:
         with np.errstate(invalid="ignore", divide="ignore"):
             var = (self.sums[:, 3] / n - self.centroid[:, 0] ** 2) + (self.sums[:, 4] / n - self.centroid[:, 1] ** 2)
             return np.sqrt(np.maximum(var, 0.0))
+
+
+class LaserBlobs:
+    """Result of detect_blobs (sba_detect_blobs, include/sba_hip.h), one row per frame: ``n_components`` (B,) int32, the true
+    number of 8-connected components of the morphed mask; ``blobs`` (B, K, 12) uint64 -- of the first K = max_blobs components
+    in label order n, sum x, sum y, n_raw, sum w, sum w x, sum w y, n_sat, xmin, ymin, xmax, ymax (zero rows beyond);
+    ``accepted`` (B,) int32, the table index of the single accepted component or -1; ``centroid`` (B, 4) float64 -- binary x, y
+    of it (over the morphed pixels), then weighted x, y (over the raw ones); ``status`` (B,) int32 of BLOB_*; ``mask`` (B, H, W)
+    uint8 and ``labels`` (B, H, W) int32 when asked for, else None."""
+
+    def __init__(self, n_components, blobs, accepted, centroid, status, mask=None, labels=None):
+        self.n_components, self.blobs, self.accepted, self.centroid, self.status = n_components, blobs, accepted, centroid, status
+        self.mask, self.labels = mask, labels
+
+    @property
+    def ok(self):
+        return self.status == BLOB_OK
 
 
 class Alignment:
@@ -377,6 +408,9 @@ def load():
                                     C.POINTER(C.c_uint8), C.POINTER(UnpReport)]),
         "sba_detect_dots": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                       C.POINTER(DotOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "sba_detect_blobs": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                       C.POINTER(BlobOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
         "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
         "sba_reproj_stats": (C.c_int, [H, C.POINTER(ReprojOpts), dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(ReprojReport)]),
@@ -524,17 +558,9 @@ def unproject_rows(uv, cam_rows, planes=None, device=0):
     return out
 
 
-def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_extent=0, roi_rect=None, roi_circle=None,
-                chunk_frames=0, device=0):
-    """Thresholded image moments of a batch of frames (sba_detect_dots, include/sba_hip.h) -> LaserDots.
-
-    ``frames``: uint8, (B, H, W, C) with C in (1, 3, 4) or (B, H, W).  A numpy array is read where it is, in any layout whose
-    pixels are contiguous (channel stride 1, pixel stride C) and whose row and frame strides are large enough: the pitches are
-    its strides, nothing is copied on the host.  A torch tensor on ``device`` is handed over as a device pointer and read in
-    place.  ``channel`` is the thresholded byte of a pixel (the reference: 1, green of BGR), a pixel counts when its value is
-    above ``threshold``; ``roi_rect`` = (x0, y0, x1, y1) half-open, ``roi_circle`` = (cx, cy, r); ``min_area``, ``max_area``,
-    ``max_extent``: the status rules, 0 = no limit; ``chunk_frames``: host frames staged per copy, 0 = the library's default."""
-    lib = load()
+def _frame_layout(frames, device):
+    """(tensor?, B, H, W, C, row stride, frame stride) of a batch of uint8 frames, numpy or device tensor; ValueError when the
+    layout is not one the detectors read in place."""
     tensor = _is_tensor(frames)
     if tensor:
         if not frames.is_cuda or (frames.device.index or 0) != device:
@@ -562,6 +588,21 @@ def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_ext
     if (sc, sp) != (1, Cn) or sr < W * Cn or sf < H * sr:
         raise ValueError("frames: pixels must be contiguous (channel stride 1, pixel stride C), rows and frames in ascending order; "
                          f"got strides {tuple(strides)} for shape {tuple(shape)}")
+    return tensor, frames, B, H, W, Cn, sr, sf
+
+
+def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_extent=0, roi_rect=None, roi_circle=None,
+                chunk_frames=0, device=0):
+    """Thresholded image moments of a batch of frames (sba_detect_dots, include/sba_hip.h) -> LaserDots.
+
+    ``frames``: uint8, (B, H, W, C) with C in (1, 3, 4) or (B, H, W).  A numpy array is read where it is, in any layout whose
+    pixels are contiguous (channel stride 1, pixel stride C) and whose row and frame strides are large enough: the pitches are
+    its strides, nothing is copied on the host.  A torch tensor on ``device`` is handed over as a device pointer and read in
+    place.  ``channel`` is the thresholded byte of a pixel (the reference: 1, green of BGR), a pixel counts when its value is
+    above ``threshold``; ``roi_rect`` = (x0, y0, x1, y1) half-open, ``roi_circle`` = (cx, cy, r); ``min_area``, ``max_area``,
+    ``max_extent``: the status rules, 0 = no limit; ``chunk_frames``: host frames staged per copy, 0 = the library's default."""
+    lib = load()
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
     opts = DotOpts()
     opts.channel, opts.threshold, opts.frames_on_device = int(channel), int(threshold), 1 if tensor else 0
     opts.min_area, opts.max_area, opts.max_extent, opts.chunk_frames = int(min_area), int(max_area), int(max_extent), int(chunk_frames)
@@ -580,6 +621,47 @@ def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_ext
     _check(lib.sba_detect_dots(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts), sums.ctypes.data, box.ctypes.data,
                                centroid.ctypes.data, status.ctypes.data))
     return LaserDots(sums, box, centroid, status)
+
+
+def detect_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=4, max_blobs=BLOB_DEFAULT_BLOBS, min_area=0,
+                 max_area=0, centre=None, max_centre_dist=0, roi_rect=None, roi_circle=None, chunk_frames=0, device=0,
+                 want_mask=False, want_labels=False):
+    """Connected-component laser-dot detection of a batch of frames (sba_detect_blobs, include/sba_hip.h) -> LaserBlobs.
+
+    ``frames`` as for ``detect_dots``: uint8, (B, H, W, C) with C in (1, 3, 4) or (B, H, W), a numpy array read where it is or a
+    torch tensor on ``device`` read in place.  The raw mask (``channel`` above ``threshold`` inside ``roi_rect`` and
+    ``roi_circle``) is dilated by disk(``dilate_radius``) and closed by disk(``close_radius``), its 8-connected components are
+    numbered in raster order and the first ``max_blobs`` measured.  ``min_area``, ``max_area`` and ``max_centre_dist`` around
+    ``centre`` = (x, y) accept or reject a component (0 = no limit); the status is BLOB_OK when exactly one is accepted.
+    ``chunk_frames`` caps the frames per chunk, 0 = the library's choice; ``want_mask`` / ``want_labels`` return the morphed
+    mask and measure.label's array."""
+    lib = load()
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    opts = BlobOpts()
+    opts.channel, opts.threshold, opts.frames_on_device = int(channel), int(threshold), 1 if tensor else 0
+    opts.dilate_radius, opts.close_radius, opts.max_blobs = int(dilate_radius), int(close_radius), int(max_blobs)
+    opts.min_area, opts.max_area, opts.max_centre_dist, opts.chunk_frames = int(min_area), int(max_area), int(max_centre_dist), int(chunk_frames)
+    if centre is not None:
+        opts.centre_x, opts.centre_y = int(centre[0]), int(centre[1])
+    if roi_rect is not None:
+        opts.roi_rect = (C.c_int32 * 4)(*(int(v) for v in roi_rect))
+    if roi_circle is not None:
+        opts.roi_circle = (C.c_int32 * 3)(*(int(v) for v in roi_circle))
+    K = int(max_blobs) if 0 < int(max_blobs) <= BLOB_MAX_BLOBS else BLOB_DEFAULT_BLOBS
+    ncomp, blobs = np.zeros(B, np.int32), np.zeros((B, K, BLOB_NREC), np.uint64)
+    accepted, centroid, status = np.full(B, -1, np.int32), np.full((B, 4), np.nan), np.full(B, BLOB_NONE, np.int32)
+    mask = np.zeros((B, H, W), np.uint8) if want_mask else None
+    labels = np.zeros((B, H, W), np.int32) if want_labels else None
+    if tensor:
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # the frames are complete before the library reads them
+        ptr = frames.data_ptr()
+    else:
+        ptr = frames.ctypes.data
+    _check(lib.sba_detect_blobs(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts), ncomp.ctypes.data, blobs.ctypes.data,
+                                accepted.ctypes.data, centroid.ctypes.data, status.ctypes.data,
+                                None if mask is None else mask.ctypes.data, None if labels is None else labels.ctypes.data))
+    return LaserBlobs(ncomp, blobs, accepted, centroid, status, mask, labels)
 
 
 class Problem:

@@ -17,6 +17,9 @@ int sba_unproject_rows_ncp13(int device, int64_t n, const double* uv, const doub
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
                     int32_t* status);
+int sba_blobs_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                   int64_t row_pitch, int64_t frame_pitch, const sba_blob_opts& opts, int32_t* n_components, uint64_t* blobs,
+                   int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -396,6 +399,37 @@ int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t
   if (n_frames == 0) return SBA_OK;
   return guarded(nullptr, [&] {
     return sba_detect_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, sums, box, centroid, status);
+  });
+}
+
+int sba_detect_blobs(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                     int64_t row_pitch, int64_t frame_pitch, const sba_blob_opts* opts, int32_t* n_components, uint64_t* blobs,
+                     int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out) {
+  sba_blob_opts o{};
+  o.channel = 1; o.threshold = 70; o.dilate_radius = 1; o.close_radius = 4;
+  if (opts) o = *opts;
+  auto invalid = [](const char* what) { g_last_error = std::string("sba_detect_blobs: ") + what; return (int)SBA_ERR_INVALID; };
+  if (n_frames < 0 || height < 0 || width < 0) return invalid("negative size");
+  if (n_frames > 0 && !frames) return invalid("null frames");
+  if (channels != 1 && channels != 3 && channels != 4) return invalid("channels must be 1, 3 or 4");
+  if (o.channel < 0 || o.channel >= channels) return invalid("channel out of range");
+  if (o.threshold < 0 || o.threshold > 255) return invalid("threshold must be in 0..255");
+  if (o.dilate_radius < 0 || o.dilate_radius > 8 || o.close_radius < 0 || o.close_radius > 8) return invalid("a radius must be in 0..8");
+  if (o.max_blobs < 0 || o.max_blobs > 64) return invalid("max_blobs must be in 0..64");
+  if (o.min_area < 0 || o.max_area < 0 || o.max_centre_dist < 0) return invalid("negative area or distance limit");
+  if (row_pitch < (int64_t)width * channels) return invalid("row_pitch is smaller than width * channels");
+  if ((__int128)height * row_pitch > frame_pitch) return invalid("frame_pitch is smaller than height * row_pitch");
+  if ((__int128)n_frames * frame_pitch > INT64_MAX) return invalid("n_frames * frame_pitch overflows");
+  if (height > 16384 || width > 16384) {     // a pixel's index y W + x fits the 32-bit labels, every sum 64 bits
+    g_last_error = "sba_detect_blobs: width and height are limited to 16384";
+    return SBA_ERR_UNSUPPORTED;
+  }
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (n_frames == 0) return SBA_OK;
+  return guarded(nullptr, [&] {
+    return sba_blobs_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, n_components, blobs, accepted,
+                          centroid, status, mask_out, labels_out);
   });
 }
 

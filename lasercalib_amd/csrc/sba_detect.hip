@@ -1,9 +1,16 @@
-// sba_detect.hip -- the laser-dot detector's kernels (sba_detect.hpp).  They do not depend on the camera model, so they are
-// compiled once, in a translation unit of their own.
-#include "sba_detect.hpp"
+// sba_detect.hip -- the laser-dot detectors' kernels (sba_detect.hpp: moments; sba_blobs.hpp: connected components).  They do
+// not depend on the camera model, so they are compiled once, in a translation unit of their own.
+#include "sba_blobs.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
                     int32_t* status) {
   return sba_detect::dot_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, opts, sums, box, centroid, status);
+}
+
+int sba_blobs_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                   int64_t row_pitch, int64_t frame_pitch, const sba_blob_opts& opts, int32_t* n_components, uint64_t* blobs,
+                   int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out) {
+  return sba_detect::blob_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, opts, n_components, blobs,
+                               accepted, centroid, status, mask_out, labels_out);
 }

@@ -1,7 +1,7 @@
 // sba_detect.hpp -- sba_detect_dots (include/sba_hip.h): thresholded image moments of video frames, one laser dot per frame.
 // Stands in for green_laser_finder_faster (lasercalib/feature_detection.py:44-54: cv.threshold + cv.moments) and, through the
 // SPREAD status, for the "exactly one connected component" rule of green_laser_finder (:24-40) -- a one-pass stand-in on the
-// bounding box of the bright pixels, NOT connected-component labelling.
+// bounding box of the bright pixels; the rule itself, with morphology and labelling, is sba_detect_blobs (sba_blobs.hpp).
 //
 // Three kernels per chunk of frames: k_dot_init (sums = 0, box = [W, H, -1, -1]), k_dot_moments (the streaming reduction,
 // one workgroup per band of rows of one frame) and k_dot_finalize (one thread per frame: centroid and status).

@@ -5,6 +5,10 @@
 * :func:`find_laser_dots`           -- the batched call: many frames, one pass, exact integer moments -> ``LaserDots``
 * :func:`centroid_table`            -- the (n_frames, 2) array detect_laser_points.py:39-57 pickles, truncated like the
   reference's or sub-pixel
+* :func:`green_laser_finder`        -- the reference's careful detector (feature_detection.py:6-40), same signature and return
+  value, on sba_detect_blobs: threshold, dilation, closing, 8-connected components, "exactly one component"
+* :func:`find_laser_blobs`          -- its batched call -> ``LaserBlobs``
+* :func:`blob_centroid_table`       -- the (n_frames, 2) (row, col) table of the accepted components
 
 The reference thresholds the green channel with ``cv.threshold(green, t, 255, 0)`` and takes ``cv.moments`` of the result:
 m00 = 255 n, m10 = 255 sum x, m01 = 255 sum y over the n pixels above t, and returns ``(int(m01 / m00), int(m10 / m00))`` =
@@ -15,12 +19,16 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native
-from ._native import DOT_NONE, DOT_OK, DOT_SPREAD, DOT_TOO_LARGE, DOT_TOO_SMALL, LaserDots  # noqa: F401
+from ._native import (BLOB_MULTIPLE, BLOB_NONE, BLOB_OK, BLOB_OVERFLOW, BLOB_REJECTED, DOT_NONE, DOT_OK, DOT_SPREAD,  # noqa: F401
+                      DOT_TOO_LARGE, DOT_TOO_SMALL, LaserBlobs, LaserDots)
 
 SBA_DOT_OK, SBA_DOT_NONE, SBA_DOT_TOO_SMALL, SBA_DOT_TOO_LARGE, SBA_DOT_SPREAD = DOT_OK, DOT_NONE, DOT_TOO_SMALL, DOT_TOO_LARGE, DOT_SPREAD
+SBA_BLOB_OK, SBA_BLOB_NONE, SBA_BLOB_OVERFLOW, SBA_BLOB_REJECTED, SBA_BLOB_MULTIPLE = BLOB_OK, BLOB_NONE, BLOB_OVERFLOW, BLOB_REJECTED, BLOB_MULTIPLE
 
 __all__ = ["green_laser_finder_faster", "find_laser_dots", "centroid_table", "LaserDots",
-           "SBA_DOT_OK", "SBA_DOT_NONE", "SBA_DOT_TOO_SMALL", "SBA_DOT_TOO_LARGE", "SBA_DOT_SPREAD"]
+           "SBA_DOT_OK", "SBA_DOT_NONE", "SBA_DOT_TOO_SMALL", "SBA_DOT_TOO_LARGE", "SBA_DOT_SPREAD",
+           "green_laser_finder", "find_laser_blobs", "blob_centroid_table", "disk", "LaserBlobs",
+           "SBA_BLOB_OK", "SBA_BLOB_NONE", "SBA_BLOB_OVERFLOW", "SBA_BLOB_REJECTED", "SBA_BLOB_MULTIPLE"]
 
 
 def find_laser_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_extent=0, roi_rect=None, roi_circle=None,
@@ -60,4 +68,66 @@ def centroid_table(dots: LaserDots, subpixel=True, weighted=True, accept=(SBA_DO
     else:
         n = dots.sums[keep, 0]
         out[keep, 0], out[keep, 1] = dots.sums[keep, 2] // n, dots.sums[keep, 1] // n
+    return out
+
+
+# ----------------------------------------------------------------------------- connected components (sba_detect_blobs)
+def disk(radius):
+    """``skimage.morphology.disk``: the (2 r + 1, 2 r + 1) uint8 footprint of the pixels with dx^2 + dy^2 <= r^2."""
+    r = int(radius)
+    d = np.arange(-r, r + 1)
+    return (d[:, None] ** 2 + d[None, :] ** 2 <= r * r).astype(np.uint8)
+
+
+def _disk_radius(footprint, default, name):
+    """The r of a footprint equal to disk(r), r <= 8; ``default`` for None; ValueError for anything else."""
+    if footprint is None:
+        return default
+    fp = np.asarray(footprint)
+    if fp.ndim == 2 and fp.shape[0] == fp.shape[1] and fp.shape[0] % 2 == 1:
+        r = fp.shape[0] // 2
+        if r <= _native.BLOB_MAX_RADIUS and np.array_equal(fp != 0, disk(r) != 0):
+            return r
+    raise ValueError(f"{name} must be None or equal to disk(r) with r <= {_native.BLOB_MAX_RADIUS}: other footprints are not supported")
+
+
+def find_laser_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=4, max_blobs=8, min_area=0, max_area=0,
+                     centre=None, max_centre_dist=0, roi_rect=None, roi_circle=None, chunk_frames=0, device=0,
+                     want_mask=False, want_labels=False) -> LaserBlobs:
+    """The connected components of every frame of a batch and the verdict on each frame: ``_native.detect_blobs``.
+    ``frames`` as for :func:`find_laser_dots`.  With the defaults (disk(1), disk(4), no filter) a frame's status is SBA_BLOB_OK
+    exactly when the reference's ``green_laser_finder`` returns a centroid, and ``centroid[:, :2]`` is that centroid as (x, y)."""
+    return _native.detect_blobs(frames, threshold=threshold, channel=channel, dilate_radius=dilate_radius, close_radius=close_radius,
+                                max_blobs=max_blobs, min_area=min_area, max_area=max_area, centre=centre,
+                                max_centre_dist=max_centre_dist, roi_rect=roi_rect, roi_circle=roi_circle, chunk_frames=chunk_frames,
+                                device=device, want_mask=want_mask, want_labels=want_labels)
+
+
+def green_laser_finder(img, laser_intensity_thresh=70, centroid_dist_thresh=1100, small_footprint=None, big_footprint=None):
+    """The reference's detector (feature_detection.py:6-40) on one (H, W, C >= 2) frame: the green channel above the threshold,
+    ``binary_dilation`` with ``small_footprint``, ``binary_closing`` with ``big_footprint``, ``measure.label``; returns the float
+    ``(row, col)`` centroid of the component (``regionprops(...).centroid``) when there is exactly one, else None.
+    A footprint is None (disk(1) / disk(4), the reference's defaults) or an array equal to some ``disk(r)``, r <= 8; anything
+    else raises ValueError.  ``centroid_dist_thresh`` is accepted and IGNORED, as in the reference, whose distance filter is
+    commented out (:32-34); ``find_laser_blobs(..., centre=, max_centre_dist=)`` applies it.  The closing keeps a dot at the image
+    border, as skimage >= 0.23 does (older versions wipe it)."""
+    r1 = _disk_radius(small_footprint, 1, "small_footprint")
+    r2 = _disk_radius(big_footprint, 4, "big_footprint")
+    img = img if _native._is_tensor(img) else np.asarray(img)
+    if img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError("green_laser_finder expects one (H, W, 3) or (H, W, 4) frame")
+    blobs = find_laser_blobs(img[None], threshold=laser_intensity_thresh, channel=1, dilate_radius=r1, close_radius=r2, max_blobs=2)
+    if blobs.n_components[0] != 1:
+        return None
+    return (float(blobs.centroid[0, 1]), float(blobs.centroid[0, 0]))
+
+
+def blob_centroid_table(blobs: LaserBlobs, weighted=False) -> np.ndarray:
+    """The (n_frames, 2) float (row, col) table of the accepted components, NaN rows where the status is not SBA_BLOB_OK:
+    the centroid over the morphed pixels (the reference's ``regionprops`` centroid) or, ``weighted``, the one over the raw pixels
+    weighted by value - threshold (NaN too where the component holds no raw pixel)."""
+    out = np.full((blobs.status.shape[0], 2), np.nan)
+    keep = blobs.status == SBA_BLOB_OK
+    cx, cy = (2, 3) if weighted else (0, 1)
+    out[keep, 0], out[keep, 1] = blobs.centroid[keep, cy], blobs.centroid[keep, cx]
     return out
