@@ -591,6 +591,24 @@ def _frame_layout(frames, device):
     return tensor, frames, B, H, W, Cn, sr, sf
 
 
+def _frame_args(frames, device, opts, channel, threshold, chunk_frames, roi_rect, roi_circle):
+    """What detect_dots and detect_blobs do alike with their frames: fills the fields both options structs have and returns
+    (B, H, W, leading arguments of the C call -- device, pointer, sizes, pitches, options --, the object that owns the pixels)."""
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    opts.channel, opts.threshold, opts.frames_on_device, opts.chunk_frames = int(channel), int(threshold), 1 if tensor else 0, int(chunk_frames)
+    if roi_rect is not None:
+        opts.roi_rect = (C.c_int32 * 4)(*(int(v) for v in roi_rect))
+    if roi_circle is not None:
+        opts.roi_circle = (C.c_int32 * 3)(*(int(v) for v in roi_circle))
+    if tensor:
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # the frames are complete before the library reads them
+        ptr = frames.data_ptr()
+    else:
+        ptr = frames.ctypes.data
+    return B, H, W, (device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts)), frames
+
+
 def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_extent=0, roi_rect=None, roi_circle=None,
                 chunk_frames=0, device=0):
     """Thresholded image moments of a batch of frames (sba_detect_dots, include/sba_hip.h) -> LaserDots.
@@ -602,24 +620,12 @@ def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_ext
     above ``threshold``; ``roi_rect`` = (x0, y0, x1, y1) half-open, ``roi_circle`` = (cx, cy, r); ``min_area``, ``max_area``,
     ``max_extent``: the status rules, 0 = no limit; ``chunk_frames``: host frames staged per copy, 0 = the library's default."""
     lib = load()
-    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
     opts = DotOpts()
-    opts.channel, opts.threshold, opts.frames_on_device = int(channel), int(threshold), 1 if tensor else 0
-    opts.min_area, opts.max_area, opts.max_extent, opts.chunk_frames = int(min_area), int(max_area), int(max_extent), int(chunk_frames)
-    if roi_rect is not None:
-        opts.roi_rect = (C.c_int32 * 4)(*(int(v) for v in roi_rect))
-    if roi_circle is not None:
-        opts.roi_circle = (C.c_int32 * 3)(*(int(v) for v in roi_circle))
+    opts.min_area, opts.max_area, opts.max_extent = int(min_area), int(max_area), int(max_extent)
+    B, H, W, args, _keep = _frame_args(frames, device, opts, channel, threshold, chunk_frames, roi_rect, roi_circle)
     sums, box = np.zeros((B, 12), np.uint64), np.zeros((B, 4), np.int32)
     centroid, status = np.full((B, 4), np.nan), np.full(B, DOT_NONE, np.int32)
-    if tensor:
-        import torch
-        torch.cuda.current_stream(device).synchronize()      # the frames are complete before the library reads them
-        ptr = frames.data_ptr()
-    else:
-        ptr = frames.ctypes.data
-    _check(lib.sba_detect_dots(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts), sums.ctypes.data, box.ctypes.data,
-                               centroid.ctypes.data, status.ctypes.data))
+    _check(lib.sba_detect_dots(*args, sums.ctypes.data, box.ctypes.data, centroid.ctypes.data, status.ctypes.data))
     return LaserDots(sums, box, centroid, status)
 
 
@@ -636,30 +642,18 @@ def detect_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=
     ``chunk_frames`` caps the frames per chunk, 0 = the library's choice; ``want_mask`` / ``want_labels`` return the morphed
     mask and measure.label's array."""
     lib = load()
-    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
     opts = BlobOpts()
-    opts.channel, opts.threshold, opts.frames_on_device = int(channel), int(threshold), 1 if tensor else 0
     opts.dilate_radius, opts.close_radius, opts.max_blobs = int(dilate_radius), int(close_radius), int(max_blobs)
-    opts.min_area, opts.max_area, opts.max_centre_dist, opts.chunk_frames = int(min_area), int(max_area), int(max_centre_dist), int(chunk_frames)
+    opts.min_area, opts.max_area, opts.max_centre_dist = int(min_area), int(max_area), int(max_centre_dist)
     if centre is not None:
         opts.centre_x, opts.centre_y = int(centre[0]), int(centre[1])
-    if roi_rect is not None:
-        opts.roi_rect = (C.c_int32 * 4)(*(int(v) for v in roi_rect))
-    if roi_circle is not None:
-        opts.roi_circle = (C.c_int32 * 3)(*(int(v) for v in roi_circle))
+    B, H, W, args, _keep = _frame_args(frames, device, opts, channel, threshold, chunk_frames, roi_rect, roi_circle)
     K = int(max_blobs) if 0 < int(max_blobs) <= BLOB_MAX_BLOBS else BLOB_DEFAULT_BLOBS
     ncomp, blobs = np.zeros(B, np.int32), np.zeros((B, K, BLOB_NREC), np.uint64)
     accepted, centroid, status = np.full(B, -1, np.int32), np.full((B, 4), np.nan), np.full(B, BLOB_NONE, np.int32)
     mask = np.zeros((B, H, W), np.uint8) if want_mask else None
     labels = np.zeros((B, H, W), np.int32) if want_labels else None
-    if tensor:
-        import torch
-        torch.cuda.current_stream(device).synchronize()      # the frames are complete before the library reads them
-        ptr = frames.data_ptr()
-    else:
-        ptr = frames.ctypes.data
-    _check(lib.sba_detect_blobs(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts), ncomp.ctypes.data, blobs.ctypes.data,
-                                accepted.ctypes.data, centroid.ctypes.data, status.ctypes.data,
+    _check(lib.sba_detect_blobs(*args, ncomp.ctypes.data, blobs.ctypes.data, accepted.ctypes.data, centroid.ctypes.data, status.ctypes.data,
                                 None if mask is None else mask.ctypes.data, None if labels is None else labels.ctypes.data))
     return LaserBlobs(ncomp, blobs, accepted, centroid, status, mask, labels)
 

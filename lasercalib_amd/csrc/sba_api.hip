@@ -372,31 +372,48 @@ int sba_reproj_stats(sba_handle* h, const sba_reproj_opts* opts, double* cam_sta
   });
 }
 
+// What sba_detect_dots and sba_detect_blobs (`fn`, for the error text) check of their frames, in the order both report it:
+// frame_args_invalid, then the entry point's own options, then frame_layout_invalid.
+static int detect_invalid(const char* fn, const char* what) { g_last_error = std::string(fn) + ": " + what; return SBA_ERR_INVALID; }
+
+static int frame_args_invalid(const char* fn, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                              int32_t channel, int32_t threshold) {
+  if (n_frames < 0 || height < 0 || width < 0) return detect_invalid(fn, "negative size");
+  if (n_frames > 0 && !frames) return detect_invalid(fn, "null frames");
+  if (channels != 1 && channels != 3 && channels != 4) return detect_invalid(fn, "channels must be 1, 3 or 4");
+  if (channel < 0 || channel >= channels) return detect_invalid(fn, "channel out of range");
+  if (threshold < 0 || threshold > 255) return detect_invalid(fn, "threshold must be in 0..255");
+  return SBA_OK;
+}
+
+// the pitches, the size limit (`why_limit` ends its text), the device
+static int frame_layout_invalid(const char* fn, int device, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                                int64_t row_pitch, int64_t frame_pitch, const char* why_limit) {
+  if (row_pitch < (int64_t)width * channels) return detect_invalid(fn, "row_pitch is smaller than width * channels");
+  if ((__int128)height * row_pitch > frame_pitch) return detect_invalid(fn, "frame_pitch is smaller than height * row_pitch");
+  if ((__int128)n_frames * frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * frame_pitch overflows");
+  if (height > 16384 || width > 16384) {
+    g_last_error = std::string(fn) + ": width and height are limited to 16384" + why_limit;
+    return SBA_ERR_UNSUPPORTED;
+  }
+  return check_device(device);
+}
+
 int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts* opts, uint64_t* sums, int32_t* box, double* centroid,
                     int32_t* status) {
+  const char* fn = "sba_detect_dots";
   sba_dot_opts o{};
   o.channel = 1; o.threshold = 50;
   if (opts) o = *opts;
-  auto invalid = [](const char* what) { g_last_error = std::string("sba_detect_dots: ") + what; return (int)SBA_ERR_INVALID; };
-  if (n_frames < 0 || height < 0 || width < 0) return invalid("negative size");
-  if (n_frames > 0 && !frames) return invalid("null frames");
-  if (channels != 1 && channels != 3 && channels != 4) return invalid("channels must be 1, 3 or 4");
-  if (o.channel < 0 || o.channel >= channels) return invalid("channel out of range");
-  if (o.threshold < 0 || o.threshold > 255) return invalid("threshold must be in 0..255");
-  if (o.min_area < 0 || o.max_area < 0 || o.max_extent < 0) return invalid("negative area or extent limit");
-  if (row_pitch < (int64_t)width * channels) return invalid("row_pitch is smaller than width * channels");
-  if ((__int128)height * row_pitch > frame_pitch) return invalid("frame_pitch is smaller than height * row_pitch");
-  if ((__int128)n_frames * frame_pitch > INT64_MAX) return invalid("n_frames * frame_pitch overflows");
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, o.threshold);
+  if (rc) return rc;
+  if (o.min_area < 0 || o.max_area < 0 || o.max_extent < 0) return detect_invalid(fn, "negative area or extent limit");
   // up to 16384 x 16384 every sum fits 64 bits: the largest a frame could ask for, sum w x^2 <= 255 * 16384 * 16384^3 / 3 = 6.1e18
   // < 2^64 = 1.8e19 (the sums actually returned are far smaller: sba_detect.hpp)
-  if (height > 16384 || width > 16384) {
-    g_last_error = "sba_detect_dots: width and height are limited to 16384 (the bound under which every sum fits 64 bits)";
-    return SBA_ERR_UNSUPPORTED;
-  }
-  int rc = check_device(device);
-  if (rc) return rc;
-  if (n_frames == 0) return SBA_OK;
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch,
+                            " (the bound under which every sum fits 64 bits)");
+  if (rc || n_frames == 0) return rc;
   return guarded(nullptr, [&] {
     return sba_detect_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, sums, box, centroid, status);
   });
@@ -405,28 +422,18 @@ int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t
 int sba_detect_blobs(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                      int64_t row_pitch, int64_t frame_pitch, const sba_blob_opts* opts, int32_t* n_components, uint64_t* blobs,
                      int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out) {
+  const char* fn = "sba_detect_blobs";
   sba_blob_opts o{};
   o.channel = 1; o.threshold = 70; o.dilate_radius = 1; o.close_radius = 4;
   if (opts) o = *opts;
-  auto invalid = [](const char* what) { g_last_error = std::string("sba_detect_blobs: ") + what; return (int)SBA_ERR_INVALID; };
-  if (n_frames < 0 || height < 0 || width < 0) return invalid("negative size");
-  if (n_frames > 0 && !frames) return invalid("null frames");
-  if (channels != 1 && channels != 3 && channels != 4) return invalid("channels must be 1, 3 or 4");
-  if (o.channel < 0 || o.channel >= channels) return invalid("channel out of range");
-  if (o.threshold < 0 || o.threshold > 255) return invalid("threshold must be in 0..255");
-  if (o.dilate_radius < 0 || o.dilate_radius > 8 || o.close_radius < 0 || o.close_radius > 8) return invalid("a radius must be in 0..8");
-  if (o.max_blobs < 0 || o.max_blobs > 64) return invalid("max_blobs must be in 0..64");
-  if (o.min_area < 0 || o.max_area < 0 || o.max_centre_dist < 0) return invalid("negative area or distance limit");
-  if (row_pitch < (int64_t)width * channels) return invalid("row_pitch is smaller than width * channels");
-  if ((__int128)height * row_pitch > frame_pitch) return invalid("frame_pitch is smaller than height * row_pitch");
-  if ((__int128)n_frames * frame_pitch > INT64_MAX) return invalid("n_frames * frame_pitch overflows");
-  if (height > 16384 || width > 16384) {     // a pixel's index y W + x fits the 32-bit labels, every sum 64 bits
-    g_last_error = "sba_detect_blobs: width and height are limited to 16384";
-    return SBA_ERR_UNSUPPORTED;
-  }
-  int rc = check_device(device);
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, o.threshold);
   if (rc) return rc;
-  if (n_frames == 0) return SBA_OK;
+  if (o.dilate_radius < 0 || o.dilate_radius > 8 || o.close_radius < 0 || o.close_radius > 8) return detect_invalid(fn, "a radius must be in 0..8");
+  if (o.max_blobs < 0 || o.max_blobs > 64) return detect_invalid(fn, "max_blobs must be in 0..64");
+  if (o.min_area < 0 || o.max_area < 0 || o.max_centre_dist < 0) return detect_invalid(fn, "negative area or distance limit");
+  // up to 16384 x 16384 a pixel's index y W + x fits the 32-bit labels, every sum 64 bits
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc || n_frames == 0) return rc;
   return guarded(nullptr, [&] {
     return sba_blobs_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, n_components, blobs, accepted,
                           centroid, status, mask_out, labels_out);

@@ -4,8 +4,9 @@
 //
 // Per chunk of frames, all on one stream:
 //   k_blob_init       the blob table: sums = 0, xmin = ymin = all ones
-//   k_blob_threshold  the ONLY pass over the frame bytes (read like k_dot_moments: aligned 16-byte loads, byte-wise head and
-//                     tail): the raw mask, one bit per pixel in 64-pixel words, and the value byte of every raw pixel
+//   k_blob_threshold  the ONLY pass over the frame bytes (read as k_dot_moments reads them: scan_row of sba_frames.hpp, which
+//                     also has the chunks and the staging of host frames): the raw mask, one bit per pixel in 64-pixel words,
+//                     and the value byte of every raw pixel
 //   k_blob_morph      dilation by disk(r1) (+) disk(r2), then erosion by disk(r2), on words: shifts with carries between
 //                     neighbouring words, a band of rows plus a halo of r1 + 2 r2 rows staged in LDS
 //   k_blob_label_tile union-find of the pixels of one 32 x 64 tile in LDS; label = smallest linear index y W + x of the tree
@@ -34,13 +35,7 @@ constexpr int64_t BLOB_SCRATCH_BYTES = (int64_t)1 << 30;  // budget of the per-f
 
 typedef unsigned long long u64;
 
-struct BlobParams {
-  const uint8_t* frames;
-  int64_t row_pitch, frame_pitch;
-  int32_t height, width, channel, threshold;
-  int32_t x0, y0, x1, y1;                    // the rectangle, clipped to the frame, half-open
-  int32_t ccx, ccy;
-  int64_t r2;                                // the circle's r^2; < 0 = no circle
+struct BlobParams : FrameView {
   int32_t rows_per_band;
   int32_t ww;                                // 64-pixel words of one row
   int32_t dh, eh;                            // rows the composed dilation / the erosion reach
@@ -90,38 +85,22 @@ __global__ void k_blob_init(u64* __restrict__ table, int64_t n) {
 }
 
 // ------------------------------------------------------------------------------------------------ threshold
-// The 16 bytes `v` start at byte s of the row (see dot_vector).  Sets the bit of every pixel above the threshold in the wave's
-// LDS row and stores its value byte; returns false, having done nothing, when no lane of the wave has one.
-template <int C>
-__device__ __forceinline__ bool blob_vector(const uint4& v, uint32_t s, uint32_t channel, uint32_t thr, uint32_t* row32, uint8_t* __restrict__ vrow) {
-  constexpr int NPIX = (16 + C - 1) / C;
-  const uint32_t q = s / C, r = s - q * C;
-  const uint32_t j0 = channel >= r ? channel - r : channel + C - r;
-  const uint32_t xq = q + (channel < r ? 1u : 0u);
-  uint32_t d[4];
-  if (C == 1) { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
-  else {
-    d[0] = __builtin_amdgcn_alignbyte(v.y, v.x, j0);
-    d[1] = __builtin_amdgcn_alignbyte(v.z, v.y, j0);
-    d[2] = __builtin_amdgcn_alignbyte(v.w, v.z, j0);
-    d[3] = __builtin_amdgcn_alignbyte(0u, v.w, j0);
-  }
-  uint32_t b[NPIX], any = 0;
+// scan_row's sink: sets the bit of every pixel above the threshold in the wave's LDS row and stores its value byte
+struct BlobSink {
+  uint32_t* row32;
+  uint8_t* __restrict__ vrow;
+  uint32_t thr;
+  template <int NPIX>
+  __device__ __forceinline__ void operator()(uint32_t xq, const uint32_t (&v)[NPIX]) {
 #pragma unroll
-  for (int k = 0; k < NPIX; ++k) {
-    b[k] = (d[(k * C) >> 2] >> (8 * ((k * C) & 3))) & 0xffu;
-    any |= b[k] > thr ? 1u : 0u;
+    for (int k = 0; k < NPIX; ++k)
+      if (v[k] > thr) {
+        const uint32_t x = xq + (uint32_t)k;
+        atomicOr(&row32[x >> 5], 1u << (x & 31u));
+        vrow[x] = (uint8_t)v[k];
+      }
   }
-  if (!__any(any != 0)) return false;
-#pragma unroll
-  for (int k = 0; k < NPIX; ++k)
-    if (b[k] > thr) {
-      const uint32_t x = xq + (uint32_t)k;
-      atomicOr(&row32[x >> 5], 1u << (x & 31u));
-      vrow[x] = (uint8_t)b[k];
-    }
-  return true;
-}
+};
 
 // grid (bands, frames), DOT_THREADS threads; wave w takes rows band_lo + w, + w + 4, ... of ALL rows of the frame (a row outside
 // the regions gets zero words).  The bits of a row are gathered in the wave's own LDS row, which is all zero between rows.
@@ -135,53 +114,14 @@ __global__ void __launch_bounds__(DOT_THREADS) k_blob_threshold(const BlobParams
   const int band_hi = min(P.height, band_lo + P.rows_per_band);
   const uint8_t* __restrict__ fp = P.frames + (int64_t)f * P.frame_pitch;
   u64* myrow = s_row[wave];
-  uint32_t* row32 = reinterpret_cast<uint32_t*>(myrow);
   for (int i = lane; i < P.ww; i += 64) myrow[i] = 0;
   blob_wave_sync();
 
   for (int y = band_lo + wave; y < band_hi; y += DOT_WAVES) {
     u64* __restrict__ out = raw + ((size_t)f * P.height + y) * P.ww;
-    uint8_t* __restrict__ vrow = vals + ((size_t)f * P.height + y) * P.width;
-    int xa = P.x0, xb = P.x1;
-    if (y < P.y0 || y >= P.y1) xb = xa;
-    else if (P.r2 >= 0) {
-      const long long dy = (long long)y - P.ccy, rem = P.r2 - dy * dy;
-      if (rem < 0) xb = xa;
-      else {
-        const long long dx = dot_isqrt(rem);
-        xa = (int)max((long long)xa, (long long)P.ccx - dx);
-        xb = (int)min((long long)xb, (long long)P.ccx + dx + 1);
-      }
-    }
-    bool hit = false;
-    if (xa < xb) {
-      const uint8_t* __restrict__ rp = fp + (int64_t)y * P.row_pitch;
-      const int bs = xa * C, be = xb * C;
-      const int head_end = min(be, bs + (int)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(rp + bs) & 15u)) & 15u));
-      const int body_end = head_end + ((be - head_end) & ~15);
-      {   // lanes 0..14: the bytes in front of the aligned body; lanes 32..46: those behind it
-        const int b = lane < 32 ? bs + lane : body_end + (lane - 32);
-        bool on = false;
-        if (b < (lane < 32 ? head_end : be)) {
-          const uint32_t q = (uint32_t)b / C;
-          if ((uint32_t)b - q * C == channel) {
-            const uint32_t v = rp[b];
-            if (v > thr) { on = true; atomicOr(&row32[q >> 5], 1u << (q & 31u)); vrow[q] = (uint8_t)v; }
-          }
-        }
-        hit = __any(on);
-      }
-      for (int s0 = head_end + lane * 16; s0 < body_end + lane * 16; s0 += 64 * 16 * DOT_UNROLL) {   // the bound is wave-uniform
-        uint4 v[DOT_UNROLL];
-#pragma unroll
-        for (int u = 0; u < DOT_UNROLL; ++u) {
-          const int s = s0 + u * 64 * 16;
-          v[u] = s < body_end ? *reinterpret_cast<const uint4*>(rp + s) : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int u = 0; u < DOT_UNROLL; ++u) hit |= blob_vector<C>(v[u], (uint32_t)(s0 + u * 64 * 16), channel, thr, row32, vrow);
-      }
-    }
+    BlobSink S{reinterpret_cast<uint32_t*>(myrow), vals + ((size_t)f * P.height + y) * P.width, thr};
+    int xa, xb;
+    const bool hit = frame_row_span(P, y, xa, xb) && scan_row<C>(fp + (int64_t)y * P.row_pitch, xa, xb, channel, thr, S);
     if (!hit) {                                                          // the usual case: a dark row
       for (int i = lane; i < P.ww; i += 64) out[i] = 0;
       continue;
@@ -590,9 +530,7 @@ inline void blob_launch(BlobParams P, int channels, int64_t nf, int64_t total_fr
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemsetAsync(S.rowcnt, 0, sizeof(int) * (size_t)nf * H, st));
   {
-    int64_t rpb = (int64_t)H * total_frames / 2048;                     // as dot_launch: about 2048 workgroups, 4 to 32 rows each
-    rpb = std::max<int64_t>(DOT_WAVES, std::min<int64_t>(32, rpb / DOT_WAVES * DOT_WAVES));
-    P.rows_per_band = (int)rpb;
+    const int rpb = P.rows_per_band = frame_rows_per_band(H, total_frames);
     const dim3 grid((unsigned)((H + rpb - 1) / rpb), (unsigned)nf);
     if (channels == 1) hipLaunchKernelGGL(k_blob_threshold<1>, grid, dim3(DOT_THREADS), 0, st, P, S.raw, S.vals);
     else if (channels == 3) hipLaunchKernelGGL(k_blob_threshold<3>, grid, dim3(DOT_THREADS), 0, st, P, S.raw, S.vals);
@@ -656,8 +594,7 @@ inline void blob_judge(const sba_blob_opts& o, int K, int32_t ncomp, uint64_t* r
 
 // Arguments are checked by the caller (sba_api.hip).  Frames are taken in chunks: of a chunk the scratch above (labels, value
 // bytes, the two bit planes: about 5.3 bytes per pixel) stays within BLOB_SCRATCH_BYTES, a single frame always being allowed,
-// so device memory does not grow with n_frames.  Host frames go through two staging buffers as in dot_call: the copy of chunk
-// k + 1 runs beside the kernels of chunk k.  One set of scratch: the stream is drained before the next chunk's kernels start.
+// so device memory does not grow with n_frames.  frames_in_chunks drives them; one set of scratch serves every chunk.
 inline int blob_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                      int64_t row_pitch, int64_t frame_pitch, const sba_blob_opts& o, int32_t* n_components, uint64_t* blobs,
                      int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out) {
@@ -674,35 +611,24 @@ inline int blob_call(int device, const uint8_t* frames, int64_t n_frames, int32_
   }
   HIPCHK(hipSetDevice(device));
   BlobParams P{};
-  P.height = height; P.width = width; P.channel = o.channel; P.threshold = o.threshold;
-  const int32_t* rr = o.roi_rect;
-  if (rr[0] == 0 && rr[1] == 0 && rr[2] == 0 && rr[3] == 0) { P.x0 = 0; P.y0 = 0; P.x1 = width; P.y1 = height; }
-  else {
-    P.x0 = std::max(rr[0], 0); P.y0 = std::max(rr[1], 0); P.x1 = std::min(rr[2], width); P.y1 = std::min(rr[3], height);
-  }
-  P.ccx = o.roi_circle[0]; P.ccy = o.roi_circle[1];
-  P.r2 = o.roi_circle[2] > 0 ? (int64_t)o.roi_circle[2] * o.roi_circle[2] : -1;
+  static_cast<FrameView&>(P) = frame_view(frames, row_pitch, frame_pitch, height, width, o.channel, o.threshold, o.roi_rect, o.roi_circle);
   P.ww = (width + 63) / 64;
   P.dh = o.dilate_radius + o.close_radius; P.eh = o.close_radius;
   blob_halfwidths(o.dilate_radius, o.close_radius, P.hwd, P.hwe);
   P.max_blobs = K; P.want_labels = labels_out ? 1 : 0;
 
   const bool on_device = o.frames_on_device != 0;
-  const int64_t row_bytes = (int64_t)width * channels, tight_frame = row_bytes * height;
+  const int64_t tight_frame = (int64_t)width * channels * height;
   const int64_t px = (int64_t)height * width, words = (int64_t)height * P.ww;
   const int64_t per_frame = px * 5 + words * 16 + (int64_t)height * 8 + (int64_t)K * BLOB_NREC * 8 + 4;
   int64_t chunk = std::max<int64_t>(1, BLOB_SCRATCH_BYTES / per_frame);
   if (!on_device) chunk = std::min(chunk, std::max<int64_t>(1, DOT_STAGE_BYTES / tight_frame));
   if (o.chunk_frames > 0) chunk = std::min<int64_t>(chunk, o.chunk_frames);
   chunk = std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames);
-  const int nbuf = !on_device && n_frames > chunk ? 2 : 1;
 
-  DotStream s_run, s_copy;
-  DotEvent ev_copied[2];
-  DevBuf<uint8_t> d_stage[2], d_vals;
+  DevBuf<uint8_t> d_vals;
   DevBuf<u64> d_raw, d_mask, d_table;
   DevBuf<int> d_lab, d_rowcnt, d_rowbase, d_ncomp;
-  if (!on_device) for (int b = 0; b < nbuf; ++b) d_stage[b].alloc((size_t)std::max<int64_t>(16, chunk * tight_frame));
   d_raw.alloc((size_t)(chunk * words)); d_mask.alloc((size_t)(chunk * words)); d_vals.alloc((size_t)(chunk * px)); d_lab.alloc((size_t)(chunk * px));
   d_rowcnt.alloc((size_t)(chunk * height)); d_rowbase.alloc((size_t)(chunk * height)); d_ncomp.alloc((size_t)chunk);
   d_table.alloc((size_t)chunk * K * BLOB_NREC);
@@ -710,46 +636,29 @@ inline int blob_call(int device, const uint8_t* frames, int64_t n_frames, int32_
   std::vector<int32_t> h_ncomp((size_t)chunk);
   if (!blobs) h_table.resize((size_t)chunk * K * BLOB_NREC);
 
-  auto stage = [&](int64_t lo, int b) {            // host frames [lo, lo + m) -> d_stage[b], rows packed (as in dot_call)
-    const int64_t m = std::min(chunk, n_frames - lo);
-    const uint8_t* src = frames + lo * frame_pitch;
-    if (row_pitch == row_bytes && frame_pitch == tight_frame)
-      HIPCHK(hipMemcpyAsync(d_stage[b].p, src, (size_t)(m * tight_frame), hipMemcpyHostToDevice, s_copy.s));
-    else if (frame_pitch == row_pitch * height)
-      HIPCHK(hipMemcpy2DAsync(d_stage[b].p, (size_t)row_bytes, src, (size_t)row_pitch, (size_t)row_bytes, (size_t)(m * height),
-                              hipMemcpyHostToDevice, s_copy.s));
-    else
-      for (int64_t i = 0; i < m; ++i)
-        HIPCHK(hipMemcpy2DAsync(d_stage[b].p + i * tight_frame, (size_t)row_bytes, src + i * frame_pitch, (size_t)row_pitch,
-                                (size_t)row_bytes, (size_t)height, hipMemcpyHostToDevice, s_copy.s));
-    HIPCHK(hipEventRecord(ev_copied[b].e, s_copy.s));
-  };
-
-  if (!on_device) stage(0, 0);
-  int b = 0;
-  for (int64_t lo = 0; lo < n_frames; lo += chunk, b ^= (nbuf - 1)) {
-    const int64_t m = std::min(chunk, n_frames - lo);
-    if (on_device) { P.frames = frames + lo * frame_pitch; P.row_pitch = row_pitch; P.frame_pitch = frame_pitch; }
-    else {
-      P.frames = d_stage[b].p; P.row_pitch = row_bytes; P.frame_pitch = tight_frame;
-      HIPCHK(hipStreamWaitEvent(s_run.s, ev_copied[b].e, 0));
-    }
-    blob_launch(P, channels, m, n_frames, S, mask_out != nullptr, s_run.s);
-    if (!on_device && lo + chunk < n_frames) stage(lo + chunk, b ^ 1);   // the other buffer is free: its kernels ended with the last pass
-    uint64_t* tab = blobs ? blobs + (size_t)lo * K * BLOB_NREC : h_table.data();
-    HIPCHK(hipMemcpyAsync(h_ncomp.data(), d_ncomp.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s_run.s));
-    HIPCHK(hipMemcpyAsync(tab, d_table.p, sizeof(uint64_t) * m * K * BLOB_NREC, hipMemcpyDeviceToHost, s_run.s));
-    if (mask_out) HIPCHK(hipMemcpyAsync(mask_out + lo * px, d_vals.p, (size_t)(m * px), hipMemcpyDeviceToHost, s_run.s));
-    if (labels_out) HIPCHK(hipMemcpyAsync(labels_out + lo * px, d_lab.p, sizeof(int32_t) * (size_t)(m * px), hipMemcpyDeviceToHost, s_run.s));
-    HIPCHK(hipStreamSynchronize(s_run.s));         // the results of this chunk are on the host; the scratch may be reused
-    for (int64_t i = 0; i < m; ++i) {
-      const int64_t f = lo + i;
-      if (n_components) n_components[f] = h_ncomp[i];
-      blob_judge(o, K, h_ncomp[i], tab + (size_t)i * K * BLOB_NREC, accepted ? accepted + f : nullptr, centroid ? centroid + 4 * f : nullptr,
-                 status ? status + f : nullptr);
-    }
-  }
-  HIPCHK(hipStreamSynchronize(s_copy.s));
+  // where the table of the chunk that starts at frame lo goes
+  auto table_of = [&](int64_t lo) { return blobs ? blobs + (size_t)lo * K * BLOB_NREC : h_table.data(); };
+  frames_in_chunks(
+      P, channels, n_frames, on_device, chunk,
+      [&](const FrameView& V, int64_t, int64_t m, hipStream_t st) {
+        static_cast<FrameView&>(P) = V;
+        blob_launch(P, channels, m, n_frames, S, mask_out != nullptr, st);
+      },
+      [&](int64_t lo, int64_t m, hipStream_t st) {
+        HIPCHK(hipMemcpyAsync(h_ncomp.data(), d_ncomp.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(table_of(lo), d_table.p, sizeof(uint64_t) * m * K * BLOB_NREC, hipMemcpyDeviceToHost, st));
+        if (mask_out) HIPCHK(hipMemcpyAsync(mask_out + lo * px, d_vals.p, (size_t)(m * px), hipMemcpyDeviceToHost, st));
+        if (labels_out) HIPCHK(hipMemcpyAsync(labels_out + lo * px, d_lab.p, sizeof(int32_t) * (size_t)(m * px), hipMemcpyDeviceToHost, st));
+      },
+      [&](int64_t lo, int64_t m) {
+        uint64_t* tab = table_of(lo);                // without `blobs`: the host table of this chunk
+        for (int64_t i = 0; i < m; ++i) {
+          const int64_t f = lo + i;
+          if (n_components) n_components[f] = h_ncomp[i];
+          blob_judge(o, K, h_ncomp[i], tab + (size_t)i * K * BLOB_NREC, accepted ? accepted + f : nullptr, centroid ? centroid + 4 * f : nullptr,
+                     status ? status + f : nullptr);
+        }
+      });
   return SBA_OK;
 }
 

@@ -284,6 +284,14 @@ def test_null_options_are_the_defaults_and_every_output_is_optional():
     assert rc == 0 and blob_diff(_native.LaserBlobs(nc, tab, acc, cen, st), want) is None
     assert want.blobs[1, 0, 3] == 8 and list(want.status) == [OK, MULTIPLE]
     assert lib.sba_detect_blobs(*args, None, None, None, None, None, None, None) == 0
+    # judged without the table, two frames in one chunk: each frame from its own rows of the chunk's table (reversed, so that
+    # the second frame, judged from the first one's rows, would come out OK with the centroid of the wrong component)
+    rev = np.ascontiguousarray(frames[::-1])
+    rargs = (0, rev.ctypes.data) + args[2:]
+    out = [(np.full(B, 7, np.int32), np.full((B, 4), 7.0), np.full(B, 7, np.int32)) for _ in range(2)]
+    for (a, c, s), table in zip(out, (tab, None)):
+        assert lib.sba_detect_blobs(*rargs, None, None if table is None else table.ctypes.data, a.ctypes.data, c.ctypes.data, s.ctypes.data, None, None) == 0
+        assert list(s) == [MULTIPLE, OK] and list(a) == [-1, 0] and np.array_equal(c, want.centroid[::-1], equal_nan=True)
     labels = np.zeros((B, H, W), np.int32)
     assert lib.sba_detect_blobs(*args, None, None, None, None, None, None, labels.ctypes.data) == 0 and np.array_equal(labels, want.labels)
     mask = np.zeros((B, H, W), np.uint8)

@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from lasercalib_amd import _native, feature_detection as fd  # noqa: E402
+from test_blobs_host import blob_diff, blobs_oracle  # noqa: E402
 from test_detect_host import (NONE, OK, RMS_CAP, SPREAD, TOO_LARGE, TOO_SMALL, all_bright_sums, centroid_errors,  # noqa: E402
                               dots_oracle, opencv_restatement, render_spots, same_dots)
 
@@ -115,6 +116,51 @@ def test_empty_frame_among_frames_with_dots():
     assert same_dots(got, dots_oracle(frames))
     assert got.status[2] == NONE and np.isnan(got.centroid[2]).all() and list(got.box[2]) == [61, 47, -1, -1]
     assert not got.sums[2].any() and np.all(got.status[[0, 1, 3, 4]] == OK) and np.isnan(got.spread_px[2])
+
+
+# ----------------------------------------------------------------------------- 1b. the seams of the row scanner, both detectors
+def seam_frames(W, C):
+    """(2, 5, W, C) frames: the other channels random bytes, channel C // 2 zero but for about min(a third of the pixels, 40) of
+    random value, some exactly 255, and a few set by hand at both ends of the rows and either side of byte 4096 of a row (one
+    step of 64 lanes x 16 bytes x 4 loads in flight): some 40 non-zero pixels a frame at the most, for at most 64 components."""
+    rng = np.random.default_rng(1000 * C + W)
+    f = rng.integers(0, 256, size=(2, 5, W, C), dtype=np.uint8)
+    g = rng.integers(1, 256, size=(2, 5, W), dtype=np.uint8)
+    g[rng.random(g.shape) < 0.2] = 255
+    g[rng.random(g.shape) >= min(0.3, 35.0 / (5 * W))] = 0
+    for y, x in ((0, 0), (2, 1), (2, W - 1), (3, 4096 // C - 1), (3, 4096 // C + 1), (1, W - 2), (4, W - 1)):
+        if 0 <= x < W:
+            g[:, y, x] = (255, 51)
+    f[..., C // 2] = g
+    return f
+
+
+@pytest.mark.parametrize("C", [1, 3, 4])
+@pytest.mark.parametrize("W", [1, 5, 16, 17, 1400])
+def test_both_detectors_see_the_same_pixels_at_the_seams_of_a_row(torch, W, C):
+    """W = 1 and 5 (C = 1): a row that lies wholly in the head or, at a misaligned base, has an empty body; 16: exactly one
+    vector; 17: a body with a tail; 1400 x 3 = 4200 bytes: more than one full step of the unrolled loop."""
+    frames = seam_frames(W, C)
+    n = frames.size
+    sources = [("host, a frame per chunk", frames, dict(chunk_frames=1))]
+    for offset in (0, 1, 15):
+        big = torch.full((n + 32,), 255, dtype=torch.uint8, device="cuda")               # bright around the frames
+        view = big[offset:offset + n].view(frames.shape)
+        view.copy_(torch.from_numpy(frames))
+        assert big.data_ptr() % 16 == 0 and view.data_ptr() % 16 == offset
+        sources.append((f"device, base + {offset}", view, {}))
+    for roi in [{}] + ([dict(roi_rect=(1, 1, W, 4))] if W > 1 else []):
+        kw = dict(threshold=50, channel=C // 2, **roi)
+        want_dots = dots_oracle(frames, **kw)
+        want_blobs = blobs_oracle(frames, dilate_radius=0, close_radius=0, max_blobs=64, **kw)
+        assert 0 < want_blobs.n_components.min() and want_blobs.n_components.max() <= 64, want_blobs.n_components
+        for name, src, how in sources:
+            dots = fd.find_laser_dots(src, **kw, **how)
+            blobs = fd.find_laser_blobs(src, dilate_radius=0, close_radius=0, max_blobs=64, **kw, **how)
+            assert same_dots(dots, want_dots), (name, roi)
+            assert blob_diff(blobs, want_blobs) is None, (blob_diff(blobs, want_blobs), name, roi)
+            for dot_sum, blob_col in ((0, 3), (6, 4), (9, 7)):                           # n = n_raw, sum w, n_sat
+                assert np.array_equal(dots.sums[:, dot_sum], blobs.blobs[:, :, blob_col].sum(axis=1)), (name, roi, dot_sum)
 
 
 # ----------------------------------------------------------------------------- 2. where a 32-bit partial sum overflows
