@@ -677,6 +677,63 @@ int sba_detect_blobs(int device, const uint8_t* frames, int64_t n_frames, int32_
                      int32_t* status /*n_frames or NULL*/, uint8_t* mask_out /*n_frames*height*width or NULL*/,
                      int32_t* labels_out /*n_frames*height*width or NULL*/);
 
+/* ---------------------------------------------------------------- undistortion of video frames (what a calibration is used for)
+ * The reference takes the lens out of its pictures with cv.getOptimalNewCameraMatrix and cv.undistort
+ * (scripts/charuco_intrinsics.py:163-184) and probes the distortion with lasercalib/utils.py:probe_monotonicity.
+ * sba_undistort_frames resamples a batch of frames of ONE camera (one lens per call) into the pinhole image of the camera
+ * matrix new_k = (fxn, fyn, cxn, cyn).  Stateless: no handle.  Frames are described as for sba_detect_dots (any pitch, any base,
+ * host memory or with frames_on_device device memory read in place); the output has out_height rows of out_width pixels of the
+ * same `channels` bytes, row r of frame f at out + f out_frame_pitch + r out_row_pitch, in host memory or with out_on_device in
+ * device memory of `device`, written in place.  The padding between output rows and frames is never written.
+ *
+ * The rule per destination pixel (x, y) -- this is the function's definition.  Every operation is ONE IEEE float64 operation,
+ * in this order, never contracted into a fused multiply-add; ifx = 1.0 / fxn and ify = 1.0 / fyn are formed once on the host.
+ *   xn = (x - cxn) * ifx;  yn = (y - cyn) * ify;  x2 = xn*xn;  y2 = yn*yn;  r2 = x2 + y2;  xy = xn*yn
+ *   t = r2*k3; t = k2 + t; t = r2*t; t = k1 + t; t = r2*t; rad = 1 + t
+ *   xd = xn*rad + ((2*p1)*xy + p2*(r2 + 2*x2));   yd = yn*rad + (p1*(r2 + 2*y2) + (2*p2)*xy)
+ *   sx = fx*xd + cx;  sy = fy*yd + cy
+ *   in_range = sx > -32768 && sx < 32768 && sy > -32768 && sy < 32768       (false for NaN)
+ *   qx = floor(sx*32 + 0.5), qy likewise  (integers; 0 when !in_range)      -> map_out = (qx, qy)
+ *   bilinear: ix = qx >> 5, ax = qx & 31 (iy, ay likewise); taps (ix,iy) (ix+1,iy) (ix,iy+1) (ix+1,iy+1) with integer weights
+ *             (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax ay;  value = (sum w * tap + 512) >> 10 per channel
+ *   nearest:  the single tap ((qx + 16) >> 5, (qy + 16) >> 5)
+ *   a tap outside the source image, and every tap when !in_range, has the value border_value
+ *   dp = r2*(3*k3); dp = (2*k2) + dp; dp = r2*dp; dp = k1 + dp
+ *   j00 = rad + (2*x2)*dp + ((2*p1)*yn + (6*p2)*xn);  j11 = rad + (2*y2)*dp + ((6*p1)*yn + (2*p2)*xn)
+ *   j01 = (2*xy)*dp + ((2*p1)*xn + (2*p2)*yn);  det = j00*j11 - j01*j01
+ *   flags: 1 OUTSIDE (a tap with non-zero weight lies outside the source, or !in_range), 2 FOLDED (!(det > 0)), 4 RANGE (!in_range)
+ * (j is the Jacobian of (xd, yd) by (xn, yn).)  FOLDED is a POINTWISE test, like the reference's probe_monotonicity: it says
+ * that the model is not locally invertible at that pixel.  Behind a second turning point of the radial polynomial the
+ * determinant is positive again and the pixel passes, although the model has folded over on the way there.
+ * The 1/32-pixel grid and the bilinear taps are OpenCV's (INTER_BITS = 5), but OpenCV rounds its weight table to 15 bits, so its
+ * bytes may differ from these by a grey level: the library agrees bit for bit with the rule above, not with cv.undistort.
+ * flags_out (out_height * out_width bytes) and map_out (out_height * out_width pairs (qx, qy), the position BEFORE nearest's
+ * rounding) are host memory; they depend on the geometry alone, are written once per call, and also when n_frames == 0.
+ * out may be NULL when a diagnostic is asked for: then no frame is read.
+ * Frames pass through the device in chunks (host frames through two staging buffers, a host output through one more); device
+ * memory does not grow with n_frames, and any chunk_frames gives the same bytes.
+ * Errors, all checked before any device work (text in sba_last_error(NULL)), out left untouched: the frame errors of
+ * sba_detect_dots; SBA_ERR_INVALID for a NULL lens or new_k, a lens or new_k value that is not finite, a focal length that is
+ * not > 0, an output size outside 0..16384, output pitches that are too small, an unknown interpolation, a border value outside
+ * 0..255, and out == NULL with n_frames > 0 when neither diagnostic is asked for. */
+typedef enum { SBA_UNDIST_OUTSIDE = 1, SBA_UNDIST_FOLDED = 2, SBA_UNDIST_RANGE = 4 } sba_undistort_flag;
+typedef struct { double fx, fy, cx, cy, k1, k2, p1, p2, k3; } sba_lens;   /* OpenCV's 5-coefficient model; the library's
+                                                                             11-/13-column rows are fx = fy = f, k3 = 0 */
+typedef struct {
+  int32_t frames_on_device;  /* as sba_dot_opts */
+  int32_t out_on_device;     /* 1: `out` is a device pointer on `device` */
+  int32_t interpolation;     /* 0 bilinear, 1 nearest */
+  int32_t border_value;      /* 0..255, every channel */
+  int32_t chunk_frames;      /* <= 0: library default */
+  int32_t reserved[7];
+} sba_undistort_opts;
+int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                         int64_t row_pitch, int64_t frame_pitch, const sba_lens* lens, const double* new_k /*fxn, fyn, cxn, cyn*/,
+                         int32_t out_height, int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch,
+                         const sba_undistort_opts* opts /*NULL: all zero*/, uint8_t* out /*or NULL*/,
+                         uint8_t* flags_out /*out_height*out_width, host, or NULL*/,
+                         int32_t* map_out /*out_height*out_width*2, host, or NULL*/);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

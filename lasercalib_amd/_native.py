@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
+    "sba_undistort_frames",
 )
 
 
@@ -127,6 +128,21 @@ BLOB_NREC, BLOB_DEFAULT_BLOBS, BLOB_MAX_BLOBS, BLOB_MAX_RADIUS = 12, 8, 64, 8
 # geometry of the kernels (csrc/sba_blobs.hpp), for the tests that straddle it: rows of a morphology band, rows of a labelling
 # tile (a tile is one 64-pixel word wide), words of a morphology band
 BLOB_MORPH_ROWS, BLOB_TILE_ROWS, BLOB_MORPH_WORDS = 32, 32, 8
+
+
+class LensStruct(C.Structure):                                            # sba_lens
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+class UndistortOpts(C.Structure):
+    _fields_ = [("frames_on_device", C.c_int32), ("out_on_device", C.c_int32), ("interpolation", C.c_int32),
+                ("border_value", C.c_int32), ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE = 1, 2, 4                       # sba_undistort_flag
+UNDIST_INTERPOLATION = {"linear": 0, "nearest": 1}                         # sba_undistort_opts.interpolation
+# the tile of destination pixels one workgroup owns (csrc/sba_undistort.hpp), for the tests that straddle it
+UNDIST_TILE_ROWS, UNDIST_TILE_COLS = 4, 256
 
 
 class AlignOpts(C.Structure):
@@ -411,6 +427,9 @@ def load():
         "sba_detect_blobs": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                        C.POINTER(BlobOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+        "sba_undistort_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                           C.POINTER(LensStruct), dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                           C.POINTER(UndistortOpts), C.c_void_p, C.c_void_p, C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
         "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
         "sba_reproj_stats": (C.c_int, [H, C.POINTER(ReprojOpts), dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(ReprojReport)]),
@@ -656,6 +675,63 @@ def detect_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=
     _check(lib.sba_detect_blobs(*args, ncomp.ctypes.data, blobs.ctypes.data, accepted.ctypes.data, centroid.ctypes.data, status.ctypes.data,
                                 None if mask is None else mask.ctypes.data, None if labels is None else labels.ctypes.data))
     return LaserBlobs(ncomp, blobs, accepted, centroid, status, mask, labels)
+
+
+def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", border_value=0, out=None, want_flags=False,
+                     want_map=False, want_frames=True, chunk_frames=0, device=0):
+    """sba_undistort_frames (include/sba_hip.h): ``frames`` as for ``detect_dots`` (numpy, or a torch tensor on ``device`` read in
+    place) resampled through the lens ``lens9`` = (fx, fy, cx, cy, k1, k2, p1, p2, k3) into the pinhole image of ``new_k`` = (fxn,
+    fyn, cxn, cyn) of ``out_size`` = (height, width).  Returns (out, flags, map): ``out`` is a numpy array for numpy frames and a
+    device tensor for tensor frames -- allocated here, or the caller's ``out``, which may be a strided view with contiguous
+    pixels --, None with ``want_frames=False`` (then no frame is read); ``flags`` (height, width) uint8 and ``map`` (height, width, 2) int32 are numpy
+    or None.  ``lasercalib_amd.imaging`` is the public face of this call."""
+    lib = load()
+    if interpolation not in UNDIST_INTERPOLATION:
+        raise ValueError(f"interpolation must be one of {sorted(UNDIST_INTERPOLATION)}, not {interpolation!r}")
+    if int(border_value) != border_value or not 0 <= int(border_value) <= 255:
+        raise ValueError(f"border_value must be an integer in 0..255, not {border_value!r}")
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    Ho, Wo = (int(v) for v in out_size)
+    if not (0 <= Ho <= DOT_MAX_DIM and 0 <= Wo <= DOT_MAX_DIM):
+        raise ValueError(f"out_size must be (height, width) within 0..{DOT_MAX_DIM}, got {(Ho, Wo)}")
+    lens = LensStruct(*(float(v) for v in lens9))
+    nk = np.ascontiguousarray([float(v) for v in new_k], dtype=np.float64)
+    opts = UndistortOpts()
+    opts.frames_on_device = opts.out_on_device = 1 if tensor else 0
+    opts.interpolation, opts.border_value, opts.chunk_frames = UNDIST_INTERPOLATION[interpolation], int(border_value), int(chunk_frames)
+    shape = (B, Ho, Wo, Cn) if len(frames.shape) == 4 else (B, Ho, Wo)
+    osr, osf, optr = Wo * Cn, Ho * Wo * Cn, None
+    if not want_frames:
+        if out is not None:
+            raise ValueError("out was given but no frames are asked for")
+        if not (want_flags or want_map):
+            raise ValueError("nothing asked for: neither frames nor flags nor map")
+        out = None
+    elif out is not None:
+        if _is_tensor(out) != tensor:
+            raise ValueError("out must be of the kind of frames: a numpy array for numpy frames, a device tensor for tensor frames")
+        if not tensor and not (isinstance(out, np.ndarray) and out.flags.writeable):
+            raise ValueError("out must be a writeable numpy array")
+        _t, _o, oB, oH, oW, oC, osr, osf = _frame_layout(out, device)
+        if (oB, oH, oW, oC) != (B, Ho, Wo, Cn):
+            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shape}")
+    elif tensor:
+        import torch
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    else:
+        out = np.empty(shape, np.uint8)
+    if tensor:
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # the frames are complete before the library reads them
+        ptr, optr = frames.data_ptr(), None if out is None else out.data_ptr()
+    else:
+        ptr, optr = frames.ctypes.data, None if out is None else out.ctypes.data
+    flags = np.zeros((Ho, Wo), np.uint8) if want_flags else None
+    qmap = np.zeros((Ho, Wo, 2), np.int32) if want_map else None
+    _check(lib.sba_undistort_frames(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(lens), _dptr(nk), Ho, Wo, osr, osf,
+                                    C.byref(opts), C.c_void_p(optr), None if flags is None else flags.ctypes.data,
+                                    None if qmap is None else qmap.ctypes.data))
+    return out, flags, qmap
 
 
 class Problem:

@@ -20,6 +20,10 @@ int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t
 int sba_blobs_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                    int64_t row_pitch, int64_t frame_pitch, const sba_blob_opts& opts, int32_t* n_components, uint64_t* blobs,
                    int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out);
+int sba_undistort_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                       int64_t row_pitch, int64_t frame_pitch, const sba_lens& lens, const double* new_k, int32_t out_height,
+                       int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out,
+                       uint8_t* flags_out, int32_t* map_out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -437,6 +441,37 @@ int sba_detect_blobs(int device, const uint8_t* frames, int64_t n_frames, int32_
   return guarded(nullptr, [&] {
     return sba_blobs_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, n_components, blobs, accepted,
                           centroid, status, mask_out, labels_out);
+  });
+}
+
+int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                         int64_t row_pitch, int64_t frame_pitch, const sba_lens* lens, const double* new_k, int32_t out_height,
+                         int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts* opts, uint8_t* out,
+                         uint8_t* flags_out, int32_t* map_out) {
+  const char* fn = "sba_undistort_frames";
+  sba_undistort_opts o{};
+  if (opts) o = *opts;
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
+  if (rc) return rc;
+  if (!lens || !new_k) return detect_invalid(fn, "null lens or new_k");
+  const double lv[9] = {lens->fx, lens->fy, lens->cx, lens->cy, lens->k1, lens->k2, lens->p1, lens->p2, lens->k3};
+  for (double v : lv) if (!std::isfinite(v)) return detect_invalid(fn, "a lens value is not finite");
+  for (int k = 0; k < 4; ++k) if (!std::isfinite(new_k[k])) return detect_invalid(fn, "a new_k value is not finite");
+  if (!(lens->fx > 0.0) || !(lens->fy > 0.0) || !(new_k[0] > 0.0) || !(new_k[1] > 0.0)) return detect_invalid(fn, "a focal length is not > 0");
+  if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
+  if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
+  if (o.border_value < 0 || o.border_value > 255) return detect_invalid(fn, "border_value must be in 0..255");
+  if (!out && n_frames > 0 && !flags_out && !map_out) return detect_invalid(fn, "null out and no diagnostic asked for");
+  if (out) {
+    if (out_row_pitch < (int64_t)out_width * channels) return detect_invalid(fn, "out_row_pitch is smaller than out_width * channels");
+    if ((__int128)out_height * out_row_pitch > out_frame_pitch) return detect_invalid(fn, "out_frame_pitch is smaller than out_height * out_row_pitch");
+    if ((__int128)n_frames * out_frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * out_frame_pitch overflows");
+  }
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc) return rc;
+  return guarded(nullptr, [&] {
+    return sba_undistort_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, *lens, new_k, out_height, out_width,
+                              out_row_pitch, out_frame_pitch, o, out, flags_out, map_out);
   });
 }
 

@@ -1,6 +1,8 @@
-// sba_detect.hip -- the laser-dot detectors' kernels (sba_detect.hpp: moments; sba_blobs.hpp: connected components).  They do
-// not depend on the camera model, so they are compiled once, in a translation unit of their own.
+// sba_detect.hip -- the kernels that work on video frames: the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
+// connected components) and the undistortion (sba_undistort.hpp).  They do not depend on the engine's camera model, so they
+// are compiled once, in a translation unit of their own.
 #include "sba_blobs.hpp"
+#include "sba_undistort.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -13,4 +15,12 @@ int sba_blobs_call(int device, const uint8_t* frames, int64_t n_frames, int32_t 
                    int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out) {
   return sba_detect::blob_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, opts, n_components, blobs,
                                accepted, centroid, status, mask_out, labels_out);
+}
+
+int sba_undistort_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                       int64_t row_pitch, int64_t frame_pitch, const sba_lens& lens, const double* new_k, int32_t out_height,
+                       int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out,
+                       uint8_t* flags_out, int32_t* map_out) {
+  return sba_detect::undistort_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, lens, new_k, out_height,
+                                    out_width, out_row_pitch, out_frame_pitch, opts, out, flags_out, map_out);
 }

@@ -1,0 +1,221 @@
+"""Taking the lens out of the pictures: what a finished calibration is used for (``scripts/charuco_intrinsics.py:163-184`` of
+the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monotonicity``), on sba_undistort_frames
+(include/sba_hip.h).
+
+* :class:`Lens`                        -- OpenCV's 5-coefficient model (fx, fy, cx, cy, k1, k2, p1, p2, k3), from a camera row of
+  the bundle adjustment or from a camera matrix and distortion coefficients
+* :func:`undistort_frames`             -- ``cv.undistort`` for a whole batch of frames of one camera, on the GPU
+* :func:`optimal_new_camera_matrix`    -- ``cv.getOptimalNewCameraMatrix``: the camera matrix that keeps only valid pixels
+  (alpha = 0), every source pixel (alpha = 1) or a blend; 81 points, on the host
+* :func:`invertible_region`            -- where the distortion model is locally invertible (the FOLDED flag), as a bool image
+
+Sizes are ``(width, height)``, as in OpenCV.  Pixels follow the rule written out in include/sba_hip.h: a float64 model, the
+source position on a 1/32-pixel grid, integer bilinear weights.  That is OpenCV's scheme, but OpenCV rounds its weight table to
+15 bits, so single bytes may differ from ``cv.undistort`` by a grey level.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _native
+from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE
+
+SBA_UNDIST_OUTSIDE, SBA_UNDIST_FOLDED, SBA_UNDIST_RANGE = UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE
+
+__all__ = ["Lens", "undistort_frames", "optimal_new_camera_matrix", "invertible_region",
+           "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
+
+
+class Lens:
+    """A pinhole camera with OpenCV's 5-coefficient distortion: focal lengths, principal point, radial k1, k2, k3 and tangential
+    p1, p2.  Every value must be finite and the focal lengths positive."""
+
+    __slots__ = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
+
+    def __init__(self, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+        vals = [float(v) for v in (fx, fy, cx, cy, k1, k2, p1, p2, k3)]
+        if not all(np.isfinite(vals)):
+            raise ValueError(f"Lens: every value must be finite, got {vals}")
+        if not (vals[0] > 0 and vals[1] > 0):
+            raise ValueError(f"Lens: the focal lengths must be > 0, got {vals[:2]}")
+        for name, v in zip(self.__slots__, vals):
+            setattr(self, name, v)
+
+    @classmethod
+    def from_camera_row(cls, row):
+        """From a camera row of the bundle adjustment: 11 columns [rvec(3), t(3), f, k1, k2, cx, cy] or 13 columns
+        [rvec(3), t(3), f, k1, k2, p1, p2, cx, cy]; fx = fy = f, k3 = 0."""
+        r = np.asarray(row, dtype=np.float64).reshape(-1)
+        if r.shape[0] == 11:
+            return cls(r[6], r[6], r[9], r[10], r[7], r[8])
+        if r.shape[0] == 13:
+            return cls(r[6], r[6], r[11], r[12], r[7], r[8], r[9], r[10])
+        raise ValueError(f"a camera row has 11 columns (radial model) or 13 (radial + tangential), not {r.shape[0]}")
+
+    @classmethod
+    def from_opencv(cls, camera_matrix, distortion_coefficients):
+        """From OpenCV's 3 x 3 camera matrix and its distortion vector (k1, k2, p1, p2[, k3]).  Longer vectors (the rational and
+        thin-prism models) are accepted only when their further coefficients are zero."""
+        K = np.asarray(camera_matrix, dtype=np.float64)
+        if K.shape != (3, 3):
+            raise ValueError(f"camera_matrix must be 3 x 3, got {K.shape}")
+        if K[0, 1] != 0 or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+            raise ValueError("camera_matrix must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]: skew is not supported")
+        d = np.asarray(distortion_coefficients, dtype=np.float64).reshape(-1)
+        if d.shape[0] < 4:
+            raise ValueError(f"distortion_coefficients must hold (k1, k2, p1, p2[, k3]), got {d.shape[0]} values")
+        if d.shape[0] > 5 and np.any(d[5:] != 0):
+            raise ValueError("only the 5-coefficient model is supported: k4..k6 and the prism / tilt terms must be zero")
+        return cls(K[0, 0], K[1, 1], K[0, 2], K[1, 2], d[0], d[1], d[2], d[3], d[4] if d.shape[0] > 4 else 0.0)
+
+    def as_tuple(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    @property
+    def camera_matrix(self):
+        return np.array([[self.fx, 0.0, self.cx], [0.0, self.fy, self.cy], [0.0, 0.0, 1.0]])
+
+    @property
+    def distortion_coefficients(self):
+        """(k1, k2, p1, p2, k3), OpenCV's order."""
+        return np.array([self.k1, self.k2, self.p1, self.p2, self.k3])
+
+    def __repr__(self):
+        return "Lens(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+    # ---- the forward model on normalised coordinates, and its inverse (host, float64)
+    def distort(self, x, y):
+        """(xd, yd) and the Jacobian entries (j00, j01, j11) of the distortion at normalised (x, y); j10 = j01."""
+        x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+        x2, y2, xy = x * x, y * y, x * y
+        r2 = x2 + y2
+        rad = 1.0 + r2 * (self.k1 + r2 * (self.k2 + r2 * self.k3))
+        dp = self.k1 + r2 * (2.0 * self.k2 + r2 * (3.0 * self.k3))
+        xd = x * rad + (2.0 * self.p1 * xy + self.p2 * (r2 + 2.0 * x2))
+        yd = y * rad + (self.p1 * (r2 + 2.0 * y2) + 2.0 * self.p2 * xy)
+        j00 = rad + 2.0 * x2 * dp + (2.0 * self.p1 * y + 6.0 * self.p2 * x)
+        j11 = rad + 2.0 * y2 * dp + (6.0 * self.p1 * y + 2.0 * self.p2 * x)
+        j01 = 2.0 * xy * dp + (2.0 * self.p1 * x + 2.0 * self.p2 * y)
+        return xd, yd, j00, j01, j11
+
+    def undistort_points(self, uv, steps=20):
+        """Normalised undistorted coordinates (n, 2) of the pixels ``uv`` (n, 2): Newton steps on distort(x, y) = ((u - cx) / fx,
+        (v - cy) / fy) from the distorted point, with the analytic Jacobian.  NaN where the Jacobian becomes singular."""
+        uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+        xd, yd = (uv[:, 0] - self.cx) / self.fx, (uv[:, 1] - self.cy) / self.fy
+        x, y = xd.copy(), yd.copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for _ in range(steps):
+                fx_, fy_, j00, j01, j11 = self.distort(x, y)
+                ex, ey = fx_ - xd, fy_ - yd
+                det = j00 * j11 - j01 * j01
+                x, y = x - (j11 * ex - j01 * ey) / det, y - (j00 * ey - j01 * ex) / det
+        return np.stack([x, y], axis=1)
+
+
+def _lens(lens):
+    if not isinstance(lens, Lens):
+        raise ValueError("lens must be a Lens (Lens.from_camera_row, Lens.from_opencv)")
+    return lens
+
+
+def _new_k(lens, new_camera_matrix):
+    """(fxn, fyn, cxn, cyn) from None (the lens's own matrix, as in cv.undistort), a 3 x 3 matrix or those four values."""
+    if new_camera_matrix is None:
+        return (lens.fx, lens.fy, lens.cx, lens.cy)
+    K = np.asarray(new_camera_matrix, dtype=np.float64)
+    if K.shape == (4,):
+        k = tuple(float(v) for v in K)
+    elif K.shape == (3, 3):
+        if K[0, 1] != 0 or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+            raise ValueError("new_camera_matrix must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]: skew and rectification are not supported")
+        k = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
+    else:
+        raise ValueError(f"new_camera_matrix must be None, 3 x 3 or (fx, fy, cx, cy), got shape {K.shape}")
+    if not all(np.isfinite(k)) or not (k[0] > 0 and k[1] > 0):
+        raise ValueError(f"new_camera_matrix: values must be finite and the focal lengths > 0, got {k}")
+    return k
+
+
+def _size(size, name):
+    try:
+        w, h = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be (width, height), got {size!r}") from None
+    if not (0 <= w <= _native.DOT_MAX_DIM and 0 <= h <= _native.DOT_MAX_DIM):
+        raise ValueError(f"{name} must be (width, height) within 0..{_native.DOT_MAX_DIM}, got {(w, h)}")
+    return w, h
+
+
+def undistort_frames(frames, lens, new_camera_matrix=None, out_size=None, interpolation="linear", border_value=0, out=None,
+                     want_flags=False, want_map=False, chunk_frames=0, device=0):
+    """``cv.undistort(frame, K, dist, None, new_camera_matrix)`` for every frame of a batch of one camera.
+
+    ``frames``: uint8, (B, H, W, C) with C in (1, 3, 4) or (B, H, W); a numpy array in any layout with contiguous pixels, or a
+    torch tensor on ``device``, read in place.  The result is a numpy array for numpy frames and a device tensor for tensor
+    frames (allocated by torch, or ``out``: same kind, shape (B, height, width[, C]), any row and frame strides, whose padding is
+    left untouched).  ``new_camera_matrix=None`` means the lens's own matrix; ``out_size=(width, height)`` defaults to the size
+    of the frames.  ``interpolation`` is "linear" or "nearest"; ``border_value`` (0..255) fills what lies outside the source.
+    With ``want_flags`` / ``want_map`` returns ``(frames, flags, map)``: ``flags`` (height, width) uint8 of SBA_UNDIST_OUTSIDE |
+    FOLDED | RANGE, ``map`` (height, width, 2) int32, the source position in 1/32 pixels; whichever was not asked for is None."""
+    lens = _lens(lens)
+    nk = _new_k(lens, new_camera_matrix)
+    _t, _f, _B, H, W, _C, _sr, _sf = _native._frame_layout(frames, device)
+    w, h = (W, H) if out_size is None else _size(out_size, "out_size")
+    res, flags, qmap = _native.undistort_frames(frames, lens.as_tuple(), nk, (h, w), interpolation=interpolation, border_value=border_value,
+                                                out=out, want_flags=want_flags, want_map=want_map, chunk_frames=chunk_frames, device=device)
+    return (res, flags, qmap) if (want_flags or want_map) else res
+
+
+def invertible_region(lens, new_camera_matrix, size, device=0):
+    """A (height, width) bool image of the destination pixels at which the distortion model is locally invertible (the Jacobian
+    determinant of the distortion is positive: the FOLDED flag of a call without frames is clear).  Like the reference's
+    ``probe_monotonicity`` this is a pointwise test: behind a second turning point of the polynomial it passes again."""
+    lens = _lens(lens)
+    w, h = _size(size, "size")
+    _o, flags, _m = _native.undistort_frames(np.zeros((0, 1, 1, 1), np.uint8), lens.as_tuple(), _new_k(lens, new_camera_matrix), (h, w),
+                                             want_flags=True, want_frames=False, device=device)
+    return (flags & UNDIST_FOLDED) == 0
+
+
+def optimal_new_camera_matrix(lens, image_size, alpha, new_size=None):
+    """``cv.getOptimalNewCameraMatrix(K, dist, image_size, alpha, new_size)`` -> ``(K_new, roi)``.
+
+    A 9 x 9 grid of source pixels spanning the image (corners included) is undistorted to normalised coordinates.  The INNER
+    rectangle is the largest axis-parallel one the grid shows to lie inside the undistorted image: bounded by the largest x of
+    the left column, the smallest x of the right column, the largest y of the top row and the smallest y of the bottom row.  The
+    OUTER rectangle is the bounding box of all 81 points.  A rectangle (x0, y0, x1, y1) gives the camera matrix that maps it onto
+    the pixel centres of the new image: fx = (width - 1) / (x1 - x0), cx = -fx x0, and likewise in y.  ``alpha`` in [0, 1] blends
+    the inner matrix (0: only valid pixels, some source pixels are lost) into the outer one (1: every source pixel is kept,
+    with border between them).  ``roi`` = (x, y, width, height) is the inner rectangle in pixels of the new image, rounded inwards
+    (a value within 1e-9 of a whole pixel counts as that pixel) and clipped to it: the region where all pixels are valid.  As in OpenCV, the rectangles come from 9 samples per edge: an
+    extremum of an edge between two samples is missed by a fraction of a pixel."""
+    lens = _lens(lens)
+    w, h = _size(image_size, "image_size")
+    nw, nh = (w, h) if new_size is None else _size(new_size, "new_size")
+    if min(w, h, nw, nh) < 2:
+        raise ValueError("image_size and new_size must be at least 2 x 2")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must be in [0, 1], got {alpha}")
+    n = 9
+    gx, gy = np.meshgrid(np.arange(n) * (w - 1) / (n - 1), np.arange(n) * (h - 1) / (n - 1))      # [row j][column i]
+    pts = lens.undistort_points(np.stack([gx.ravel(), gy.ravel()], axis=1)).reshape(n, n, 2)
+    if not np.all(np.isfinite(pts)):
+        raise ValueError("the distortion cannot be inverted over the whole image: the model folds inside it")
+    inner = (pts[:, 0, 0].max(), pts[0, :, 1].max(), pts[:, -1, 0].min(), pts[-1, :, 1].min())
+    outer = (pts[..., 0].min(), pts[..., 1].min(), pts[..., 0].max(), pts[..., 1].max())
+    if not (inner[2] > inner[0] and inner[3] > inner[1]):
+        raise ValueError("the undistorted image has no inner rectangle: the model folds inside the image")
+
+    def matrix(r):
+        fx, fy = (nw - 1) / (r[2] - r[0]), (nh - 1) / (r[3] - r[1])
+        return np.array([fx, fy, -fx * r[0], -fy * r[1]])
+
+    k = matrix(inner) * (1.0 - alpha) + matrix(outer) * alpha
+    K_new = np.array([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]])
+    x0, y0 = int(np.ceil(inner[0] * k[0] + k[2] - 1e-9)), int(np.ceil(inner[1] * k[1] + k[3] - 1e-9))
+    x1, y1 = int(np.floor(inner[2] * k[0] + k[2] + 1e-9)), int(np.floor(inner[3] * k[1] + k[3] + 1e-9))
+    x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, nw - 1), min(y1, nh - 1)
+    roi = (x0, y0, max(x1 - x0 + 1, 0), max(y1 - y0 + 1, 0))
+    return K_new, roi
