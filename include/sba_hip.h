@@ -734,6 +734,72 @@ int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, in
                          uint8_t* flags_out /*out_height*out_width, host, or NULL*/,
                          int32_t* map_out /*out_height*out_width*2, host, or NULL*/);
 
+/* ---------------------------------------------------------------- static light in video frames: learn it, take it out
+ * The detectors above inherit the reference's precondition that the laser dot is the only bright spot of a frame.  A status
+ * LED, a leaking illuminator or a reflection that sits above the threshold in every frame of a camera breaks it.  What tells
+ * the dot from such light is time: the dot visits a pixel in a handful of frames, a static source is there in all of them.
+ * sba_background_accumulate reads every frame once and keeps per-pixel statistics over time; sba_background_suppress applies
+ * what the caller derived from them (a level and a mask per pixel) to a batch of frames and returns one-channel frames for the
+ * detectors.  Both are stateless and describe their frames as sba_detect_dots does (8-bit, channels 1, 3 or 4 interleaved, any
+ * base, any row_pitch and frame_pitch, host memory or with frames_on_device device memory read in place; host frames are
+ * staged chunk by chunk through two device buffers).
+ *
+ * sba_background_accumulate.  Let v be byte `channel` of pixel p in a frame f that takes part: `use`, n_frames bytes in host
+ * memory, non-zero = the frame takes part; NULL = all do.  The accumulators are the caller's, height*width values each,
+ * row-major and packed, naturally aligned; each may be NULL; all in host memory, or with stats_on_device all in device memory:
+ *   sum   (uint32) += v            sumsq (uint64) += v*v
+ *   hot   (uint32) += [v > threshold]                 vmax  (uint8)  = max(vmax, v)
+ *   n_used (uint64, ONE value, always host memory, may be NULL) += the number of frames that took part
+ * accumulate = 0: the arrays and *n_used are taken as zero on entry and overwritten; accumulate = 1: the call adds to what
+ * they hold, so a video can stream through in as many calls as the caller likes.  Every stored value is an integer: any
+ * chunk_frames, any split of the frames over calls and any order of the calls give the same bits.
+ * n_frames = 0, or no frame taking part, returns SBA_OK and leaves the arrays as they are (accumulate = 0: zeroed).
+ * Errors, all checked before any device work (text in sba_last_error(NULL)), arrays and *n_used left untouched: the frame
+ * errors of sba_detect_dots; SBA_ERR_UNSUPPORTED when (accumulate ? *n_used : 0) + n_frames exceeds 2^24 -- the bound under
+ * which `sum` cannot overflow, 255 * 2^24 < 2^32 (sumsq: 255^2 * 2^24 < 2^41; hot <= 2^24).
+ *
+ * sba_background_suppress.  level: height*width bytes or NULL for all 0; mask: height*width bytes or NULL for none, non-zero =
+ * the pixel is removed; both in host memory, or with model_on_device both in device memory.  The output is a batch of
+ * ONE-CHANNEL frames, row r of frame f at out + f out_frame_pitch + r out_row_pitch, in host memory or with out_on_device in
+ * device memory; the padding between rows and frames is never written.  Per pixel, with v as above:
+ *   mode 0 (gate):      out = 0 if mask != 0 or v <= level, else v
+ *   mode 1 (subtract):  out = 0 if mask != 0, else max(v - level, 0)
+ * Gate leaves the values of the surviving pixels alone: thresholds, weighted centroids and saturation counts of the detectors
+ * mean on its output (channels = 1, channel = 0) what they mean on raw frames.  Any chunk_frames gives the same bytes.
+ * n_frames = 0 returns SBA_OK and writes nothing.
+ * Errors, all checked before any device work, out left untouched: the frame errors of sba_detect_dots; SBA_ERR_INVALID for a
+ * NULL out with n_frames > 0, out_row_pitch < width, out_frame_pitch < height out_row_pitch, and a mode that is not 0 or 1. */
+typedef struct {
+  int32_t channel;          /* interleaved channel that is read; the reference: 1 (green of BGR)         */
+  int32_t threshold;        /* 0..255; `hot` counts v > threshold                                        */
+  int32_t frames_on_device; /* 1: `frames` is a device pointer on `device`                               */
+  int32_t stats_on_device;  /* 1: sum, sumsq, hot and vmax are device pointers on `device`               */
+  int32_t accumulate;       /* 0: overwrite, 1: add to what the arrays and *n_used hold                  */
+  int32_t chunk_frames;     /* frames per chunk at most; <= 0 = library default                          */
+  int32_t reserved[6];
+} sba_background_accumulate_opts;
+int sba_background_accumulate(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width,
+                              int32_t channels /*1, 3 or 4*/, int64_t row_pitch, int64_t frame_pitch,
+                              const sba_background_accumulate_opts* opts /*NULL: {1, 50, 0...}*/,
+                              const uint8_t* use /*n_frames, host, or NULL*/, uint32_t* sum /*height*width or NULL*/,
+                              uint64_t* sumsq /*height*width or NULL*/, uint32_t* hot /*height*width or NULL*/,
+                              uint8_t* vmax /*height*width or NULL*/, uint64_t* n_used /*1, host, or NULL*/);
+typedef enum { SBA_BG_GATE = 0, SBA_BG_SUBTRACT = 1 } sba_background_mode;
+typedef struct {
+  int32_t channel;          /* interleaved channel that is read                                          */
+  int32_t frames_on_device; /* 1: `frames` is a device pointer on `device`                               */
+  int32_t model_on_device;  /* 1: level and mask are device pointers on `device`                         */
+  int32_t out_on_device;    /* 1: `out` is a device pointer on `device`                                  */
+  int32_t mode;             /* sba_background_mode                                                       */
+  int32_t chunk_frames;     /* frames per chunk at most; <= 0 = library default                          */
+  int32_t reserved[6];
+} sba_background_suppress_opts;
+int sba_background_suppress(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width,
+                            int32_t channels /*1, 3 or 4*/, int64_t row_pitch, int64_t frame_pitch,
+                            const uint8_t* level /*height*width or NULL*/, const uint8_t* mask /*height*width or NULL*/,
+                            int64_t out_row_pitch /*bytes, >= width*/, int64_t out_frame_pitch /*bytes, >= height*out_row_pitch*/,
+                            const sba_background_suppress_opts* opts /*NULL: {1, 0...}*/, uint8_t* out);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
-    "sba_undistort_frames",
+    "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress",
 )
 
 
@@ -143,6 +143,25 @@ UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE = 1, 2, 4                       # sb
 UNDIST_INTERPOLATION = {"linear": 0, "nearest": 1}                         # sba_undistort_opts.interpolation
 # the tile of destination pixels one workgroup owns (csrc/sba_undistort.hpp), for the tests that straddle it
 UNDIST_TILE_ROWS, UNDIST_TILE_COLS = 4, 256
+
+
+class BgAccumulateOpts(C.Structure):                                      # sba_background_accumulate_opts
+    _fields_ = [("channel", C.c_int32), ("threshold", C.c_int32), ("frames_on_device", C.c_int32), ("stats_on_device", C.c_int32),
+                ("accumulate", C.c_int32), ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class BgSuppressOpts(C.Structure):                                        # sba_background_suppress_opts
+    _fields_ = [("channel", C.c_int32), ("frames_on_device", C.c_int32), ("model_on_device", C.c_int32), ("out_on_device", C.c_int32),
+                ("mode", C.c_int32), ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+BG_MODES = {"gate": 0, "subtract": 1}                                      # sba_background_mode
+BG_MAX_FRAMES = 1 << 24                                                    # frames one set of accumulators takes
+# where the accumulate kernel splits the frames of a chunk over grid.y and merges with atomics (csrc/sba_background.hpp), for the
+# tests that sit either side of it: a frame of fewer than BG_SPLIT_GROUPS 16-byte groups (height * ceil(width * channels / 16))
+# in a chunk of more than BG_SPLIT_FRAMES frames
+BG_SPLIT_GROUPS, BG_SPLIT_FRAMES = 65536, 16
+BG_STAT_BYTES = {"sum": 4, "sumsq": 8, "hot": 4, "vmax": 1}               # bytes of a value of each accumulator
 
 
 class AlignOpts(C.Structure):
@@ -430,6 +449,11 @@ def load():
         "sba_undistort_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                            C.POINTER(LensStruct), dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                            C.POINTER(UndistortOpts), C.c_void_p, C.c_void_p, C.c_void_p]),
+        "sba_background_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                                C.POINTER(BgAccumulateOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_uint64)]),
+        "sba_background_suppress": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BgSuppressOpts), C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
         "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
         "sba_reproj_stats": (C.c_int, [H, C.POINTER(ReprojOpts), dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(ReprojReport)]),
@@ -732,6 +756,109 @@ def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", bor
                                     C.byref(opts), C.c_void_p(optr), None if flags is None else flags.ctypes.data,
                                     None if qmap is None else qmap.ctypes.data))
     return out, flags, qmap
+
+
+def _plane(name, a, itemsize, H, W, device, writeable):
+    """(is a tensor, pointer) of a packed (H, W) plane of ``itemsize``-byte integers, a numpy array or a tensor on ``device``."""
+    if _is_tensor(a):
+        if not a.is_cuda or (a.device.index or 0) != device:
+            raise ValueError(f"{name}: the tensor must live on cuda:{device}")
+        if tuple(a.shape) != (H, W) or a.element_size() != itemsize or a.is_floating_point() or not a.is_contiguous():
+            raise ValueError(f"{name}: must be a contiguous ({H}, {W}) tensor of {itemsize}-byte integers, got {tuple(a.shape)} {a.dtype}")
+        return True, a.data_ptr()
+    if not isinstance(a, np.ndarray) or a.shape != (H, W) or a.dtype.kind not in "uib" or a.dtype.itemsize != itemsize or not a.flags.c_contiguous:
+        raise ValueError(f"{name}: must be a C-contiguous ({H}, {W}) numpy array of {itemsize}-byte integers")
+    if writeable and not a.flags.writeable:
+        raise ValueError(f"{name}: must be writeable")
+    return False, a.ctypes.data
+
+
+def background_accumulate(frames, sum=None, sumsq=None, hot=None, vmax=None, n_used=0, use=None, threshold=50, channel=1,
+                          accumulate=True, chunk_frames=0, device=0):
+    """sba_background_accumulate (include/sba_hip.h): per-pixel statistics over time of byte ``channel`` of ``frames`` (as for
+    ``detect_dots``: numpy, or a torch tensor on ``device`` read in place).  ``sum`` and ``hot`` (4-byte integers), ``sumsq``
+    (8-byte) and ``vmax`` (uint8) are (H, W) planes, updated IN PLACE; each may be None; they are all numpy arrays or all
+    tensors on ``device`` (torch.int32 / torch.int64 hold the unsigned values' bits).  ``use``: one flag per frame, None = all
+    frames.  ``accumulate=False`` overwrites the planes instead of adding to them.  Returns the new frame count:
+    ``n_used`` (taken as 0 with ``accumulate=False``) plus the frames that took part."""
+    lib = load()
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    opts = BgAccumulateOpts()
+    opts.channel, opts.threshold, opts.frames_on_device = int(channel), int(threshold), 1 if tensor else 0
+    opts.accumulate, opts.chunk_frames = 1 if accumulate else 0, int(chunk_frames)
+    ptrs, kinds = [], set()
+    for name, a in (("sum", sum), ("sumsq", sumsq), ("hot", hot), ("vmax", vmax)):
+        if a is None:
+            ptrs.append(None)
+            continue
+        on_dev, ptr = _plane(name, a, BG_STAT_BYTES[name], H, W, device, True)
+        kinds.add(on_dev)
+        ptrs.append(C.c_void_p(ptr))
+    if len(kinds) > 1:
+        raise ValueError("sum, sumsq, hot and vmax must all be numpy arrays or all be device tensors")
+    opts.stats_on_device = 1 if True in kinds else 0
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+        if use.shape != (B,):
+            raise ValueError(f"use must hold one flag per frame ({B}), got the shape {use.shape}")
+    if tensor or opts.stats_on_device:
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # frames and planes are complete before the library touches them
+    n = C.c_uint64(int(n_used))
+    _check(lib.sba_background_accumulate(device, C.c_void_p(frames.data_ptr() if tensor else frames.ctypes.data), B, H, W, Cn, sr, sf,
+                                         C.byref(opts), None if use is None else C.c_void_p(use.ctypes.data), *ptrs, C.byref(n)))
+    return int(n.value)
+
+
+def background_suppress(frames, level=None, mask=None, mode="gate", channel=1, out=None, chunk_frames=0, device=0):
+    """sba_background_suppress (include/sba_hip.h): byte ``channel`` of ``frames`` (as for ``detect_dots``) with the static light
+    taken out -> (B, H, W) uint8, a numpy array for numpy frames and a device tensor for tensor frames (allocated here, or the
+    caller's ``out``, which may be a strided view with contiguous pixels).  ``level`` and ``mask`` are (H, W) planes of bytes or
+    None, both numpy arrays or both tensors on ``device``.  ``mode`` "gate": 0 where the mask is set or the value is not above
+    the level, else the value; "subtract": 0 where the mask is set, else max(value - level, 0)."""
+    lib = load()
+    if mode not in BG_MODES:
+        raise ValueError(f"mode must be one of {sorted(BG_MODES)}, not {mode!r}")
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    opts = BgSuppressOpts()
+    opts.channel, opts.frames_on_device, opts.out_on_device = int(channel), 1 if tensor else 0, 1 if tensor else 0
+    opts.mode, opts.chunk_frames = BG_MODES[mode], int(chunk_frames)
+    ptrs, kinds, keep = [], set(), []
+    for name, a in (("level", level), ("mask", mask)):
+        if a is None:
+            ptrs.append(None)
+            continue
+        if not _is_tensor(a):
+            a = np.ascontiguousarray(a)                  # uint8, or bool (a byte of 0 / 1)
+        keep.append(a)
+        on_dev, ptr = _plane(name, a, 1, H, W, device, False)
+        kinds.add(on_dev)
+        ptrs.append(C.c_void_p(ptr))
+    if len(kinds) > 1:
+        raise ValueError("level and mask must both be numpy arrays or both be device tensors")
+    opts.model_on_device = 1 if True in kinds else 0
+    osr, osf = W, H * W
+    if out is not None:
+        if _is_tensor(out) != tensor:
+            raise ValueError("out must be of the kind of frames: a numpy array for numpy frames, a device tensor for tensor frames")
+        if not tensor and not (isinstance(out, np.ndarray) and out.flags.writeable):
+            raise ValueError("out must be a writeable numpy array")
+        if len(out.shape) != 3:
+            raise ValueError(f"out must be (B, H, W), got the shape {tuple(out.shape)}")
+        _t, _o, oB, oH, oW, _c, osr, osf = _frame_layout(out, device)
+        if (oB, oH, oW) != (B, H, W):
+            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {(B, H, W)}")
+    elif tensor:
+        import torch
+        out = torch.empty((B, H, W), dtype=torch.uint8, device=frames.device)
+    else:
+        out = np.empty((B, H, W), np.uint8)
+    if tensor or opts.model_on_device:
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # frames, level and mask are complete before the library reads them
+    ptr, optr = (frames.data_ptr(), out.data_ptr()) if tensor else (frames.ctypes.data, out.ctypes.data)
+    _check(lib.sba_background_suppress(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, *ptrs, osr, osf, C.byref(opts), C.c_void_p(optr)))
+    return out
 
 
 class Problem:

@@ -24,6 +24,12 @@ int sba_undistort_call(int device, const uint8_t* frames, int64_t n_frames, int3
                        int64_t row_pitch, int64_t frame_pitch, const sba_lens& lens, const double* new_k, int32_t out_height,
                        int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out,
                        uint8_t* flags_out, int32_t* map_out);
+int sba_bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                           int64_t row_pitch, int64_t frame_pitch, const sba_background_accumulate_opts& opts, const uint8_t* use,
+                           uint32_t* sum, uint64_t* sumsq, uint32_t* hot, uint8_t* vmax, uint64_t* n_used);
+int sba_bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                         int64_t row_pitch, int64_t frame_pitch, const uint8_t* level, const uint8_t* mask, int64_t out_row_pitch,
+                         int64_t out_frame_pitch, const sba_background_suppress_opts& opts, uint8_t* out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -472,6 +478,50 @@ int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, in
   return guarded(nullptr, [&] {
     return sba_undistort_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, *lens, new_k, out_height, out_width,
                               out_row_pitch, out_frame_pitch, o, out, flags_out, map_out);
+  });
+}
+
+int sba_background_accumulate(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                              int64_t row_pitch, int64_t frame_pitch, const sba_background_accumulate_opts* opts, const uint8_t* use,
+                              uint32_t* sum, uint64_t* sumsq, uint32_t* hot, uint8_t* vmax, uint64_t* n_used) {
+  const char* fn = "sba_background_accumulate";
+  sba_background_accumulate_opts o{};
+  o.channel = 1; o.threshold = 50;
+  if (opts) o = *opts;
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, o.threshold);
+  if (rc) return rc;
+  // 255 * 2^24 < 2^32: below it `sum` cannot overflow
+  if ((o.accumulate && n_used ? *n_used : 0) + (uint64_t)n_frames > ((uint64_t)1 << 24)) {
+    g_last_error = std::string(fn) + ": more than 2^24 frames in all (the bound under which the 32-bit sum cannot overflow)";
+    return SBA_ERR_UNSUPPORTED;
+  }
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc) return rc;
+  return guarded(nullptr, [&] {
+    return sba_bg_accumulate_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, use, sum, sumsq, hot, vmax,
+                                  n_used);
+  });
+}
+
+int sba_background_suppress(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                            int64_t row_pitch, int64_t frame_pitch, const uint8_t* level, const uint8_t* mask, int64_t out_row_pitch,
+                            int64_t out_frame_pitch, const sba_background_suppress_opts* opts, uint8_t* out) {
+  const char* fn = "sba_background_suppress";
+  sba_background_suppress_opts o{};
+  o.channel = 1;
+  if (opts) o = *opts;
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, 0);
+  if (rc) return rc;
+  if (o.mode != SBA_BG_GATE && o.mode != SBA_BG_SUBTRACT) return detect_invalid(fn, "mode must be 0 (gate) or 1 (subtract)");
+  if (!out && n_frames > 0) return detect_invalid(fn, "null out");
+  if (out_row_pitch < (int64_t)width) return detect_invalid(fn, "out_row_pitch is smaller than width");
+  if ((__int128)height * out_row_pitch > out_frame_pitch) return detect_invalid(fn, "out_frame_pitch is smaller than height * out_row_pitch");
+  if ((__int128)n_frames * out_frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * out_frame_pitch overflows");
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc || n_frames == 0) return rc;
+  return guarded(nullptr, [&] {
+    return sba_bg_suppress_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, level, mask, out_row_pitch,
+                                out_frame_pitch, o, out);
   });
 }
 

@@ -1,8 +1,9 @@
 // sba_detect.hip -- the kernels that work on video frames: the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
-// connected components) and the undistortion (sba_undistort.hpp).  They do not depend on the engine's camera model, so they
-// are compiled once, in a translation unit of their own.
+// connected components), the undistortion (sba_undistort.hpp) and the background statistics (sba_background.hpp).  They do not
+// depend on the engine's camera model, so they are compiled once, in a translation unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
+#include "sba_background.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -23,4 +24,18 @@ int sba_undistort_call(int device, const uint8_t* frames, int64_t n_frames, int3
                        uint8_t* flags_out, int32_t* map_out) {
   return sba_detect::undistort_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, lens, new_k, out_height,
                                     out_width, out_row_pitch, out_frame_pitch, opts, out, flags_out, map_out);
+}
+
+int sba_bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                           int64_t row_pitch, int64_t frame_pitch, const sba_background_accumulate_opts& opts, const uint8_t* use,
+                           uint32_t* sum, uint64_t* sumsq, uint32_t* hot, uint8_t* vmax, uint64_t* n_used) {
+  return sba_detect::bg_accumulate_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, opts, use, sum, sumsq,
+                                        hot, vmax, n_used);
+}
+
+int sba_bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                         int64_t row_pitch, int64_t frame_pitch, const uint8_t* level, const uint8_t* mask, int64_t out_row_pitch,
+                         int64_t out_frame_pitch, const sba_background_suppress_opts& opts, uint8_t* out) {
+  return sba_detect::bg_suppress_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, level, mask,
+                                      out_row_pitch, out_frame_pitch, opts, out);
 }

@@ -31,12 +31,42 @@ __all__ = ["green_laser_finder_faster", "find_laser_dots", "centroid_table", "La
            "SBA_BLOB_OK", "SBA_BLOB_NONE", "SBA_BLOB_OVERFLOW", "SBA_BLOB_REJECTED", "SBA_BLOB_MULTIPLE"]
 
 
+SUPPRESS_CHUNK_BYTES = 64 << 20     # one-channel frames held at a time when a background is taken out in front of a detector
+
+
+def _without_background(frames, background, channel, chunk_frames, device, detect, fields, make):
+    """Runs ``detect(one-channel frames)`` on the frames with the background taken out (gate mode), chunk by chunk, and joins
+    the results' ``fields`` with ``make``.  ``background``: an ``imaging.BackgroundModel`` or a ``(level, mask)`` pair."""
+    if hasattr(background, "suppress"):
+        if background.channel != channel:
+            raise ValueError(f"the background model was built on channel {background.channel}, the detector reads channel {channel}")
+        level, mask = background.level(), background.hot_mask()
+    else:
+        level, mask = background
+    _t, frames, B, H, W, _C, _sr, _sf = _native._frame_layout(frames, device)
+    step = int(chunk_frames) if chunk_frames > 0 else max(1, SUPPRESS_CHUNK_BYTES // max(1, H * W))
+    parts = []
+    for lo in range(0, max(B, 1), step):
+        clean = _native.background_suppress(frames[lo:lo + step], level=level, mask=mask, mode="gate", channel=channel, device=device)
+        parts.append(detect(clean))
+    return make(*(None if getattr(parts[0], f) is None else np.concatenate([getattr(p, f) for p in parts]) for f in fields))
+
+
 def find_laser_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_extent=0, roi_rect=None, roi_circle=None,
-                    chunk_frames=0, device=0) -> LaserDots:
+                    chunk_frames=0, device=0, background=None) -> LaserDots:
     """Moments, bounding box, centroids and status of the laser dot of every frame of a batch: ``_native.detect_dots``.
     ``frames`` is a uint8 numpy array or a torch tensor on the device, (B, H, W, C) or (B, H, W); a single (H, W, C) frame has
     to be passed as ``frame[None]``.  ``max_extent`` rejects frames whose bright pixels do not fit a box of that size (status
-    SPREAD): the one-pass stand-in for the one-connected-component rule of the reference's ``green_laser_finder``."""
+    SPREAD): the one-pass stand-in for the one-connected-component rule of the reference's ``green_laser_finder``.
+    ``background``: an ``imaging.BackgroundModel`` (its ``level()`` and ``hot_mask()``) or a ``(level, mask)`` pair of (H, W)
+    planes; the static light is then gated out chunk by chunk (sba_background_suppress) and the detector reads the one-channel
+    result, whose surviving pixels keep their values."""
+    if background is not None:
+        return _without_background(
+            frames, background, channel, chunk_frames, device,
+            lambda clean: _native.detect_dots(clean, threshold=threshold, channel=0, min_area=min_area, max_area=max_area,
+                                              max_extent=max_extent, roi_rect=roi_rect, roi_circle=roi_circle, device=device),
+            ("sums", "box", "centroid", "status"), LaserDots)
     return _native.detect_dots(frames, threshold=threshold, channel=channel, min_area=min_area, max_area=max_area,
                                max_extent=max_extent, roi_rect=roi_rect, roi_circle=roi_circle, chunk_frames=chunk_frames,
                                device=device)
@@ -93,10 +123,19 @@ def _disk_radius(footprint, default, name):
 
 def find_laser_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=4, max_blobs=8, min_area=0, max_area=0,
                      centre=None, max_centre_dist=0, roi_rect=None, roi_circle=None, chunk_frames=0, device=0,
-                     want_mask=False, want_labels=False) -> LaserBlobs:
+                     want_mask=False, want_labels=False, background=None) -> LaserBlobs:
     """The connected components of every frame of a batch and the verdict on each frame: ``_native.detect_blobs``.
     ``frames`` as for :func:`find_laser_dots`.  With the defaults (disk(1), disk(4), no filter) a frame's status is SBA_BLOB_OK
-    exactly when the reference's ``green_laser_finder`` returns a centroid, and ``centroid[:, :2]`` is that centroid as (x, y)."""
+    exactly when the reference's ``green_laser_finder`` returns a centroid, and ``centroid[:, :2]`` is that centroid as (x, y).
+    ``background`` as for :func:`find_laser_dots`."""
+    if background is not None:
+        return _without_background(
+            frames, background, channel, chunk_frames, device,
+            lambda clean: _native.detect_blobs(clean, threshold=threshold, channel=0, dilate_radius=dilate_radius, close_radius=close_radius,
+                                               max_blobs=max_blobs, min_area=min_area, max_area=max_area, centre=centre,
+                                               max_centre_dist=max_centre_dist, roi_rect=roi_rect, roi_circle=roi_circle, device=device,
+                                               want_mask=want_mask, want_labels=want_labels),
+            ("n_components", "blobs", "accepted", "centroid", "status", "mask", "labels"), LaserBlobs)
     return _native.detect_blobs(frames, threshold=threshold, channel=channel, dilate_radius=dilate_radius, close_radius=close_radius,
                                 max_blobs=max_blobs, min_area=min_area, max_area=max_area, centre=centre,
                                 max_centre_dist=max_centre_dist, roi_rect=roi_rect, roi_circle=roi_circle, chunk_frames=chunk_frames,

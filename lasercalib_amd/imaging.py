@@ -8,6 +8,8 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
 * :func:`optimal_new_camera_matrix`    -- ``cv.getOptimalNewCameraMatrix``: the camera matrix that keeps only valid pixels
   (alpha = 0), every source pixel (alpha = 1) or a blend; 81 points, on the host
 * :func:`invertible_region`            -- where the distortion model is locally invertible (the FOLDED flag), as a bool image
+* :class:`BackgroundModel`             -- what every pixel of a camera shows over a video (sba_background_accumulate) and the
+  removal of the light that is always there (sba_background_suppress), for rigs that cannot be made dark
 
 Sizes are ``(width, height)``, as in OpenCV.  Pixels follow the rule written out in include/sba_hip.h: a float64 model, the
 source position on a 1/32-pixel grid, integer bilinear weights.  That is OpenCV's scheme, but OpenCV rounds its weight table to
@@ -22,7 +24,7 @@ from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE
 
 SBA_UNDIST_OUTSIDE, SBA_UNDIST_FOLDED, SBA_UNDIST_RANGE = UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE
 
-__all__ = ["Lens", "undistort_frames", "optimal_new_camera_matrix", "invertible_region",
+__all__ = ["Lens", "undistort_frames", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
            "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
 
 
@@ -219,3 +221,124 @@ def optimal_new_camera_matrix(lens, image_size, alpha, new_size=None):
     x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, nw - 1), min(y1, nh - 1)
     roi = (x0, y0, max(x1 - x0 + 1, 0), max(y1 - y0 + 1, 0))
     return K_new, roi
+
+
+class BackgroundModel:
+    """Per-pixel statistics over time of one channel of one camera's frames, and what follows from them.
+
+    The laser dot visits a pixel in a handful of frames; a status LED, a leaking illuminator or a reflection is there in all of
+    them.  ``add`` streams frames through sba_background_accumulate (exact integers: the sum, the square sum, the number of
+    frames above ``threshold`` and the maximum of every pixel; any batching gives the same bits), ``level`` and ``hot_mask``
+    turn the statistics into a per-pixel level and a mask of the pixels that are lit too often, and ``suppress`` takes both out
+    of a batch of frames (sba_background_suppress) -> one-channel frames for the detectors, which
+    ``feature_detection.find_laser_dots`` / ``find_laser_blobs`` do by themselves when given ``background=model``.
+
+    ``on_device=True`` keeps the accumulators in device memory (torch tensors on ``device``, created with the first ``add``);
+    otherwise they are numpy arrays.  ``state()`` / ``from_state`` give and take a dict of plain numpy arrays, to be pickled
+    next to the centroids."""
+
+    _KINDS = (("sum", np.uint32), ("sumsq", np.uint64), ("hot", np.uint32), ("vmax", np.uint8))
+
+    def __init__(self, height, width, channel=1, threshold=50, device=0, on_device=True):
+        self.height, self.width, self.channel, self.threshold = int(height), int(width), int(channel), int(threshold)
+        self.device, self.on_device = int(device), bool(on_device)
+        if not (0 <= self.height <= _native.DOT_MAX_DIM and 0 <= self.width <= _native.DOT_MAX_DIM):
+            raise ValueError(f"height and width must be within 0..{_native.DOT_MAX_DIM}, got {(height, width)}")
+        if not 0 <= self.threshold <= 255:
+            raise ValueError(f"threshold must be in 0..255, got {threshold}")
+        self.n = 0
+        self._acc = {name: np.zeros((self.height, self.width), dt) for name, dt in self._KINDS}
+
+    # ---- accumulators
+    def _numpy(self, name):
+        a = self._acc[name]
+        if _native._is_tensor(a):
+            a = a.cpu().numpy().view(dict(self._KINDS)[name])
+        return a
+
+    def _to_device(self):
+        import torch
+        signed = {"sum": np.int32, "sumsq": np.int64, "hot": np.int32, "vmax": np.uint8}      # the same bits
+        for name, a in self._acc.items():
+            if not _native._is_tensor(a):
+                self._acc[name] = torch.from_numpy(a.view(signed[name])).to(f"cuda:{self.device}")
+
+    def add(self, frames, use=None):
+        """Adds the frames (uint8 (B, H, W, C) or (B, H, W), numpy or a tensor on the device) whose ``use`` flag is set -- None:
+        all -- to the statistics.  Returns self."""
+        _t, _f, _B, H, W, _C, _sr, _sf = _native._frame_layout(frames, self.device)
+        if (H, W) != (self.height, self.width):
+            raise ValueError(f"frames are {H} x {W}, the model is {self.height} x {self.width}")
+        if self.on_device:
+            self._to_device()
+        self.n = _native.background_accumulate(frames, n_used=self.n, use=use, threshold=self.threshold, channel=self.channel,
+                                               accumulate=True, device=self.device, **self._acc)
+        return self
+
+    def state(self):
+        """A dict of plain numbers and numpy arrays that ``from_state`` turns back into the model."""
+        out = {k: getattr(self, k) for k in ("height", "width", "channel", "threshold", "n")}
+        out.update({name: self._numpy(name).copy() for name, _dt in self._KINDS})
+        return out
+
+    @classmethod
+    def from_state(cls, state, device=0, on_device=True):
+        m = cls(state["height"], state["width"], channel=state["channel"], threshold=state["threshold"], device=device, on_device=on_device)
+        m.n = int(state["n"])
+        if not 0 <= m.n <= _native.BG_MAX_FRAMES:
+            raise ValueError(f"n must be within 0..2^24, got {m.n}")
+        for name, dt in cls._KINDS:
+            a = np.ascontiguousarray(state[name], dtype=dt)
+            if a.shape != (m.height, m.width):
+                raise ValueError(f"{name} has the shape {a.shape}, expected {(m.height, m.width)}")
+            m._acc[name] = a.copy()
+        return m
+
+    # ---- what the statistics say (host, float64: H x W arithmetic once per video)
+    def _need_frames(self):
+        if self.n <= 0:
+            raise ValueError("the model has seen no frame yet")
+
+    def mean(self):
+        self._need_frames()
+        return self._numpy("sum").astype(np.float64) / self.n
+
+    def std(self):
+        """sqrt(max(sumsq / n - mean^2, 0)): the population standard deviation."""
+        mean = self.mean()
+        return np.sqrt(np.maximum(self._numpy("sumsq").astype(np.float64) / self.n - mean * mean, 0.0))
+
+    def max(self):
+        return self._numpy("vmax").copy()
+
+    def hot_fraction(self):
+        """The fraction of the frames in which the pixel was above the threshold."""
+        self._need_frames()
+        return self._numpy("hot").astype(np.float64) / self.n
+
+    def level(self, k_sigma=4.0, margin=4):
+        """clip(ceil(mean + k_sigma * std) + margin, 0, 255) as uint8: what a pixel has to exceed to be more than its background.
+        The dot's own visits are part of the statistics: a pixel it lit once with the value v in n frames has about
+        v (1 / n + k_sigma / sqrt(n)), which stays below v -- the dot passes its own level -- from some twenty frames on at
+        k_sigma = 4; a video has thousands."""
+        return np.clip(np.ceil(self.mean() + float(k_sigma) * self.std()) + margin, 0, 255).astype(np.uint8)
+
+    def hot_mask(self, fraction=0.05, grow=0):
+        """1 where the pixel was above the threshold in more than ``fraction`` of the frames (the dot passes, a lamp stays),
+        dilated by ``disk(grow)``; uint8."""
+        self._need_frames()
+        mask = self._numpy("hot") > float(fraction) * self.n
+        if grow:
+            from scipy import ndimage
+            r = int(grow)
+            d = np.arange(-r, r + 1)
+            mask = ndimage.binary_dilation(mask, structure=d[:, None] ** 2 + d[None, :] ** 2 <= r * r)
+        return mask.astype(np.uint8)
+
+    def suppress(self, frames, mode="gate", level=None, mask=None, out=None, chunk_frames=0):
+        """The model's channel of ``frames`` without the static light -> (B, H, W) uint8 on the side the frames are on.
+        ``level`` / ``mask``: (H, W) planes, None = ``self.level()`` / ``self.hot_mask()`` with their defaults."""
+        level = self.level() if level is None else level
+        mask = self.hot_mask() if mask is None else mask
+        return _native.background_suppress(frames, level=level, mask=mask, mode=mode, channel=self.channel, out=out,
+                                           chunk_frames=chunk_frames, device=self.device)
