@@ -800,6 +800,58 @@ int sba_background_suppress(int device, const uint8_t* frames, int64_t n_frames,
                             int64_t out_row_pitch /*bytes, >= width*/, int64_t out_frame_pitch /*bytes, >= height*out_row_pitch*/,
                             const sba_background_suppress_opts* opts /*NULL: {1, 0...}*/, uint8_t* out);
 
+/* ---------------------------------------------------------------- decoder frames: YUV 4:2:0 to BGR or one plane
+ * Every decoder of the reference's .mp4 videos produces 8-bit YUV 4:2:0 (ffmpeg's yuv420p / nv12, PyAV planes, a hardware
+ * decoder's NV12 surfaces in device memory); the reference converts on the host (-pix_fmt rgb24, cv.VideoCapture.read) and
+ * then reads one byte in three.  sba_convert_frames converts a batch of such frames into interleaved 3- or 4-channel frames or
+ * into ONE plane, the input of the frame functions above (channels = 1, channel = 0).  Stateless: no handle.
+ *
+ * The source is three plane pointers.  Luma sample (x, y) of frame f is y[f y_frame_pitch + y y_row_pitch + x]; the chroma
+ * planes have (height + 1) / 2 rows of (width + 1) / 2 samples (odd sizes are allowed) and share their pitches and c_step, the
+ * bytes between neighbouring samples of a row: sample (i, j) is u[f c_frame_pitch + j c_row_pitch + i c_step], v likewise.
+ *   NV12: u = uv, v = uv + 1, c_step = 2       NV21: u = vu + 1, v = vu, c_step = 2       I420 / YV12: three planes, c_step = 1
+ * Any base address, any pitch that holds a row.  The planes are all host memory, or with frames_on_device all device memory
+ * of `device`, read in place.  The output has `height` rows of `width` pixels, row r of frame f at
+ * out + f out_frame_pitch + r out_row_pitch, in host memory or with out_on_device in device memory, written in place; the
+ * padding between rows and frames is never written.
+ *
+ * The rule per pixel (x, y) -- this is the function's definition:
+ *   Y = y_plane[y][x];  U = u_plane[y >> 1][x >> 1];  V = v_plane[y >> 1][x >> 1]     (nearest chroma, OpenCV's choice)
+ *   l = max(Y - y_offset, 0) * cy;   u = U - 128;   v = V - 128
+ *   R = clip255((l + cvr*v         + 2^19) >> 20)
+ *   G = clip255((l + cug*u + cvg*v + 2^19) >> 20)
+ *   B = clip255((l + cub*u         + 2^19) >> 20)          (>> is the arithmetic shift: floor; clip255(s) = min(max(s, 0), 255))
+ * y_offset, cy, cvr, cug, cvg, cub are the integers of *matrix; NULL is the table of OpenCV's cvtColor(COLOR_YUV2BGR_NV12 /
+ * _I420), {16, 1220542, 1673527, -409993, -852492, 2116026}: 1.164, 1.596, -0.391, -0.813 and 2.018 times 2^20, rounded.
+ * A matrix must have y_offset in 0..255 and, for each of its three output rows with the chroma coefficients a and b (the
+ * missing one 0), 255 |cy| + 128 (|a| + |b|) + 2^19 < 2^31: then every sum above fits 32 bits.
+ * out_format (sba_pixel_format): BGR, RGB (3 bytes a pixel, in that order), BGRA, RGBA (4 bytes, A = 255), or the single plane
+ * B, G or R (1 byte a pixel).
+ * Frames pass through the device in chunks (host planes through two staging buffers, a host output through one more); device
+ * memory does not grow with n_frames, and any chunk_frames gives the same bytes.  n_frames = 0 returns SBA_OK and writes
+ * nothing.
+ * Errors, all checked before any device work (text in sba_last_error(NULL)), out left untouched: SBA_ERR_INVALID for a
+ * negative size, a NULL plane or a NULL out with n_frames > 0, a c_step that is not 1 or 2, y_row_pitch < width,
+ * c_row_pitch < c_step ((width + 1) / 2 - 1) + 1, a frame pitch smaller than the plane's rows times its row pitch,
+ * out_row_pitch < width times the bytes of a pixel, out_frame_pitch < height out_row_pitch, an unknown out_format and a matrix
+ * outside the bound; SBA_ERR_UNSUPPORTED for width or height above 16384; SBA_ERR_NO_DEVICE as everywhere. */
+typedef enum {
+  SBA_PIX_BGR = 0, SBA_PIX_RGB = 1, SBA_PIX_BGRA = 2, SBA_PIX_RGBA = 3, SBA_PIX_B = 4, SBA_PIX_G = 5, SBA_PIX_R = 6
+} sba_pixel_format;
+typedef struct { int32_t y_offset, cy, cvr, cug, cvg, cub; } sba_yuv_matrix;
+typedef struct {
+  int32_t frames_on_device;  /* 1: y, u and v are device pointers on `device`  */
+  int32_t out_on_device;     /* 1: `out` is a device pointer on `device`       */
+  int32_t out_format;        /* sba_pixel_format                               */
+  int32_t chunk_frames;      /* frames per chunk at most; <= 0 = library default */
+  int32_t reserved[8];
+} sba_convert_opts;
+int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height,
+                       int32_t width, int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch,
+                       int32_t c_step /*1 or 2*/, const sba_yuv_matrix* matrix /*NULL: OpenCV's BT.601 table*/,
+                       int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts* opts /*NULL: all zero*/,
+                       uint8_t* out);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
-    "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress",
+    "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames",
 )
 
 
@@ -162,6 +162,33 @@ BG_MAX_FRAMES = 1 << 24                                                    # fra
 # in a chunk of more than BG_SPLIT_FRAMES frames
 BG_SPLIT_GROUPS, BG_SPLIT_FRAMES = 65536, 16
 BG_STAT_BYTES = {"sum": 4, "sumsq": 8, "hot": 4, "vmax": 1}               # bytes of a value of each accumulator
+
+
+class YuvMatrix(C.Structure):                                             # sba_yuv_matrix
+    _fields_ = [(n, C.c_int32) for n in ("y_offset", "cy", "cvr", "cug", "cvg", "cub")]
+
+
+class ConvertOpts(C.Structure):                                           # sba_convert_opts
+    _fields_ = [("frames_on_device", C.c_int32), ("out_on_device", C.c_int32), ("out_format", C.c_int32),
+                ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+PIXEL_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "b": 4, "g": 5, "r": 6}      # sba_pixel_format
+PIXEL_BYTES = {"bgr": 3, "rgb": 3, "bgra": 4, "rgba": 4, "b": 1, "g": 1, "r": 1}
+YUV_FORMATS = ("nv12", "nv21", "i420", "yv12")
+YUV_BT601 = (16, 1220542, 1673527, -409993, -852492, 2116026)             # OpenCV's table: what a NULL matrix means
+# geometry of the kernel (csrc/sba_convert.hpp), for the tests that straddle it: the pixels of a row a lane owns, the pixels a
+# wave spans, the rows of a workgroup's tile
+CONVERT_RUN, CONVERT_WAVE_COLS, CONVERT_TILE_ROWS = 16, 512, 16
+
+
+def yuv_matrix_in_bound(m):
+    """Whether the six integers (y_offset, cy, cvr, cug, cvg, cub) are a matrix sba_convert_frames accepts: 32-bit values,
+    y_offset in 0..255 and 255 |cy| + 128 (|a| + |b|) + 2^19 < 2^31 for each output row's chroma coefficients a, b."""
+    y_offset, cy, cvr, cug, cvg, cub = (int(v) for v in m)
+    if any(not -(1 << 31) <= v < (1 << 31) for v in (cy, cvr, cug, cvg, cub)) or not 0 <= y_offset <= 255:
+        return False
+    return all(255 * abs(cy) + 128 * ab + (1 << 19) < (1 << 31) for ab in (abs(cvr), abs(cug) + abs(cvg), abs(cub)))
 
 
 class AlignOpts(C.Structure):
@@ -454,6 +481,9 @@ def load():
                                                 C.POINTER(C.c_uint64)]),
         "sba_background_suppress": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BgSuppressOpts), C.c_void_p]),
+        "sba_convert_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_int64, C.c_int64, C.c_int32, C.POINTER(YuvMatrix), C.c_int64, C.c_int64,
+                                         C.POINTER(ConvertOpts), C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
         "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
         "sba_reproj_stats": (C.c_int, [H, C.POINTER(ReprojOpts), dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(ReprojReport)]),
@@ -858,6 +888,177 @@ def background_suppress(frames, level=None, mask=None, mode="gate", channel=1, o
         torch.cuda.current_stream(device).synchronize()      # frames, level and mask are complete before the library reads them
     ptr, optr = (frames.data_ptr(), out.data_ptr()) if tensor else (frames.ctypes.data, out.ctypes.data)
     _check(lib.sba_background_suppress(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, *ptrs, osr, osf, C.byref(opts), C.c_void_p(optr)))
+    return out
+
+
+class YuvLayout:
+    """What sba_convert_frames is told about a batch of YUV 4:2:0 frames: the addresses of the three planes, their pitches in
+    bytes and the chroma step; ``keep`` holds the objects that own the memory."""
+
+    __slots__ = ("tensor", "n_frames", "height", "width", "y", "u", "v", "y_row_pitch", "y_frame_pitch", "c_row_pitch",
+                 "c_frame_pitch", "c_step", "keep")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def _bytes_view(name, a, device):
+    """(is a tensor, the object, base address, shape, strides in bytes) of a uint8 numpy array or tensor on ``device``."""
+    if _is_tensor(a):
+        if not a.is_cuda or (a.device.index or 0) != device:
+            raise ValueError(f"{name}: the tensor must live on cuda:{device}")
+        if str(a.dtype) != "torch.uint8":
+            raise ValueError(f"{name}: the tensor must be uint8, not {a.dtype}")
+        return True, a, a.data_ptr(), tuple(int(v) for v in a.shape), tuple(int(v) for v in a.stride())
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise ValueError(f"{name} must be uint8, not {a.dtype}")
+    return False, a, a.ctypes.data, tuple(int(v) for v in a.shape), tuple(int(v) for v in a.strides)
+
+
+def _plane_pitches(name, shape, strides, steps):
+    """(frame pitch, row pitch, step) of a (B, rows, cols) plane whose samples lie ``step`` bytes apart, step in ``steps``.  The
+    strides of an axis of length 1, and all strides of an empty plane, say nothing: those of a packed plane are taken."""
+    B, R, Cl = shape
+    sf, sr, sp = strides
+    empty = B * R * Cl == 0
+    sp = steps[0] if Cl == 1 or empty else sp
+    if sp not in steps:
+        raise ValueError(f"{name}: neighbouring samples of a row must lie {' or '.join(str(s) for s in steps)} byte(s) apart, got {sp}")
+    row = sp * (Cl - 1) + 1 if Cl else 0
+    sr = row if R == 1 or empty else sr
+    sf = R * sr if B == 1 or empty else sf
+    if sr < row or sf < R * sr:
+        raise ValueError(f"{name}: rows and frames must be in ascending order and must not overlap; got strides {strides} for shape {shape}")
+    return sf, sr, sp
+
+
+def _yuv_layout(frames, pixel_format, device=0):
+    """Reads the layout of a batch of 8-bit YUV 4:2:0 frames -> YuvLayout.  ``pixel_format``: "nv12", "nv21" (a luma plane and one
+    plane of interleaved UV / VU pairs) or "i420", "yv12" (a luma plane and two chroma planes, U first / V first).  ``frames``:
+
+    * a tuple of planes in the format's order -- ``(y, uv)``, or ``(y, u, v)`` (yv12: ``(y, v, u)``) -- with y (B, H, W), uv
+      (B, ceil(H / 2), ceil(W / 2), 2) and u, v (B, ceil(H / 2), ceil(W / 2)); any row and frame strides; the samples of a planar
+      chroma row 1 or 2 bytes apart (``uv[..., 0]`` is a plane), the two chroma planes with equal strides; H and W may be odd;
+    * one stacked array (B, H + ceil(H / 2), W), as ffmpeg's rawvideo pipe delivers ``nv12`` and ``yuv420p`` frames: the luma
+      rows, then the chroma.  nv12 / nv21 need an even W (a chroma row is 2 ceil(W / 2) bytes).  i420 / yv12 need even W and H and
+      packed rows (row stride W): their chroma rows are half rows of one packed buffer."""
+    fmt = str(pixel_format).lower()
+    if fmt not in YUV_FORMATS:
+        raise ValueError(f"pixel_format must be one of {YUV_FORMATS}, not {pixel_format!r}")
+    semi, first_is_u = fmt in ("nv12", "nv21"), fmt in ("nv12", "i420")
+    if isinstance(frames, (tuple, list)):
+        if len(frames) != (2 if semi else 3):
+            raise ValueError(f"{fmt}: expected a tuple of {'(y, uv)' if semi else '(y, u, v)'} planes, got {len(frames)} planes")
+        views = [_bytes_view(n, a, device) for n, a in zip(("y", "chroma", "chroma 2"), frames)]
+        if len({t for t, *_ in views}) != 1:
+            raise ValueError("the planes must all be numpy arrays or all be tensors on the device")
+        tensor, yobj, yptr, yshape, ystr = views[0]
+        if len(yshape) != 3:
+            raise ValueError(f"y must be (B, H, W), got the shape {yshape}")
+        B, H, W = yshape
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        ysf, ysr, _one = _plane_pitches("y", yshape, ystr, (1,))
+        if semi:
+            _t, cobj, cptr, cshape, cstr = views[1]
+            if cshape != (B, ch, cw, 2):
+                raise ValueError(f"uv must be {(B, ch, cw, 2)} for y of {yshape}, got the shape {cshape}")
+            if B * ch * cw and cstr[3] != 1:
+                raise ValueError(f"uv: the two bytes of a pair must be neighbours, got strides {cstr}")
+            csf, csr, step = _plane_pitches("uv", (B, ch, 2 * cw), (cstr[0], cstr[1], 1), (1,))
+            step, first, second = 2, cptr, cptr + 1
+            if B * ch * cw and cw > 1 and cstr[2] != 2:
+                raise ValueError(f"uv: pairs must be contiguous (stride 2), got strides {cstr}")
+        else:
+            (_t1, c1, p1, s1, st1), (_t2, c2, p2, s2, st2) = views[1], views[2]
+            if s1 != (B, ch, cw) or s2 != (B, ch, cw):
+                raise ValueError(f"the chroma planes must be {(B, ch, cw)} for y of {yshape}, got the shapes {s1} and {s2}")
+            csf, csr, step = _plane_pitches("chroma", s1, st1, (1, 2))
+            if _plane_pitches("chroma 2", s2, st2, (step,)) != (csf, csr, step):
+                raise ValueError(f"the two chroma planes must have the same strides, got {st1} and {st2}")
+            first, second = p1, p2
+        keep = tuple(v[1] for v in views)
+    else:
+        tensor, obj, ptr, shape, strides = _bytes_view("frames", frames, device)
+        if len(shape) != 3:
+            raise ValueError(f"frames must be a tuple of planes or one stacked (B, H + ceil(H / 2), W) array, got the shape {shape}")
+        B, T, W = shape
+        ysf, ysr, _one = _plane_pitches("frames", shape, strides, (1,))
+        k, rem = divmod(T, 3)
+        if rem == 1:
+            raise ValueError(f"stacked frames have H + ceil(H / 2) rows; {T} rows fit no H")
+        H = 2 * k + (1 if rem else 0)
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        if semi:
+            if W % 2:
+                raise ValueError(f"stacked {fmt} frames need an even width (a chroma row is 2 ceil(W / 2) bytes), got {W}; "
+                                 "pass a tuple of planes instead")
+            first, second, step, csr, csf = ptr + H * ysr, ptr + H * ysr + 1, 2, ysr, ysf
+        else:
+            if W % 2 or H % 2:
+                raise ValueError(f"stacked {fmt} frames need an even width and height, got {W} x {H}; pass a tuple of planes instead")
+            if ysr != W and B * T * W:
+                raise ValueError(f"stacked {fmt} frames need packed rows (row stride {W}), got {ysr}; pass a tuple of planes instead")
+            first, step, csr, csf = ptr + H * W, 1, W // 2, ysf
+            second = first + ch * cw
+        yptr, keep = ptr, (obj,)
+    u, v = (first, second) if first_is_u else (second, first)
+    return YuvLayout(tensor=tensor, n_frames=B, height=H, width=W, y=yptr, u=u, v=v, y_row_pitch=ysr, y_frame_pitch=ysf,
+                     c_row_pitch=csr, c_frame_pitch=csf, c_step=step, keep=keep)
+
+
+def yuv_frame_slice(frames, lo, hi):
+    """The frames [lo, hi) of a batch given as a tuple of planes or as a stacked array."""
+    return tuple(p[lo:hi] for p in frames) if isinstance(frames, (tuple, list)) else frames[lo:hi]
+
+
+def convert_frames(frames, pixel_format, out_format="bgr", matrix=None, out=None, out_on_device=None, chunk_frames=0, device=0):
+    """sba_convert_frames (include/sba_hip.h): 8-bit YUV 4:2:0 ``frames`` (see ``_yuv_layout``; numpy, or torch tensors on
+    ``device`` read in place) -> (B, H, W, 3 | 4) frames of ``out_format`` "bgr", "rgb", "bgra", "rgba", or the (B, H, W) plane
+    "b", "g", "r".  ``matrix``: the six integers (y_offset, cy, cvr, cug, cvg, cub) or None for OpenCV's BT.601 table.  The
+    result is allocated on the side the source is on (``out_on_device`` True / False overrides that), or is the caller's
+    ``out``: a writeable numpy array or a tensor on ``device`` of that shape, any row and frame strides, padding left untouched.
+    ``lasercalib_amd.imaging.convert_frames`` is the public face of this call."""
+    lib = load()
+    L = _yuv_layout(frames, pixel_format, device)
+    fmt = str(out_format).lower()
+    if fmt not in PIXEL_FORMATS:
+        raise ValueError(f"out_format must be one of {sorted(PIXEL_FORMATS)}, not {out_format!r}")
+    Cn = PIXEL_BYTES[fmt]
+    B, H, W = L.n_frames, L.height, L.width
+    shape = (B, H, W) if Cn == 1 else (B, H, W, Cn)
+    m = None
+    if matrix is not None:
+        vals = [int(v) for v in matrix]
+        if len(vals) != 6 or any(not -(1 << 31) <= v < (1 << 31) for v in vals):
+            raise ValueError(f"matrix must be six 32-bit integers (y_offset, cy, cvr, cug, cvg, cub), got {matrix!r}")
+        m = YuvMatrix(*vals)
+    if out is not None:
+        out_tensor = _is_tensor(out)
+        if not out_tensor and not (isinstance(out, np.ndarray) and out.flags.writeable):
+            raise ValueError("out must be a writeable numpy array or a tensor on the device")
+        if tuple(out.shape) not in (shape, (B, H, W, Cn)):
+            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shape}")
+        _t, _o, _B, _H, _W, _C, osr, osf = _frame_layout(out, device)
+    else:
+        out_tensor = L.tensor if out_on_device is None else bool(out_on_device)
+        if out_tensor:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{device}")
+        else:
+            out = np.empty(shape, np.uint8)
+        osr, osf = W * Cn, H * W * Cn
+    opts = ConvertOpts()
+    opts.frames_on_device, opts.out_on_device = 1 if L.tensor else 0, 1 if out_tensor else 0
+    opts.out_format, opts.chunk_frames = PIXEL_FORMATS[fmt], int(chunk_frames)
+    if L.tensor or out_tensor:
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # planes and out are complete before the library touches them
+    optr = out.data_ptr() if out_tensor else out.ctypes.data
+    _check(lib.sba_convert_frames(device, C.c_void_p(L.y), C.c_void_p(L.u), C.c_void_p(L.v), B, H, W, L.y_row_pitch, L.y_frame_pitch,
+                                  L.c_row_pitch, L.c_frame_pitch, L.c_step, None if m is None else C.byref(m), osr, osf, C.byref(opts),
+                                  C.c_void_p(optr)))
     return out
 
 

@@ -30,6 +30,10 @@ int sba_bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frames, 
 int sba_bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                          int64_t row_pitch, int64_t frame_pitch, const uint8_t* level, const uint8_t* mask, int64_t out_row_pitch,
                          int64_t out_frame_pitch, const sba_background_suppress_opts& opts, uint8_t* out);
+int sba_convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height, int32_t width,
+                     int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step,
+                     const sba_yuv_matrix& matrix, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& opts,
+                     uint8_t* out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -522,6 +526,50 @@ int sba_background_suppress(int device, const uint8_t* frames, int64_t n_frames,
   return guarded(nullptr, [&] {
     return sba_bg_suppress_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, level, mask, out_row_pitch,
                                 out_frame_pitch, o, out);
+  });
+}
+
+int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height, int32_t width,
+                       int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step,
+                       const sba_yuv_matrix* matrix, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts* opts,
+                       uint8_t* out) {
+  const char* fn = "sba_convert_frames";
+  sba_convert_opts o{};
+  if (opts) o = *opts;
+  sba_yuv_matrix m{16, 1220542, 1673527, -409993, -852492, 2116026};      // OpenCV's cvtColor(COLOR_YUV2BGR_NV12 / _I420)
+  if (matrix) m = *matrix;
+  if (n_frames < 0 || height < 0 || width < 0) return detect_invalid(fn, "negative size");
+  if (n_frames > 0 && (!y || !u || !v)) return detect_invalid(fn, "null plane");
+  if (n_frames > 0 && !out) return detect_invalid(fn, "null out");
+  if (c_step != 1 && c_step != 2) return detect_invalid(fn, "c_step must be 1 (planar) or 2 (interleaved)");
+  if (o.out_format < SBA_PIX_BGR || o.out_format > SBA_PIX_R) return detect_invalid(fn, "unknown out_format");
+  {   // every sum of the rule fits 32 bits: 255 |cy| + 128 (|a| + |b|) + 2^19 < 2^31 for each output row
+    auto mag = [](int32_t c) { return c < 0 ? -(int64_t)c : (int64_t)c; };
+    const int64_t rows[3] = {mag(m.cvr), mag(m.cug) + mag(m.cvg), mag(m.cub)};
+    if (m.y_offset < 0 || m.y_offset > 255) return detect_invalid(fn, "matrix: y_offset must be in 0..255");
+    for (int64_t ab : rows)
+      if (255 * mag(m.cy) + 128 * ab + ((int64_t)1 << 19) >= ((int64_t)1 << 31))
+        return detect_invalid(fn, "matrix: 255 |cy| + 128 (|a| + |b|) + 2^19 must stay below 2^31 for every output row");
+  }
+  const int64_t cw = ((int64_t)width + 1) / 2, ch = ((int64_t)height + 1) / 2, px = o.out_format <= SBA_PIX_RGB ? 3 : o.out_format <= SBA_PIX_RGBA ? 4 : 1;
+  if (y_row_pitch < width) return detect_invalid(fn, "y_row_pitch is smaller than width");
+  if ((__int128)height * y_row_pitch > y_frame_pitch) return detect_invalid(fn, "y_frame_pitch is smaller than height * y_row_pitch");
+  if (cw > 0 && c_row_pitch < c_step * (cw - 1) + 1) return detect_invalid(fn, "c_row_pitch is smaller than c_step * ((width + 1) / 2 - 1) + 1");
+  if (c_row_pitch < 0 || (__int128)ch * c_row_pitch > c_frame_pitch) return detect_invalid(fn, "c_frame_pitch is smaller than ((height + 1) / 2) * c_row_pitch");
+  if (out_row_pitch < width * px) return detect_invalid(fn, "out_row_pitch is smaller than width * bytes of a pixel");
+  if ((__int128)height * out_row_pitch > out_frame_pitch) return detect_invalid(fn, "out_frame_pitch is smaller than height * out_row_pitch");
+  if ((__int128)n_frames * y_frame_pitch > INT64_MAX || (__int128)n_frames * c_frame_pitch > INT64_MAX ||
+      (__int128)n_frames * out_frame_pitch > INT64_MAX)
+    return detect_invalid(fn, "n_frames * a frame pitch overflows");
+  if (height > 16384 || width > 16384) {
+    g_last_error = std::string(fn) + ": width and height are limited to 16384";
+    return SBA_ERR_UNSUPPORTED;
+  }
+  const int rc = check_device(device);
+  if (rc || n_frames == 0) return rc;
+  return guarded(nullptr, [&] {
+    return sba_convert_call(device, y, u, v, n_frames, height, width, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, m,
+                            out_row_pitch, out_frame_pitch, o, out);
   });
 }
 

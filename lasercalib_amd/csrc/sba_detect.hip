@@ -1,9 +1,11 @@
 // sba_detect.hip -- the kernels that work on video frames: the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
-// connected components), the undistortion (sba_undistort.hpp) and the background statistics (sba_background.hpp).  They do not
-// depend on the engine's camera model, so they are compiled once, in a translation unit of their own.
+// connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp) and the
+// conversion of decoder frames (sba_convert.hpp).  They do not depend on the engine's camera model, so they are compiled once,
+// in a translation unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
 #include "sba_background.hpp"
+#include "sba_convert.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -38,4 +40,12 @@ int sba_bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, in
                          int64_t out_frame_pitch, const sba_background_suppress_opts& opts, uint8_t* out) {
   return sba_detect::bg_suppress_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, level, mask,
                                       out_row_pitch, out_frame_pitch, opts, out);
+}
+
+int sba_convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height, int32_t width,
+                     int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step,
+                     const sba_yuv_matrix& matrix, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& opts,
+                     uint8_t* out) {
+  return sba_detect::convert_call(device, y, u, v, n_frames, height, width, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step,
+                                  matrix, out_row_pitch, out_frame_pitch, opts, out);
 }

@@ -12,7 +12,8 @@
 
 The reference thresholds the green channel with ``cv.threshold(green, t, 255, 0)`` and takes ``cv.moments`` of the result:
 m00 = 255 n, m10 = 255 sum x, m01 = 255 sum y over the n pixels above t, and returns ``(int(m01 / m00), int(m10 / m00))`` =
-``(sum y // n, sum x // n)`` -- (row, col).  Video decoding stays with the caller.
+``(sum y // n, sum x // n)`` -- (row, col).  Video decoding stays with the caller; what the decoder produced -- YUV 4:2:0 -- can be passed as it is with
+``pixel_format=`` (sba_convert_frames turns it into the detector's plane on the device).
 """
 from __future__ import annotations
 
@@ -34,39 +35,68 @@ __all__ = ["green_laser_finder_faster", "find_laser_dots", "centroid_table", "La
 SUPPRESS_CHUNK_BYTES = 64 << 20     # one-channel frames held at a time when a background is taken out in front of a detector
 
 
-def _without_background(frames, background, channel, chunk_frames, device, detect, fields, make):
-    """Runs ``detect(one-channel frames)`` on the frames with the background taken out (gate mode), chunk by chunk, and joins
-    the results' ``fields`` with ``make``.  ``background``: an ``imaging.BackgroundModel`` or a ``(level, mask)`` pair."""
+def _level_and_mask(background, channel):
+    """(level, mask) of an ``imaging.BackgroundModel`` built on ``channel`` or of a ``(level, mask)`` pair."""
     if hasattr(background, "suppress"):
         if background.channel != channel:
             raise ValueError(f"the background model was built on channel {background.channel}, the detector reads channel {channel}")
-        level, mask = background.level(), background.hot_mask()
-    else:
-        level, mask = background
+        return background.level(), background.hot_mask()
+    level, mask = background
+    return level, mask
+
+
+def _join(parts, fields, make):
+    return make(*(None if getattr(parts[0], f) is None else np.concatenate([getattr(p, f) for p in parts]) for f in fields))
+
+
+def _without_background(frames, background, channel, chunk_frames, device, detect, fields, make):
+    """Runs ``detect(one-channel frames)`` on the frames with the background taken out (gate mode), chunk by chunk, and joins
+    the results' ``fields`` with ``make``.  ``background``: an ``imaging.BackgroundModel`` or a ``(level, mask)`` pair."""
+    level, mask = _level_and_mask(background, channel)
     _t, frames, B, H, W, _C, _sr, _sf = _native._frame_layout(frames, device)
     step = int(chunk_frames) if chunk_frames > 0 else max(1, SUPPRESS_CHUNK_BYTES // max(1, H * W))
     parts = []
     for lo in range(0, max(B, 1), step):
         clean = _native.background_suppress(frames[lo:lo + step], level=level, mask=mask, mode="gate", channel=channel, device=device)
         parts.append(detect(clean))
-    return make(*(None if getattr(parts[0], f) is None else np.concatenate([getattr(p, f) for p in parts]) for f in fields))
+    return _join(parts, fields, make)
+
+
+def _from_decoder_frames(frames, pixel_format, matrix, background, channel, chunk_frames, device, detect, fields, make):
+    """Runs ``detect(one-channel frames)`` on YUV 4:2:0 frames (``imaging.convert_frames`` describes them): chunk by chunk they are
+    converted on the device to the plane ``channel`` names (0, 1, 2 = B, G, R; sba_convert_frames), the background, if any, is
+    gated out of that plane, and the results' ``fields`` are joined with ``make``.  One chunk of one-channel frames is held on
+    the device at a time, whatever the length of the video."""
+    from . import imaging
+    level, mask = (None, None) if background is None else _level_and_mask(background, channel)
+    parts = []
+    for _lo, _hi, plane in imaging.planes_in_chunks(frames, pixel_format, matrix, channel, chunk_frames, device):
+        if background is not None:
+            plane = _native.background_suppress(plane, level=level, mask=mask, mode="gate", channel=0, device=device)
+        parts.append(detect(plane))
+    return _join(parts, fields, make)
 
 
 def find_laser_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_extent=0, roi_rect=None, roi_circle=None,
-                    chunk_frames=0, device=0, background=None) -> LaserDots:
+                    chunk_frames=0, device=0, background=None, pixel_format=None, matrix="bt601") -> LaserDots:
     """Moments, bounding box, centroids and status of the laser dot of every frame of a batch: ``_native.detect_dots``.
     ``frames`` is a uint8 numpy array or a torch tensor on the device, (B, H, W, C) or (B, H, W); a single (H, W, C) frame has
     to be passed as ``frame[None]``.  ``max_extent`` rejects frames whose bright pixels do not fit a box of that size (status
     SPREAD): the one-pass stand-in for the one-connected-component rule of the reference's ``green_laser_finder``.
     ``background``: an ``imaging.BackgroundModel`` (its ``level()`` and ``hot_mask()``) or a ``(level, mask)`` pair of (H, W)
     planes; the static light is then gated out chunk by chunk (sba_background_suppress) and the detector reads the one-channel
-    result, whose surviving pixels keep their values."""
-    if background is not None:
-        return _without_background(
-            frames, background, channel, chunk_frames, device,
-            lambda clean: _native.detect_dots(clean, threshold=threshold, channel=0, min_area=min_area, max_area=max_area,
-                                              max_extent=max_extent, roi_rect=roi_rect, roi_circle=roi_circle, device=device),
-            ("sums", "box", "centroid", "status"), LaserDots)
+    result, whose surviving pixels keep their values.
+    ``pixel_format``: "nv12", "nv21", "i420" or "yv12" when ``frames`` are what the video decoder produced, 8-bit YUV 4:2:0 as
+    ``imaging.convert_frames`` takes them (a tuple of planes or a stacked array, numpy or device tensors); they are converted on
+    the device, chunk by chunk, to the plane ``channel`` names -- 0, 1, 2 = B, G, R, so that 1 stays green -- under ``matrix``."""
+    if background is not None or pixel_format is not None:
+        def detect(clean):
+            return _native.detect_dots(clean, threshold=threshold, channel=0, min_area=min_area, max_area=max_area,
+                                       max_extent=max_extent, roi_rect=roi_rect, roi_circle=roi_circle, device=device)
+        fields = ("sums", "box", "centroid", "status")
+        if pixel_format is not None:
+            return _from_decoder_frames(frames, pixel_format, matrix, background, channel, chunk_frames, device, detect, fields, LaserDots)
+        return _without_background(frames, background, channel, chunk_frames, device, detect, fields, LaserDots)
     return _native.detect_dots(frames, threshold=threshold, channel=channel, min_area=min_area, max_area=max_area,
                                max_extent=max_extent, roi_rect=roi_rect, roi_circle=roi_circle, chunk_frames=chunk_frames,
                                device=device)
@@ -123,19 +153,21 @@ def _disk_radius(footprint, default, name):
 
 def find_laser_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=4, max_blobs=8, min_area=0, max_area=0,
                      centre=None, max_centre_dist=0, roi_rect=None, roi_circle=None, chunk_frames=0, device=0,
-                     want_mask=False, want_labels=False, background=None) -> LaserBlobs:
+                     want_mask=False, want_labels=False, background=None, pixel_format=None, matrix="bt601") -> LaserBlobs:
     """The connected components of every frame of a batch and the verdict on each frame: ``_native.detect_blobs``.
     ``frames`` as for :func:`find_laser_dots`.  With the defaults (disk(1), disk(4), no filter) a frame's status is SBA_BLOB_OK
     exactly when the reference's ``green_laser_finder`` returns a centroid, and ``centroid[:, :2]`` is that centroid as (x, y).
-    ``background`` as for :func:`find_laser_dots`."""
-    if background is not None:
-        return _without_background(
-            frames, background, channel, chunk_frames, device,
-            lambda clean: _native.detect_blobs(clean, threshold=threshold, channel=0, dilate_radius=dilate_radius, close_radius=close_radius,
-                                               max_blobs=max_blobs, min_area=min_area, max_area=max_area, centre=centre,
-                                               max_centre_dist=max_centre_dist, roi_rect=roi_rect, roi_circle=roi_circle, device=device,
-                                               want_mask=want_mask, want_labels=want_labels),
-            ("n_components", "blobs", "accepted", "centroid", "status", "mask", "labels"), LaserBlobs)
+    ``background``, ``pixel_format`` and ``matrix`` as for :func:`find_laser_dots`."""
+    if background is not None or pixel_format is not None:
+        def detect(clean):
+            return _native.detect_blobs(clean, threshold=threshold, channel=0, dilate_radius=dilate_radius, close_radius=close_radius,
+                                        max_blobs=max_blobs, min_area=min_area, max_area=max_area, centre=centre,
+                                        max_centre_dist=max_centre_dist, roi_rect=roi_rect, roi_circle=roi_circle, device=device,
+                                        want_mask=want_mask, want_labels=want_labels)
+        fields = ("n_components", "blobs", "accepted", "centroid", "status", "mask", "labels")
+        if pixel_format is not None:
+            return _from_decoder_frames(frames, pixel_format, matrix, background, channel, chunk_frames, device, detect, fields, LaserBlobs)
+        return _without_background(frames, background, channel, chunk_frames, device, detect, fields, LaserBlobs)
     return _native.detect_blobs(frames, threshold=threshold, channel=channel, dilate_radius=dilate_radius, close_radius=close_radius,
                                 max_blobs=max_blobs, min_area=min_area, max_area=max_area, centre=centre,
                                 max_centre_dist=max_centre_dist, roi_rect=roi_rect, roi_circle=roi_circle, chunk_frames=chunk_frames,

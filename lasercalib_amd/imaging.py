@@ -10,6 +10,8 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
 * :func:`invertible_region`            -- where the distortion model is locally invertible (the FOLDED flag), as a bool image
 * :class:`BackgroundModel`             -- what every pixel of a camera shows over a video (sba_background_accumulate) and the
   removal of the light that is always there (sba_background_suppress), for rigs that cannot be made dark
+* :func:`convert_frames`, :class:`YuvMatrix` -- a decoder's YUV 4:2:0 frames (NV12, NV21, I420, YV12) into BGR / RGB frames or the
+  one plane the detectors read (sba_convert_frames): ``cv.cvtColor(frame, cv.COLOR_YUV2BGR_NV12)`` for a batch, on the GPU
 
 Sizes are ``(width, height)``, as in OpenCV.  Pixels follow the rule written out in include/sba_hip.h: a float64 model, the
 source position on a 1/32-pixel grid, integer bilinear weights.  That is OpenCV's scheme, but OpenCV rounds its weight table to
@@ -25,7 +27,7 @@ from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE
 SBA_UNDIST_OUTSIDE, SBA_UNDIST_FOLDED, SBA_UNDIST_RANGE = UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE
 
 __all__ = ["Lens", "undistort_frames", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
-           "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
+           "YuvMatrix", "convert_frames", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
 
 
 class Lens:
@@ -223,6 +225,108 @@ def optimal_new_camera_matrix(lens, image_size, alpha, new_size=None):
     return K_new, roi
 
 
+class YuvMatrix:
+    """The six integers of sba_convert_frames' rule (include/sba_hip.h), coefficients times 2^20:
+    ``l = max(Y - y_offset, 0) cy``, ``R = l + cvr v``, ``G = l + cug u + cvg v``, ``B = l + cub u`` with u = U - 128,
+    v = V - 128, each sum rounded by ``(s + 2^19) >> 20`` and clipped to 0..255.  The kernel knows nothing of standards:
+    ``from_standard`` and the presets compute the integers here, on the host."""
+
+    __slots__ = ("y_offset", "cy", "cvr", "cug", "cvg", "cub")
+    SHIFT = 20
+
+    def __init__(self, y_offset, cy, cvr, cug, cvg, cub):
+        vals = (y_offset, cy, cvr, cug, cvg, cub)
+        if any(int(v) != v for v in vals):
+            raise ValueError(f"YuvMatrix: the six values must be integers, got {vals}")
+        for name, v in zip(self.__slots__, vals):
+            setattr(self, name, int(v))
+        if not _native.yuv_matrix_in_bound(self.as_tuple()):
+            raise ValueError(f"YuvMatrix{self.as_tuple()}: y_offset must be in 0..255 and 255 |cy| + 128 (|a| + |b|) + 2^19 below 2^31 "
+                             "for the chroma coefficients a, b of every output row (the bound under which the sums fit 32 bits)")
+
+    @classmethod
+    def from_standard(cls, kr, kb, full_range=False):
+        """From the luma weights of a standard (BT.601: 0.299, 0.114; BT.709: 0.2126, 0.0722), each coefficient c as
+        ``round(c * 2**20)``.  Limited range (Y in 16..235, chroma in 16..240): cy = 255/219, cvr = 2 (1 - kr) 255/224,
+        cub = 2 (1 - kb) 255/224, cug = -2 kb (1 - kb) / kg 255/224, cvg = -2 kr (1 - kr) / kg 255/224 with kg = 1 - kr - kb,
+        y_offset = 16.  Full range: without the factors 255/219 and 255/224, y_offset = 0."""
+        kr, kb = float(kr), float(kb)
+        kg = 1.0 - kr - kb
+        if not (0.0 < kr < 1.0 and 0.0 < kb < 1.0 and kg > 0.0):
+            raise ValueError(f"kr, kb and 1 - kr - kb must lie in (0, 1), got kr = {kr}, kb = {kb}")
+        sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+        coeff = (sy, 2.0 * (1.0 - kr) * sc, -2.0 * kb * (1.0 - kb) / kg * sc, -2.0 * kr * (1.0 - kr) / kg * sc, 2.0 * (1.0 - kb) * sc)
+        return cls(0 if full_range else 16, *(int(round(c * (1 << cls.SHIFT))) for c in coeff))
+
+    @classmethod
+    def preset(cls, name):
+        """"bt601": the table of OpenCV's ``cvtColor(COLOR_YUV2BGR_NV12 / _I420)`` (limited range, three-decimal constants);
+        "bt709", "bt601-full", "bt709-full": ``from_standard``."""
+        key = str(name).lower()
+        if key == "bt601":
+            return cls(*_native.YUV_BT601)
+        if key in ("bt709", "bt601-full", "bt709-full"):
+            kr, kb = (0.299, 0.114) if key.startswith("bt601") else (0.2126, 0.0722)
+            return cls.from_standard(kr, kb, full_range=key.endswith("-full"))
+        raise ValueError(f"unknown matrix {name!r}: one of 'bt601', 'bt709', 'bt601-full', 'bt709-full' or a YuvMatrix")
+
+    def as_tuple(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, YuvMatrix) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def __repr__(self):
+        return "YuvMatrix(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.__slots__) + ")"
+
+
+def _matrix(matrix):
+    """The six integers of a YuvMatrix, a preset's name or a sequence of six integers."""
+    if isinstance(matrix, YuvMatrix):
+        return matrix.as_tuple()
+    if isinstance(matrix, str):
+        return YuvMatrix.preset(matrix).as_tuple()
+    return YuvMatrix(*matrix).as_tuple()
+
+
+def convert_frames(frames, pixel_format, out_format="bgr", matrix="bt601", out=None, chunk_frames=0, device=0):
+    """What a video decoder produces -- 8-bit YUV 4:2:0 -- into what the rest of the library reads, on the GPU
+    (sba_convert_frames, include/sba_hip.h): ``cv.cvtColor(frame, cv.COLOR_YUV2BGR_NV12 / _I420)`` for a whole batch.
+
+    ``pixel_format``: "nv12", "nv21", "i420" or "yv12".  ``frames``: a tuple of planes in the format's order, ``(y, uv)`` or
+    ``(y, u, v)`` (yv12: ``(y, v, u)``), with y (B, H, W), uv (B, ceil(H / 2), ceil(W / 2), 2), u and v (B, ceil(H / 2),
+    ceil(W / 2)) and any strides; or one stacked array (B, H + ceil(H / 2), W), as ffmpeg's rawvideo pipe delivers ``nv12``
+    (even W) and ``yuv420p`` (even W and H).  numpy arrays, or torch tensors on ``device`` read in place.
+    ``out_format``: "bgr", "rgb", "bgra", "rgba" -> (B, H, W, 3 | 4), or "b", "g", "r" -> the (B, H, W) plane, the input of the
+    detectors and the background model (``channel=0``).  ``matrix``: "bt601" (OpenCV's table, limited range), "bt709",
+    "bt601-full", "bt709-full" or a :class:`YuvMatrix`.  Chroma is taken from the nearest sample, as OpenCV does.  The result is
+    a numpy array for numpy frames and a device tensor for tensors, or ``out`` (either kind, any row and frame strides)."""
+    return _native.convert_frames(frames, pixel_format, out_format=out_format, matrix=_matrix(matrix), out=out,
+                                  chunk_frames=chunk_frames, device=device)
+
+
+CONVERT_CHUNK_BYTES = 1 << 30       # bytes of the one-channel plane held at a time when decoder frames go to a detector or the model
+_PLANE_OF_CHANNEL = ("b", "g", "r")
+
+
+def planes_in_chunks(frames, pixel_format, matrix, channel, chunk_frames, device):
+    """Yields (lo, hi, plane) over a batch of YUV 4:2:0 frames: ``plane`` is the (hi - lo, H, W) device tensor of channel
+    ``channel`` (0, 1, 2 = B, G, R: the reference's ``channel=1`` keeps meaning green) of the frames [lo, hi).  One chunk is
+    held at a time, whatever the length of the video; a batch without frames yields one empty plane."""
+    if channel not in (0, 1, 2):
+        raise ValueError(f"with a pixel_format, channel names a plane of BGR: 0, 1 or 2, not {channel!r}")
+    L = _native._yuv_layout(frames, pixel_format, device)
+    m = _matrix(matrix)
+    step = int(chunk_frames) if chunk_frames > 0 else max(1, CONVERT_CHUNK_BYTES // max(1, L.height * L.width))
+    for lo in range(0, max(L.n_frames, 1), step):
+        hi = min(lo + step, L.n_frames)
+        yield lo, hi, _native.convert_frames(_native.yuv_frame_slice(frames, lo, hi), pixel_format, out_format=_PLANE_OF_CHANNEL[channel],
+                                             matrix=m, out_on_device=True, device=device)
+
+
 class BackgroundModel:
     """Per-pixel statistics over time of one channel of one camera's frames, and what follows from them.
 
@@ -263,9 +367,28 @@ class BackgroundModel:
             if not _native._is_tensor(a):
                 self._acc[name] = torch.from_numpy(a.view(signed[name])).to(f"cuda:{self.device}")
 
-    def add(self, frames, use=None):
+    def _add_planes(self, frames, use, pixel_format, matrix, chunk_frames):
+        L = _native._yuv_layout(frames, pixel_format, self.device)
+        if (L.height, L.width) != (self.height, self.width):
+            raise ValueError(f"frames are {L.height} x {L.width}, the model is {self.height} x {self.width}")
+        if use is not None:
+            use = np.asarray(use)
+            if use.shape != (L.n_frames,):
+                raise ValueError(f"use must hold one flag per frame ({L.n_frames}), got the shape {use.shape}")
+        if self.on_device:
+            self._to_device()
+        for lo, hi, plane in planes_in_chunks(frames, pixel_format, matrix, self.channel, chunk_frames, self.device):
+            self.n = _native.background_accumulate(plane, n_used=self.n, use=None if use is None else use[lo:hi], threshold=self.threshold,
+                                                   channel=0, accumulate=True, device=self.device, **self._acc)
+        return self
+
+    def add(self, frames, use=None, pixel_format=None, matrix="bt601", chunk_frames=0):
         """Adds the frames (uint8 (B, H, W, C) or (B, H, W), numpy or a tensor on the device) whose ``use`` flag is set -- None:
-        all -- to the statistics.  Returns self."""
+        all -- to the statistics.  Returns self.  With a ``pixel_format`` ("nv12", "nv21", "i420", "yv12") the frames are YUV
+        4:2:0 as :func:`convert_frames` takes them; they are converted chunk by chunk (``chunk_frames`` frames, 0 = the default)
+        to the plane the model's ``channel`` names (0, 1, 2 = B, G, R) under ``matrix``, and the plane is added."""
+        if pixel_format is not None:
+            return self._add_planes(frames, use, pixel_format, matrix, chunk_frames)
         _t, _f, _B, H, W, _C, _sr, _sf = _native._frame_layout(frames, self.device)
         if (H, W) != (self.height, self.width):
             raise ValueError(f"frames are {H} x {W}, the model is {self.height} x {self.width}")
@@ -335,10 +458,32 @@ class BackgroundModel:
             mask = ndimage.binary_dilation(mask, structure=d[:, None] ** 2 + d[None, :] ** 2 <= r * r)
         return mask.astype(np.uint8)
 
-    def suppress(self, frames, mode="gate", level=None, mask=None, out=None, chunk_frames=0):
+    def suppress(self, frames, mode="gate", level=None, mask=None, out=None, chunk_frames=0, pixel_format=None, matrix="bt601"):
         """The model's channel of ``frames`` without the static light -> (B, H, W) uint8 on the side the frames are on.
-        ``level`` / ``mask``: (H, W) planes, None = ``self.level()`` / ``self.hot_mask()`` with their defaults."""
+        ``level`` / ``mask``: (H, W) planes, None = ``self.level()`` / ``self.hot_mask()`` with their defaults.  With a
+        ``pixel_format`` the frames are YUV 4:2:0 as for ``add``: each chunk is converted to the model's plane on the device and
+        the static light is taken out of that."""
         level = self.level() if level is None else level
         mask = self.hot_mask() if mask is None else mask
+        if pixel_format is not None:
+            L = _native._yuv_layout(frames, pixel_format, self.device)
+            if out is None:
+                if L.tensor:
+                    import torch
+                    out = torch.empty((L.n_frames, L.height, L.width), dtype=torch.uint8, device=f"cuda:{self.device}")
+                else:
+                    out = np.empty((L.n_frames, L.height, L.width), np.uint8)
+            elif tuple(out.shape) != (L.n_frames, L.height, L.width):
+                raise ValueError(f"out has the shape {tuple(out.shape)}, expected {(L.n_frames, L.height, L.width)}")
+            if not _native._is_tensor(level) or not _native._is_tensor(mask):      # one upload for all chunks
+                import torch
+                level, mask = (a if _native._is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(f"cuda:{self.device}")
+                               for a in (level, mask))
+            for lo, hi, plane in planes_in_chunks(frames, pixel_format, matrix, self.channel, chunk_frames, self.device):
+                if _native._is_tensor(out):
+                    _native.background_suppress(plane, level=level, mask=mask, mode=mode, channel=0, out=out[lo:hi], device=self.device)
+                else:
+                    out[lo:hi] = _native.background_suppress(plane, level=level, mask=mask, mode=mode, channel=0, device=self.device).cpu().numpy()
+            return out
         return _native.background_suppress(frames, level=level, mask=mask, mode=mode, channel=self.channel, out=out,
                                            chunk_frames=chunk_frames, device=self.device)
