@@ -852,6 +852,57 @@ int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uin
                        int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts* opts /*NULL: all zero*/,
                        uint8_t* out);
 
+/* ---------------------------------------------------------------- previews: area-averaged smaller frames, grey planes, mosaics
+ * The reference shrinks every frame on the host before a person sees it (scripts/run_viewers.py:121, cv2.resize(frame,
+ * (802, 550), interpolation=cv2.INTER_AREA): a 4 x 4 box average of a 3208 x 2200 frame; scripts/charuco_intrinsics.py:55,
+ * cv.resize to (1604, 1100): 2 x 2) and forms the grey plane its marker search reads with cv2.cvtColor(frame,
+ * cv2.COLOR_BGR2GRAY) (run_viewers.py:72, charuco_intrinsics.py:29).  sba_resize_frames does both for a batch of frames:
+ * every output pixel is the average of a block of fx x fy source pixels, of every channel or of the grey value.  Stateless: no
+ * handle.  Frames are described as for sba_detect_dots (8-bit, channels 1, 3 or 4 interleaved, any base, any pitches, host
+ * memory or with frames_on_device device memory read in place).
+ *
+ * The output has out_h = height / fy rows of out_w = width / fx pixels (floor division) of `channels` bytes, or of ONE byte
+ * with `gray`; row r of frame f at out + f out_frame_pitch + r out_row_pitch, in host memory or with out_on_device in device
+ * memory of `device`, written in place.  The padding between rows and frames is never written: base and pitches are the
+ * caller's, so a call can write its frames into a tile of a larger canvas (a mosaic of cameras is one call per camera).
+ * When a size is not a multiple of its factor, the width % fx columns on the right and the height % fy rows at the bottom are
+ * NOT READ.  OpenCV takes a different path there: with a requested size that is not an exact integer fraction its INTER_AREA
+ * uses fractional weights over the whole frame.  The two agree only when both sizes are exact multiples.
+ *
+ * The rule -- this is the function's definition:
+ * 1. Grey, when asked for, is formed first, per SOURCE pixel with the bytes c0, c1, c2 of its first three channels:
+ *      g = (c0*w0 + c1*w1 + c2*w2 + 2^14) >> 15
+ *    gray_w = {w0, w1, w2} are integers >= 0 that sum to exactly 2^15, so g <= 255 without a clip; all zero means OpenCV's
+ *    {3735, 19235, 9798} for B, G, R: this is cvtColor(COLOR_BGR2GRAY)'s 8-bit rule in OpenCV 4.  A fourth channel is ignored.
+ * 2. Per output pixel (x, y) and output channel, s is the integer sum of the fx*fy source values (bytes of that channel, or
+ *    grey values) of the block of columns [x fx, (x + 1) fx) and rows [y fy, (y + 1) fy):
+ *      fx == 2 && fy == 2:  out = (s + 2) >> 2                                   (OpenCV's 2 x 2 special case: half up)
+ *      otherwise:           out = rint(fl32(fl32(s) * fl32(1.0f / (fx*fy))))
+ *    ONE IEEE float32 division forms the scale, on the host; ONE float32 multiply follows, never fused with anything; the
+ *    product is rounded to the nearest integer, ties to even.  This is saturate_cast<uchar>(sum * scale) of OpenCV's
+ *    integer-factor INTER_AREA path.  For areas that are powers of two (4 x 4 among them) it is the exact quotient with ties
+ *    to even.  fx == fy == 1 copies, or only converts to grey.
+ * 3. fx and fy lie in 1..16, so s <= 255 * 256 and every value above is exact in float32.
+ * Frames pass through the device in chunks (host frames through two staging buffers, a host output through one more); device
+ * memory does not grow with n_frames, and any chunk_frames gives the same bytes.  n_frames = 0 returns SBA_OK and writes
+ * nothing.
+ * Errors, all checked before any device work (text in sba_last_error(NULL)), out left untouched: the frame errors of
+ * sba_detect_dots; SBA_ERR_INVALID for a factor outside 1..16, a factor larger than the frame's size with n_frames > 0 (the
+ * output would have no pixels), out_row_pitch < out_w times the bytes of an output pixel, out_frame_pitch < out_h
+ * out_row_pitch, a NULL out with n_frames > 0, gray with channels == 1, and weights that are negative or do not sum to 2^15. */
+typedef struct {
+  int32_t frames_on_device;  /* as sba_dot_opts */
+  int32_t out_on_device;     /* 1: `out` is a device pointer on `device` */
+  int32_t chunk_frames;      /* frames per chunk at most; <= 0 = library default */
+  int32_t gray;              /* 0: the output keeps `channels`; 1: ONE byte per pixel, the grey value */
+  int32_t gray_w[3];         /* weights of the interleaved channels 0, 1, 2; all zero = {3735, 19235, 9798} (B, G, R) */
+  int32_t reserved[5];
+} sba_resize_opts;
+int sba_resize_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width,
+                      int32_t channels /*1, 3 or 4*/, int64_t row_pitch, int64_t frame_pitch, int32_t fx /*1..16*/,
+                      int32_t fy /*1..16*/, int64_t out_row_pitch, int64_t out_frame_pitch,
+                      const sba_resize_opts* opts /*NULL: all zero*/, uint8_t* out);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

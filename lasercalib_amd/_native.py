@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "sba_comm_get_unique_id", "sba_comm_init", "sba_set_fixed_points", "sba_set_robust_loss", "sba_covariance",
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
-    "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames",
+    "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames", "sba_resize_frames",
 )
 
 
@@ -180,6 +180,19 @@ YUV_BT601 = (16, 1220542, 1673527, -409993, -852492, 2116026)             # Open
 # geometry of the kernel (csrc/sba_convert.hpp), for the tests that straddle it: the pixels of a row a lane owns, the pixels a
 # wave spans, the rows of a workgroup's tile
 CONVERT_RUN, CONVERT_WAVE_COLS, CONVERT_TILE_ROWS = 16, 512, 16
+
+
+class ResizeOpts(C.Structure):                                            # sba_resize_opts
+    _fields_ = [("frames_on_device", C.c_int32), ("out_on_device", C.c_int32), ("chunk_frames", C.c_int32), ("gray", C.c_int32),
+                ("gray_w", C.c_int32 * 3), ("reserved", C.c_int32 * 5)]
+
+
+RESIZE_MAX_FACTOR = 16
+GRAY_BGR = (3735, 19235, 9798)                                            # OpenCV's weights of B, G, R: what all-zero gray_w means
+GRAY_SHIFT = 15                                                           # the weights sum to 2^15
+# the items (source bytes, or source pixels with gray) of a row that a wave takes in one step (csrc/sba_resize.hpp), for the
+# tests that straddle a segment
+RESIZE_ITEMS = 1024
 
 
 def yuv_matrix_in_bound(m):
@@ -484,6 +497,8 @@ def load():
         "sba_convert_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                          C.c_int64, C.c_int64, C.c_int32, C.POINTER(YuvMatrix), C.c_int64, C.c_int64,
                                          C.POINTER(ConvertOpts), C.c_void_p]),
+        "sba_resize_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                        C.c_int32, C.c_int64, C.c_int64, C.POINTER(ResizeOpts), C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
         "sba_apply_similarity": (C.c_int, [H, C.c_double, dp, dp]),
         "sba_reproj_stats": (C.c_int, [H, C.POINTER(ReprojOpts), dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(ReprojReport)]),
@@ -1059,6 +1074,53 @@ def convert_frames(frames, pixel_format, out_format="bgr", matrix=None, out=None
     _check(lib.sba_convert_frames(device, C.c_void_p(L.y), C.c_void_p(L.u), C.c_void_p(L.v), B, H, W, L.y_row_pitch, L.y_frame_pitch,
                                   L.c_row_pitch, L.c_frame_pitch, L.c_step, None if m is None else C.byref(m), osr, osf, C.byref(opts),
                                   C.c_void_p(optr)))
+    return out
+
+
+def resize_frames(frames, fx, fy, gray_w=None, out=None, out_on_device=None, chunk_frames=0, device=0):
+    """sba_resize_frames (include/sba_hip.h): every pixel of the result is the average of a block of ``fx`` x ``fy`` pixels of
+    ``frames`` (as for ``detect_dots``: numpy, or a torch tensor on ``device`` read in place) -> (B, H // fy, W // fx[, C]).
+    ``gray_w``: None keeps the channels; three integer weights of the channels 0, 1, 2 (all zero: OpenCV's of B, G, R) give the
+    (B, H // fy, W // fx) plane of grey values.  The result is allocated on the side the frames are on (``out_on_device`` True /
+    False overrides that), or is the caller's ``out``: a writeable numpy array or a tensor on ``device`` of that shape, which
+    may be a view into a larger array -- a tile of a canvas: its row and frame strides are the pitches, the pixels must be
+    contiguous, and what lies between its rows is left untouched.  ``lasercalib_amd.imaging.resize_frames`` is the public
+    face of this call."""
+    lib = load()
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    fx, fy = int(fx), int(fy)
+    if not (1 <= fx <= RESIZE_MAX_FACTOR and 1 <= fy <= RESIZE_MAX_FACTOR):
+        raise ValueError(f"the factors must be in 1..{RESIZE_MAX_FACTOR}, got {(fx, fy)}")
+    opts = ResizeOpts()
+    if gray_w is not None:
+        vals = [int(v) for v in gray_w]
+        if len(vals) != 3 or any(not -(1 << 31) <= v < (1 << 31) for v in vals):
+            raise ValueError(f"gray_w must be three 32-bit integers, got {gray_w!r}")
+        opts.gray, opts.gray_w = 1, (C.c_int32 * 3)(*vals)
+    Ho, Wo, Co = H // fy, W // fx, 1 if gray_w is not None else Cn
+    shape = (B, Ho, Wo, Cn) if gray_w is None and len(frames.shape) == 4 else (B, Ho, Wo)
+    if out is not None:
+        out_tensor = _is_tensor(out)
+        if not out_tensor and not (isinstance(out, np.ndarray) and out.flags.writeable):
+            raise ValueError("out must be a writeable numpy array or a tensor on the device")
+        if tuple(out.shape) not in ((B, Ho, Wo, Co), (B, Ho, Wo) if Co == 1 else None):
+            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shape}")
+        _t, _o, _B, _H, _W, _C, osr, osf = _frame_layout(out, device)
+    else:
+        out_tensor = tensor if out_on_device is None else bool(out_on_device)
+        if out_tensor:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{device}")
+        else:
+            out = np.empty(shape, np.uint8)
+        osr, osf = Wo * Co, Ho * Wo * Co
+    opts.frames_on_device, opts.out_on_device, opts.chunk_frames = 1 if tensor else 0, 1 if out_tensor else 0, int(chunk_frames)
+    if tensor or out_tensor:
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # frames and out are complete before the library touches them
+    ptr = frames.data_ptr() if tensor else frames.ctypes.data
+    optr = out.data_ptr() if out_tensor else out.ctypes.data
+    _check(lib.sba_resize_frames(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, fx, fy, osr, osf, C.byref(opts), C.c_void_p(optr)))
     return out
 
 

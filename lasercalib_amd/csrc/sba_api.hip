@@ -34,6 +34,9 @@ int sba_convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8
                      int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step,
                      const sba_yuv_matrix& matrix, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& opts,
                      uint8_t* out);
+int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                    int64_t row_pitch, int64_t frame_pitch, int32_t fx, int32_t fy, int64_t out_row_pitch, int64_t out_frame_pitch,
+                    const sba_resize_opts& opts, uint8_t* out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -570,6 +573,35 @@ int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uin
   return guarded(nullptr, [&] {
     return sba_convert_call(device, y, u, v, n_frames, height, width, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, m,
                             out_row_pitch, out_frame_pitch, o, out);
+  });
+}
+
+int sba_resize_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                      int64_t row_pitch, int64_t frame_pitch, int32_t fx, int32_t fy, int64_t out_row_pitch, int64_t out_frame_pitch,
+                      const sba_resize_opts* opts, uint8_t* out) {
+  const char* fn = "sba_resize_frames";
+  sba_resize_opts o{};
+  if (opts) o = *opts;
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
+  if (rc) return rc;
+  if (fx < 1 || fx > 16 || fy < 1 || fy > 16) return detect_invalid(fn, "fx and fy must be in 1..16");
+  if (n_frames > 0 && (fx > width || fy > height)) return detect_invalid(fn, "a factor is larger than the frame: the output would have no pixels");
+  if (o.gray) {
+    if (channels == 1) return detect_invalid(fn, "gray needs 3 or 4 channels");
+    if (o.gray_w[0] == 0 && o.gray_w[1] == 0 && o.gray_w[2] == 0) { o.gray_w[0] = 3735; o.gray_w[1] = 19235; o.gray_w[2] = 9798; }   // OpenCV's B, G, R
+    if (o.gray_w[0] < 0 || o.gray_w[1] < 0 || o.gray_w[2] < 0) return detect_invalid(fn, "a gray weight is negative");
+    if ((int64_t)o.gray_w[0] + o.gray_w[1] + o.gray_w[2] != 1 << 15) return detect_invalid(fn, "the gray weights must sum to 2^15");
+  }
+  if (!out && n_frames > 0) return detect_invalid(fn, "null out");
+  const int64_t out_h = height / fy, out_w = width / fx, px = o.gray ? 1 : channels;
+  if (out_row_pitch < out_w * px) return detect_invalid(fn, "out_row_pitch is smaller than (width / fx) times the bytes of an output pixel");
+  if ((__int128)out_h * out_row_pitch > out_frame_pitch) return detect_invalid(fn, "out_frame_pitch is smaller than (height / fy) * out_row_pitch");
+  if ((__int128)n_frames * out_frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * out_frame_pitch overflows");
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc || n_frames == 0) return rc;
+  return guarded(nullptr, [&] {
+    return sba_resize_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, fx, fy, out_row_pitch, out_frame_pitch,
+                           o, out);
   });
 }
 

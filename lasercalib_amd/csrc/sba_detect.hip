@@ -1,11 +1,12 @@
 // sba_detect.hip -- the kernels that work on video frames: the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
-// connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp) and the
-// conversion of decoder frames (sba_convert.hpp).  They do not depend on the engine's camera model, so they are compiled once,
-// in a translation unit of their own.
+// connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp), the
+// conversion of decoder frames (sba_convert.hpp) and the area-averaged previews (sba_resize.hpp).  They do not depend on the
+// engine's camera model, so they are compiled once, in a translation unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
 #include "sba_background.hpp"
 #include "sba_convert.hpp"
+#include "sba_resize.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -48,4 +49,11 @@ int sba_convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8
                      uint8_t* out) {
   return sba_detect::convert_call(device, y, u, v, n_frames, height, width, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step,
                                   matrix, out_row_pitch, out_frame_pitch, opts, out);
+}
+
+int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                    int64_t row_pitch, int64_t frame_pitch, int32_t fx, int32_t fy, int64_t out_row_pitch, int64_t out_frame_pitch,
+                    const sba_resize_opts& opts, uint8_t* out) {
+  return sba_detect::resize_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, fx, fy, out_row_pitch,
+                                 out_frame_pitch, opts, out);
 }

@@ -12,6 +12,8 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
   removal of the light that is always there (sba_background_suppress), for rigs that cannot be made dark
 * :func:`convert_frames`, :class:`YuvMatrix` -- a decoder's YUV 4:2:0 frames (NV12, NV21, I420, YV12) into BGR / RGB frames or the
   one plane the detectors read (sba_convert_frames): ``cv.cvtColor(frame, cv.COLOR_YUV2BGR_NV12)`` for a batch, on the GPU
+* :func:`resize_frames`, :func:`mosaic` -- previews: ``cv2.resize(frame, size, interpolation=cv2.INTER_AREA)`` at an integer factor
+  and ``cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)`` for a batch (sba_resize_frames), and the cameras of a rig side by side in one canvas
 
 Sizes are ``(width, height)``, as in OpenCV.  Pixels follow the rule written out in include/sba_hip.h: a float64 model, the
 source position on a 1/32-pixel grid, integer bilinear weights.  That is OpenCV's scheme, but OpenCV rounds its weight table to
@@ -27,7 +29,7 @@ from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE
 SBA_UNDIST_OUTSIDE, SBA_UNDIST_FOLDED, SBA_UNDIST_RANGE = UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE
 
 __all__ = ["Lens", "undistort_frames", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
-           "YuvMatrix", "convert_frames", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
+           "YuvMatrix", "convert_frames", "resize_frames", "mosaic", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
 
 
 class Lens:
@@ -325,6 +327,123 @@ def planes_in_chunks(frames, pixel_format, matrix, channel, chunk_frames, device
         hi = min(lo + step, L.n_frames)
         yield lo, hi, _native.convert_frames(_native.yuv_frame_slice(frames, lo, hi), pixel_format, out_format=_PLANE_OF_CHANNEL[channel],
                                              matrix=m, out_on_device=True, device=device)
+
+
+def _factor(factor):
+    """(fx, fy) from an int or a pair, each in 1..16."""
+    try:
+        fx, fy = (factor, factor) if np.ndim(factor) == 0 else factor
+        if int(fx) != fx or int(fy) != fy:
+            raise ValueError
+        fx, fy = int(fx), int(fy)
+    except (TypeError, ValueError):
+        raise ValueError(f"factor must be an integer or (fx, fy), got {factor!r}") from None
+    if not (1 <= fx <= _native.RESIZE_MAX_FACTOR and 1 <= fy <= _native.RESIZE_MAX_FACTOR):
+        raise ValueError(f"factor must be within 1..{_native.RESIZE_MAX_FACTOR}, got {(fx, fy)}")
+    return fx, fy
+
+
+def _gray_weights(gray, channel_order):
+    """None (keep the channels) or the three integer weights of the channels 0, 1, 2, which sum to 2^15."""
+    order = str(channel_order).lower()
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', not {channel_order!r}")
+    if gray is None or isinstance(gray, (bool, np.bool_)):
+        w = _native.GRAY_BGR
+        return None if not gray else w if order == "bgr" else w[::-1]
+    try:
+        w = tuple(int(v) for v in gray)
+        if len(w) != 3 or any(a != b for a, b in zip(w, gray)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"gray must be a bool or three integer weights, got {gray!r}") from None
+    if min(w) < 0 or sum(w) != 1 << _native.GRAY_SHIFT:
+        raise ValueError(f"the gray weights must be >= 0 and sum to 2^{_native.GRAY_SHIFT}, got {w}")
+    return w
+
+
+def resize_frames(frames, factor, gray=False, channel_order="bgr", out=None, chunk_frames=0, pixel_format=None, matrix="bt601", device=0):
+    """Previews of a batch of frames, on the GPU (sba_resize_frames, include/sba_hip.h): ``cv2.resize(frame, (W // fx, H // fy),
+    interpolation=cv2.INTER_AREA)`` for sizes that are multiples of the factor -- every pixel the average of a block of
+    fx x fy pixels --, after ``cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)`` with ``gray``.
+
+    ``frames``: uint8, (B, H, W, C) with C in (1, 3, 4) or (B, H, W); a numpy array in any layout with contiguous pixels, or a
+    torch tensor on ``device``, read in place.  ``factor``: an int, or ``(fx, fy)``, each in 1..16; columns and rows beyond the
+    last whole block are not read (OpenCV would spread fractional weights over them).  ``gray``: False keeps the channels ->
+    (B, H // fy, W // fx[, C]); True writes the grey value of OpenCV's weights -> (B, H // fy, W // fx), with
+    ``channel_order`` "bgr" or "rgb" saying which channel is which; or three integer weights >= 0 of the channels 0, 1, 2 that
+    sum to 2^15.  A factor of 1 with ``gray`` only converts.  The result is a numpy array for numpy frames and a device tensor
+    for tensors, or ``out`` (either kind), which may be a view into a larger array or tensor: what lies between its rows and
+    frames is left untouched.  With a ``pixel_format`` ("nv12", "nv21", "i420", "yv12") the frames are YUV 4:2:0 as
+    :func:`convert_frames` takes them: they are converted to BGR chunk by chunk (``chunk_frames`` frames; 0 = the default) on
+    the device under ``matrix``, and each chunk is resized."""
+    fx, fy = _factor(factor)
+    w = _gray_weights(gray, channel_order)
+    if pixel_format is None:
+        return _native.resize_frames(frames, fx, fy, gray_w=w, out=out, chunk_frames=chunk_frames, device=device)
+    L = _native._yuv_layout(frames, pixel_format, device)
+    m = _matrix(matrix)
+    shape = (L.n_frames, L.height // fy, L.width // fx) + (() if w is not None else (3,))
+    if out is None:
+        if L.tensor:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{device}")
+        else:
+            out = np.empty(shape, np.uint8)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shape}")
+    w = _gray_weights(gray, "bgr")                           # the converted chunks are BGR: channel_order says nothing about them
+    step = int(chunk_frames) if chunk_frames > 0 else max(1, CONVERT_CHUNK_BYTES // max(1, 3 * L.height * L.width))
+    for lo in range(0, L.n_frames, step):
+        hi = min(lo + step, L.n_frames)
+        bgr = _native.convert_frames(_native.yuv_frame_slice(frames, lo, hi), pixel_format, out_format="bgr", matrix=m, out_on_device=True,
+                                     device=device)
+        _native.resize_frames(bgr, fx, fy, gray_w=w, out=out[lo:hi], device=device)
+    return out
+
+
+def mosaic(batches, factor, columns=None, gap=0, fill=0, gray=False, on_device=False, channel_order="bgr", device=0):
+    """The cameras of a rig side by side: one canvas per frame index, each camera's preview in its own tile, as the reference's
+    tiled viewer shows them.  Returns ``(canvas, origins)``.
+
+    ``batches``: a list of per-camera frame batches as :func:`resize_frames` takes them, of equal length and the same number
+    of channels; their sizes may differ.  ``factor``, ``gray`` and ``channel_order`` as there.  The tiles are as large as the
+    largest preview and lie row-major, ``columns`` to a row (default ``ceil(sqrt(n))``), ``gap`` pixels apart; the gaps and the
+    part of a tile that its preview does not cover hold ``fill`` (0..255).  ``canvas`` is (n_frames, H, W[, C]) uint8, a numpy
+    array or with ``on_device`` a tensor on ``device``; every camera is ONE resize_frames call that writes straight into its
+    tile.  ``origins`` is (n, 2) int64, the (x, y) of every tile's first pixel: a click at (X, Y) inside camera k's preview is
+    the source pixel ((X - x_k) fx, (Y - y_k) fy) of that camera."""
+    fx, fy = _factor(factor)
+    w = _gray_weights(gray, channel_order)
+    n = len(batches)
+    if n == 0:
+        raise ValueError("mosaic needs at least one camera")
+    columns = int(np.ceil(np.sqrt(n))) if columns is None else int(columns)
+    gap, fill = int(gap), int(fill)
+    if columns < 1 or gap < 0 or not 0 <= fill <= 255:
+        raise ValueError(f"columns must be >= 1, gap >= 0 and fill in 0..255, got {(columns, gap, fill)}")
+    layouts = [_native._frame_layout(b, device) for b in batches]
+    n_frames = layouts[0][2]
+    if any(L[2] != n_frames for L in layouts):
+        raise ValueError(f"every camera must have the same number of frames, got {[L[2] for L in layouts]}")
+    tails = {() if w is not None or len(L[1].shape) == 3 else (L[5],) for L in layouts}
+    if len(tails) != 1:
+        raise ValueError("every camera must have the same number of channels")
+    sizes = [(L[3] // fy, L[4] // fx) for L in layouts]                   # (height, width) of every preview
+    th, tw = max(s[0] for s in sizes), max(s[1] for s in sizes)
+    if min(min(s) for s in sizes) == 0:
+        raise ValueError(f"a factor is larger than a camera's frames: previews of {sizes}")
+    rows = (n + columns - 1) // columns
+    shape = (n_frames, rows * th + (rows - 1) * gap, columns * tw + (columns - 1) * gap) + next(iter(tails))
+    if on_device:
+        import torch
+        canvas = torch.full(shape, fill, dtype=torch.uint8, device=f"cuda:{device}")
+    else:
+        canvas = np.full(shape, fill, np.uint8)
+    origins = np.array([[(k % columns) * (tw + gap), (k // columns) * (th + gap)] for k in range(n)], np.int64)
+    for b, (h, wd), (x, y) in zip(batches, sizes, origins):
+        _native.resize_frames(b, fx, fy, gray_w=w, out=canvas[:, y:y + h, x:x + wd], device=device)
+    return canvas, origins
 
 
 class BackgroundModel:
