@@ -679,6 +679,44 @@ def _frame_layout(frames, device):
     return tensor, frames, B, H, W, Cn, sr, sf
 
 
+def _addr(a):
+    return a.data_ptr() if _is_tensor(a) else a.ctypes.data
+
+
+def _synced(device, a=None, also=False):
+    """The address of ``a`` (a numpy array or a device tensor; None: None) for the C call.  When it is a tensor, or with ``also``
+    (the call hands over other tensors), the current stream is synchronised first: what was queued on it is complete before
+    the library touches the memory."""
+    if also or _is_tensor(a):
+        import torch
+        torch.cuda.current_stream(device).synchronize()
+    return None if a is None else _addr(a)
+
+
+def _frames_out(out, shapes, on_device, device, like_frames=None):
+    """The result of a call that turns frames into frames -> (out, is a tensor, address, row stride, frame stride).  ``out``
+    None: a packed uint8 array of ``shapes[0]`` is allocated, a tensor on ``device`` with ``on_device``, else a numpy array.
+    Otherwise the caller's array is checked -- of one of ``shapes`` (the expected one first; a None among them counts for
+    nothing), pixels contiguous -- and its strides are the pitches.  ``like_frames`` True / False: ``out`` must be a tensor / a numpy array,
+    as the frames are; None: it may lie on either side."""
+    if out is None:
+        if on_device:
+            import torch
+            out = torch.empty(shapes[0], dtype=torch.uint8, device=f"cuda:{device}")
+        else:
+            out = np.empty(shapes[0], np.uint8)
+    else:
+        on_device = _is_tensor(out)
+        if like_frames is not None and on_device != like_frames:
+            raise ValueError("out must be of the kind of frames: a numpy array for numpy frames, a device tensor for tensor frames")
+        if not on_device and not (isinstance(out, np.ndarray) and out.flags.writeable):
+            raise ValueError("out must be a writeable numpy array" + ("" if like_frames is not None else " or a tensor on the device"))
+        if tuple(out.shape) not in shapes:
+            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shapes[0]}")
+    _t, _o, _B, _H, _W, _C, osr, osf = _frame_layout(out, device)
+    return out, on_device, _addr(out), osr, osf
+
+
 def _frame_args(frames, device, opts, channel, threshold, chunk_frames, roi_rect, roi_circle):
     """What detect_dots and detect_blobs do alike with their frames: fills the fields both options structs have and returns
     (B, H, W, leading arguments of the C call -- device, pointer, sizes, pitches, options --, the object that owns the pixels)."""
@@ -688,13 +726,7 @@ def _frame_args(frames, device, opts, channel, threshold, chunk_frames, roi_rect
         opts.roi_rect = (C.c_int32 * 4)(*(int(v) for v in roi_rect))
     if roi_circle is not None:
         opts.roi_circle = (C.c_int32 * 3)(*(int(v) for v in roi_circle))
-    if tensor:
-        import torch
-        torch.cuda.current_stream(device).synchronize()      # the frames are complete before the library reads them
-        ptr = frames.data_ptr()
-    else:
-        ptr = frames.ctypes.data
-    return B, H, W, (device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts)), frames
+    return B, H, W, (device, C.c_void_p(_synced(device, frames)), B, H, W, Cn, sr, sf, C.byref(opts)), frames
 
 
 def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_extent=0, roi_rect=None, roi_circle=None,
@@ -768,36 +800,18 @@ def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", bor
     opts = UndistortOpts()
     opts.frames_on_device = opts.out_on_device = 1 if tensor else 0
     opts.interpolation, opts.border_value, opts.chunk_frames = UNDIST_INTERPOLATION[interpolation], int(border_value), int(chunk_frames)
-    shape = (B, Ho, Wo, Cn) if len(frames.shape) == 4 else (B, Ho, Wo)
+    shapes = ((B, Ho, Wo, Cn), (B, Ho, Wo) if Cn == 1 else None)            # a one-channel result may drop the last axis
     osr, osf, optr = Wo * Cn, Ho * Wo * Cn, None
     if not want_frames:
         if out is not None:
             raise ValueError("out was given but no frames are asked for")
         if not (want_flags or want_map):
             raise ValueError("nothing asked for: neither frames nor flags nor map")
-        out = None
-    elif out is not None:
-        if _is_tensor(out) != tensor:
-            raise ValueError("out must be of the kind of frames: a numpy array for numpy frames, a device tensor for tensor frames")
-        if not tensor and not (isinstance(out, np.ndarray) and out.flags.writeable):
-            raise ValueError("out must be a writeable numpy array")
-        _t, _o, oB, oH, oW, oC, osr, osf = _frame_layout(out, device)
-        if (oB, oH, oW, oC) != (B, Ho, Wo, Cn):
-            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shape}")
-    elif tensor:
-        import torch
-        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
     else:
-        out = np.empty(shape, np.uint8)
-    if tensor:
-        import torch
-        torch.cuda.current_stream(device).synchronize()      # the frames are complete before the library reads them
-        ptr, optr = frames.data_ptr(), None if out is None else out.data_ptr()
-    else:
-        ptr, optr = frames.ctypes.data, None if out is None else out.ctypes.data
+        out, _t, optr, osr, osf = _frames_out(out, shapes if len(frames.shape) == 4 else shapes[::-1], tensor, device, like_frames=tensor)
     flags = np.zeros((Ho, Wo), np.uint8) if want_flags else None
     qmap = np.zeros((Ho, Wo, 2), np.int32) if want_map else None
-    _check(lib.sba_undistort_frames(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(lens), _dptr(nk), Ho, Wo, osr, osf,
+    _check(lib.sba_undistort_frames(device, C.c_void_p(_synced(device, frames)), B, H, W, Cn, sr, sf, C.byref(lens), _dptr(nk), Ho, Wo, osr, osf,
                                     C.byref(opts), C.c_void_p(optr), None if flags is None else flags.ctypes.data,
                                     None if qmap is None else qmap.ctypes.data))
     return out, flags, qmap
@@ -846,12 +860,10 @@ def background_accumulate(frames, sum=None, sumsq=None, hot=None, vmax=None, n_u
         use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
         if use.shape != (B,):
             raise ValueError(f"use must hold one flag per frame ({B}), got the shape {use.shape}")
-    if tensor or opts.stats_on_device:
-        import torch
-        torch.cuda.current_stream(device).synchronize()      # frames and planes are complete before the library touches them
     n = C.c_uint64(int(n_used))
-    _check(lib.sba_background_accumulate(device, C.c_void_p(frames.data_ptr() if tensor else frames.ctypes.data), B, H, W, Cn, sr, sf,
-                                         C.byref(opts), None if use is None else C.c_void_p(use.ctypes.data), *ptrs, C.byref(n)))
+    ptr = _synced(device, frames, also=bool(opts.stats_on_device))
+    _check(lib.sba_background_accumulate(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts),
+                                         None if use is None else C.c_void_p(use.ctypes.data), *ptrs, C.byref(n)))
     return int(n.value)
 
 
@@ -882,26 +894,10 @@ def background_suppress(frames, level=None, mask=None, mode="gate", channel=1, o
     if len(kinds) > 1:
         raise ValueError("level and mask must both be numpy arrays or both be device tensors")
     opts.model_on_device = 1 if True in kinds else 0
-    osr, osf = W, H * W
-    if out is not None:
-        if _is_tensor(out) != tensor:
-            raise ValueError("out must be of the kind of frames: a numpy array for numpy frames, a device tensor for tensor frames")
-        if not tensor and not (isinstance(out, np.ndarray) and out.flags.writeable):
-            raise ValueError("out must be a writeable numpy array")
-        if len(out.shape) != 3:
-            raise ValueError(f"out must be (B, H, W), got the shape {tuple(out.shape)}")
-        _t, _o, oB, oH, oW, _c, osr, osf = _frame_layout(out, device)
-        if (oB, oH, oW) != (B, H, W):
-            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {(B, H, W)}")
-    elif tensor:
-        import torch
-        out = torch.empty((B, H, W), dtype=torch.uint8, device=frames.device)
-    else:
-        out = np.empty((B, H, W), np.uint8)
-    if tensor or opts.model_on_device:
-        import torch
-        torch.cuda.current_stream(device).synchronize()      # frames, level and mask are complete before the library reads them
-    ptr, optr = (frames.data_ptr(), out.data_ptr()) if tensor else (frames.ctypes.data, out.ctypes.data)
+    if len(getattr(out, "shape", (B, H, W))) != 3:                         # not (B, H, W, 1): the result has no channel axis
+        raise ValueError(f"out must be (B, H, W), got the shape {tuple(out.shape)}")
+    out, _t, optr, osr, osf = _frames_out(out, ((B, H, W),), tensor, device, like_frames=tensor)
+    ptr = _synced(device, frames, also=bool(opts.model_on_device))
     _check(lib.sba_background_suppress(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, *ptrs, osr, osf, C.byref(opts), C.c_void_p(optr)))
     return out
 
@@ -1049,28 +1045,11 @@ def convert_frames(frames, pixel_format, out_format="bgr", matrix=None, out=None
         if len(vals) != 6 or any(not -(1 << 31) <= v < (1 << 31) for v in vals):
             raise ValueError(f"matrix must be six 32-bit integers (y_offset, cy, cvr, cug, cvg, cub), got {matrix!r}")
         m = YuvMatrix(*vals)
-    if out is not None:
-        out_tensor = _is_tensor(out)
-        if not out_tensor and not (isinstance(out, np.ndarray) and out.flags.writeable):
-            raise ValueError("out must be a writeable numpy array or a tensor on the device")
-        if tuple(out.shape) not in (shape, (B, H, W, Cn)):
-            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shape}")
-        _t, _o, _B, _H, _W, _C, osr, osf = _frame_layout(out, device)
-    else:
-        out_tensor = L.tensor if out_on_device is None else bool(out_on_device)
-        if out_tensor:
-            import torch
-            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{device}")
-        else:
-            out = np.empty(shape, np.uint8)
-        osr, osf = W * Cn, H * W * Cn
+    out, out_tensor, optr, osr, osf = _frames_out(out, (shape, (B, H, W, Cn)), L.tensor if out_on_device is None else bool(out_on_device), device)
     opts = ConvertOpts()
     opts.frames_on_device, opts.out_on_device = 1 if L.tensor else 0, 1 if out_tensor else 0
     opts.out_format, opts.chunk_frames = PIXEL_FORMATS[fmt], int(chunk_frames)
-    if L.tensor or out_tensor:
-        import torch
-        torch.cuda.current_stream(device).synchronize()      # planes and out are complete before the library touches them
-    optr = out.data_ptr() if out_tensor else out.ctypes.data
+    _synced(device, also=L.tensor or out_tensor)             # the planes' addresses are in L
     _check(lib.sba_convert_frames(device, C.c_void_p(L.y), C.c_void_p(L.u), C.c_void_p(L.v), B, H, W, L.y_row_pitch, L.y_frame_pitch,
                                   L.c_row_pitch, L.c_frame_pitch, L.c_step, None if m is None else C.byref(m), osr, osf, C.byref(opts),
                                   C.c_void_p(optr)))
@@ -1099,27 +1078,10 @@ def resize_frames(frames, fx, fy, gray_w=None, out=None, out_on_device=None, chu
         opts.gray, opts.gray_w = 1, (C.c_int32 * 3)(*vals)
     Ho, Wo, Co = H // fy, W // fx, 1 if gray_w is not None else Cn
     shape = (B, Ho, Wo, Cn) if gray_w is None and len(frames.shape) == 4 else (B, Ho, Wo)
-    if out is not None:
-        out_tensor = _is_tensor(out)
-        if not out_tensor and not (isinstance(out, np.ndarray) and out.flags.writeable):
-            raise ValueError("out must be a writeable numpy array or a tensor on the device")
-        if tuple(out.shape) not in ((B, Ho, Wo, Co), (B, Ho, Wo) if Co == 1 else None):
-            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shape}")
-        _t, _o, _B, _H, _W, _C, osr, osf = _frame_layout(out, device)
-    else:
-        out_tensor = tensor if out_on_device is None else bool(out_on_device)
-        if out_tensor:
-            import torch
-            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{device}")
-        else:
-            out = np.empty(shape, np.uint8)
-        osr, osf = Wo * Co, Ho * Wo * Co
+    shapes = (shape, (B, Ho, Wo, Co), (B, Ho, Wo) if Co == 1 else None)
+    out, out_tensor, optr, osr, osf = _frames_out(out, shapes, tensor if out_on_device is None else bool(out_on_device), device)
     opts.frames_on_device, opts.out_on_device, opts.chunk_frames = 1 if tensor else 0, 1 if out_tensor else 0, int(chunk_frames)
-    if tensor or out_tensor:
-        import torch
-        torch.cuda.current_stream(device).synchronize()      # frames and out are complete before the library touches them
-    ptr = frames.data_ptr() if tensor else frames.ctypes.data
-    optr = out.data_ptr() if out_tensor else out.ctypes.data
+    ptr = _synced(device, frames, also=out_tensor)
     _check(lib.sba_resize_frames(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, fx, fy, osr, osf, C.byref(opts), C.c_void_p(optr)))
     return out
 

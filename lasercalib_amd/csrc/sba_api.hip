@@ -403,17 +403,33 @@ static int frame_args_invalid(const char* fn, const uint8_t* frames, int64_t n_f
   return SBA_OK;
 }
 
-// the pitches, the size limit (`why_limit` ends its text), the device
-static int frame_layout_invalid(const char* fn, int device, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                                int64_t row_pitch, int64_t frame_pitch, const char* why_limit) {
-  if (row_pitch < (int64_t)width * channels) return detect_invalid(fn, "row_pitch is smaller than width * channels");
-  if ((__int128)height * row_pitch > frame_pitch) return detect_invalid(fn, "frame_pitch is smaller than height * row_pitch");
-  if ((__int128)n_frames * frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * frame_pitch overflows");
+// the size limit (`why_limit` ends its text), the device
+static int frame_limit_invalid(const char* fn, int device, int32_t height, int32_t width, const char* why_limit) {
   if (height > 16384 || width > 16384) {
     g_last_error = std::string(fn) + ": width and height are limited to 16384" + why_limit;
     return SBA_ERR_UNSUPPORTED;
   }
   return check_device(device);
+}
+
+// the pitches, then frame_limit_invalid
+static int frame_layout_invalid(const char* fn, int device, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                                int64_t row_pitch, int64_t frame_pitch, const char* why_limit) {
+  if (row_pitch < (int64_t)width * channels) return detect_invalid(fn, "row_pitch is smaller than width * channels");
+  if ((__int128)height * row_pitch > frame_pitch) return detect_invalid(fn, "frame_pitch is smaller than height * row_pitch");
+  if ((__int128)n_frames * frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * frame_pitch overflows");
+  return frame_limit_invalid(fn, device, height, width, why_limit);
+}
+
+// The pitches of an output of n_frames frames of `rows` rows of `row_bytes` bytes.  Each entry point words the first two
+// texts in its own terms: `row_text` in full, `rows_text` is what it calls the rows; `overflow_text` as well where it differs.
+static int out_pitch_invalid(const char* fn, int64_t n_frames, int64_t rows, int64_t row_bytes, int64_t out_row_pitch, int64_t out_frame_pitch,
+                             const char* row_text, const char* rows_text, const char* overflow_text = "n_frames * out_frame_pitch overflows") {
+  if (out_row_pitch < row_bytes) return detect_invalid(fn, row_text);
+  if ((__int128)rows * out_row_pitch > out_frame_pitch)
+    return detect_invalid(fn, (std::string("out_frame_pitch is smaller than ") + rows_text + " * out_row_pitch").c_str());
+  if ((__int128)n_frames * out_frame_pitch > INT64_MAX) return detect_invalid(fn, overflow_text);
+  return SBA_OK;
 }
 
 int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -475,12 +491,9 @@ int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, in
   if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
   if (o.border_value < 0 || o.border_value > 255) return detect_invalid(fn, "border_value must be in 0..255");
   if (!out && n_frames > 0 && !flags_out && !map_out) return detect_invalid(fn, "null out and no diagnostic asked for");
-  if (out) {
-    if (out_row_pitch < (int64_t)out_width * channels) return detect_invalid(fn, "out_row_pitch is smaller than out_width * channels");
-    if ((__int128)out_height * out_row_pitch > out_frame_pitch) return detect_invalid(fn, "out_frame_pitch is smaller than out_height * out_row_pitch");
-    if ((__int128)n_frames * out_frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * out_frame_pitch overflows");
-  }
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (out) rc = out_pitch_invalid(fn, n_frames, out_height, (int64_t)out_width * channels, out_row_pitch, out_frame_pitch,
+                                  "out_row_pitch is smaller than out_width * channels", "out_height");
+  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
   if (rc) return rc;
   return guarded(nullptr, [&] {
     return sba_undistort_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, *lens, new_k, out_height, out_width,
@@ -521,10 +534,8 @@ int sba_background_suppress(int device, const uint8_t* frames, int64_t n_frames,
   if (rc) return rc;
   if (o.mode != SBA_BG_GATE && o.mode != SBA_BG_SUBTRACT) return detect_invalid(fn, "mode must be 0 (gate) or 1 (subtract)");
   if (!out && n_frames > 0) return detect_invalid(fn, "null out");
-  if (out_row_pitch < (int64_t)width) return detect_invalid(fn, "out_row_pitch is smaller than width");
-  if ((__int128)height * out_row_pitch > out_frame_pitch) return detect_invalid(fn, "out_frame_pitch is smaller than height * out_row_pitch");
-  if ((__int128)n_frames * out_frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * out_frame_pitch overflows");
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  rc = out_pitch_invalid(fn, n_frames, height, width, out_row_pitch, out_frame_pitch, "out_row_pitch is smaller than width", "height");
+  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
   if (rc || n_frames == 0) return rc;
   return guarded(nullptr, [&] {
     return sba_bg_suppress_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, level, mask, out_row_pitch,
@@ -559,16 +570,12 @@ int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uin
   if ((__int128)height * y_row_pitch > y_frame_pitch) return detect_invalid(fn, "y_frame_pitch is smaller than height * y_row_pitch");
   if (cw > 0 && c_row_pitch < c_step * (cw - 1) + 1) return detect_invalid(fn, "c_row_pitch is smaller than c_step * ((width + 1) / 2 - 1) + 1");
   if (c_row_pitch < 0 || (__int128)ch * c_row_pitch > c_frame_pitch) return detect_invalid(fn, "c_frame_pitch is smaller than ((height + 1) / 2) * c_row_pitch");
-  if (out_row_pitch < width * px) return detect_invalid(fn, "out_row_pitch is smaller than width * bytes of a pixel");
-  if ((__int128)height * out_row_pitch > out_frame_pitch) return detect_invalid(fn, "out_frame_pitch is smaller than height * out_row_pitch");
-  if ((__int128)n_frames * y_frame_pitch > INT64_MAX || (__int128)n_frames * c_frame_pitch > INT64_MAX ||
-      (__int128)n_frames * out_frame_pitch > INT64_MAX)
-    return detect_invalid(fn, "n_frames * a frame pitch overflows");
-  if (height > 16384 || width > 16384) {
-    g_last_error = std::string(fn) + ": width and height are limited to 16384";
-    return SBA_ERR_UNSUPPORTED;
-  }
-  const int rc = check_device(device);
+  const char* overflows = "n_frames * a frame pitch overflows";           // one text for the three pitches
+  int rc = out_pitch_invalid(fn, n_frames, height, width * px, out_row_pitch, out_frame_pitch,
+                             "out_row_pitch is smaller than width * bytes of a pixel", "height", overflows);
+  if (rc) return rc;
+  if ((__int128)n_frames * y_frame_pitch > INT64_MAX || (__int128)n_frames * c_frame_pitch > INT64_MAX) return detect_invalid(fn, overflows);
+  rc = frame_limit_invalid(fn, device, height, width, "");
   if (rc || n_frames == 0) return rc;
   return guarded(nullptr, [&] {
     return sba_convert_call(device, y, u, v, n_frames, height, width, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, m,
@@ -593,11 +600,9 @@ int sba_resize_frames(int device, const uint8_t* frames, int64_t n_frames, int32
     if ((int64_t)o.gray_w[0] + o.gray_w[1] + o.gray_w[2] != 1 << 15) return detect_invalid(fn, "the gray weights must sum to 2^15");
   }
   if (!out && n_frames > 0) return detect_invalid(fn, "null out");
-  const int64_t out_h = height / fy, out_w = width / fx, px = o.gray ? 1 : channels;
-  if (out_row_pitch < out_w * px) return detect_invalid(fn, "out_row_pitch is smaller than (width / fx) times the bytes of an output pixel");
-  if ((__int128)out_h * out_row_pitch > out_frame_pitch) return detect_invalid(fn, "out_frame_pitch is smaller than (height / fy) * out_row_pitch");
-  if ((__int128)n_frames * out_frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * out_frame_pitch overflows");
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  rc = out_pitch_invalid(fn, n_frames, height / fy, (int64_t)(width / fx) * (o.gray ? 1 : channels), out_row_pitch, out_frame_pitch,
+                         "out_row_pitch is smaller than (width / fx) times the bytes of an output pixel", "(height / fy)");
+  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
   if (rc || n_frames == 0) return rc;
   return guarded(nullptr, [&] {
     return sba_resize_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, fx, fy, out_row_pitch, out_frame_pitch,

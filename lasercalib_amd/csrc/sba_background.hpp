@@ -20,7 +20,7 @@
 // walks the frames of its share.  The output leaves as 16-byte stores; padding is never written.
 // How frames are described and staged chunk by chunk is sba_frames.hpp.
 #pragma once
-#include "sba_undistort.hpp"
+#include "sba_frames.hpp"
 
 namespace sba_detect {
 
@@ -49,21 +49,6 @@ struct BgGroup {
   static constexpr int NPIX = (16 + C - 1) / C;
 };
 
-// The values of the channel whose first byte lies j0 (0..3) bytes into v, one every C bytes; a byte beyond the 16 reads as 0.
-template <int C>
-__device__ __forceinline__ void bg_decode(const uint4& v, uint32_t j0, uint32_t (&b)[BgGroup<C>::NPIX]) {
-  uint32_t d[4];
-  if (C == 1) { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
-  else {
-    d[0] = __builtin_amdgcn_alignbyte(v.y, v.x, j0);
-    d[1] = __builtin_amdgcn_alignbyte(v.z, v.y, j0);
-    d[2] = __builtin_amdgcn_alignbyte(v.w, v.z, j0);
-    d[3] = __builtin_amdgcn_alignbyte(0u, v.w, j0);
-  }
-#pragma unroll
-  for (int k = 0; k < BgGroup<C>::NPIX; ++k) b[k] = (d[(k * C) >> 2] >> (8 * ((k * C) & 3))) & 0xffu;
-}
-
 // a launch walks at most DOT_MAX_CHUNK = 16384 frames: 255^2 * 16384 < 2^32, the square sum of a share fits 32 bits
 template <int C, bool ALL>
 struct BgAcc {
@@ -74,8 +59,10 @@ struct BgAcc {
     for (int k = 0; k < N; ++k) s[k] = q[k] = h[k] = m[k] = 0u;
   }
   __device__ __forceinline__ void fold(const uint4& v, uint32_t j0, uint32_t thr) {
-    uint32_t b[N];
-    bg_decode<C>(v, j0, b);
+    uint32_t d[4], b[N];
+    channel_words<C>(v, j0, d);
+#pragma unroll
+    for (int k = 0; k < N; ++k) b[k] = channel_byte<C>(d, k);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       s[k] += b[k];
@@ -300,10 +287,7 @@ inline int bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frame
                               uint32_t* sum, uint64_t* sumsq, uint32_t* hot, uint8_t* vmax, uint64_t* n_used) {
   const int64_t px = (int64_t)height * width;
   const bool fresh = o.accumulate == 0, frames_dev = o.frames_on_device != 0, stats_dev = o.stats_on_device != 0;
-  int64_t chunk = DOT_MAX_CHUNK;
-  if (o.chunk_frames > 0) chunk = o.chunk_frames;
-  else if (!frames_dev) chunk = std::max<int64_t>(1, DOT_STAGE_BYTES / std::max<int64_t>(1, (int64_t)width * channels * height));
-  chunk = std::max<int64_t>(1, std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames));
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, frames_dev ? 0 : (int64_t)width * channels * height);
 
   // the frames that take part, chunk by chunk, numbered from the chunk's first frame
   const int64_t n_chunks = n_frames > 0 ? (n_frames + chunk - 1) / chunk : 0;
@@ -395,7 +379,7 @@ inline int bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frame
         bg_accumulate_launch(P, channels, all, st);
         P.add = 1;
       },
-      [](int64_t, int64_t, hipStream_t) {}, [](int64_t, int64_t) {});
+      [](int64_t, int64_t, hipStream_t) {});
   if (P.vmax32) {
     hipLaunchKernelGGL(k_bg_fold_max, dim3((unsigned)((px + BG_THREADS - 1) / BG_THREADS)), dim3(BG_THREADS), 0, s0.s, P.vmax, P.vmax32, px,
                        fresh ? 0 : 1);
@@ -407,7 +391,7 @@ inline int bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frame
 }
 
 // Arguments are checked by the caller (sba_api.hip).  Level and mask in host memory are copied to the device once; frames and
-// output pass through the device as in undistort_call.
+// output pass through the device as sba_frames.hpp has it (frames_in_chunks, FrameOutput).
 inline int bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                             int64_t row_pitch, int64_t frame_pitch, const uint8_t* level, const uint8_t* mask, int64_t out_row_pitch,
                             int64_t out_frame_pitch, const sba_background_suppress_opts& o, uint8_t* out) {
@@ -420,24 +404,21 @@ inline int bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames,
   P.V = frame_view(frames, row_pitch, frame_pitch, height, width, o.channel, 0, whole, whole);
   P.level = level; P.mask = mask; P.mode = o.mode;
   P.row_groups = (width + 15) / 16;
-  DevBuf<uint8_t> d_level, d_mask, d_out;
+  DevBuf<uint8_t> d_level, d_mask;
   if (!o.model_on_device) {
     if (level) { d_level.alloc((size_t)px); HIPCHK(hipMemcpy(d_level.p, level, (size_t)px, hipMemcpyHostToDevice)); P.level = d_level.p; }
     if (mask) { d_mask.alloc((size_t)px); HIPCHK(hipMemcpy(d_mask.p, mask, (size_t)px, hipMemcpyHostToDevice)); P.mask = d_mask.p; }
   }
-  int64_t chunk = DOT_MAX_CHUNK;
-  if (o.chunk_frames > 0) chunk = o.chunk_frames;
-  else if (!in_dev || !out_dev) chunk = std::max<int64_t>(1, DOT_STAGE_BYTES / std::max<int64_t>(1, (int64_t)width * channels * height));
-  chunk = std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames);
-  if (!out_dev) d_out.alloc((size_t)(chunk * px));
+  // the packed output of a frame is never larger than the frame
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : (int64_t)width * channels * height);
+  FrameOutput O(out, out_row_pitch, out_frame_pitch, width, height, out_dev, chunk);
 
   const int64_t blocks = ((int64_t)height * P.row_groups + BG_THREADS - 1) / BG_THREADS;
   frames_in_chunks(
       P.V, channels, n_frames, in_dev, chunk,
       [&](const FrameView& V, int64_t lo, int64_t m, hipStream_t st) {
         P.V = V;
-        if (out_dev) { P.out = out + lo * out_frame_pitch; P.out_row_pitch = out_row_pitch; P.out_frame_pitch = out_frame_pitch; }
-        else { P.out = d_out.p; P.out_row_pitch = width; P.out_frame_pitch = px; }
+        O.target(lo, P.out, P.out_row_pitch, P.out_frame_pitch);
         unsigned groups;
         bg_shares(blocks, m, 1, P.frames_per_group, groups);              // which share takes a frame does not change its bytes
         const dim3 grid((unsigned)blocks, groups);
@@ -446,10 +427,7 @@ inline int bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames,
         else hipLaunchKernelGGL(k_bg_suppress<4>, grid, dim3(BG_THREADS), 0, st, P, (int)m);
         HIPCHK(hipGetLastError());
       },
-      [&](int64_t lo, int64_t m, hipStream_t st) {
-        if (!out_dev) ud_fetch(out + lo * out_frame_pitch, out_row_pitch, out_frame_pitch, d_out.p, width, height, m, st);
-      },
-      [](int64_t, int64_t) {});
+      [&](int64_t lo, int64_t m, hipStream_t st) { O.fetch(lo, m, st); });
   return SBA_OK;
 }
 

@@ -69,14 +69,6 @@ inline void blob_halfwidths(int r1, int r2, int8_t* hwd, int8_t* hwe) {
   for (int d = 0; d <= BLOB_MAX_RADIUS; ++d) hwe[d] = (int8_t)(d <= r2 ? hw(r2, d) : -1);
 }
 
-// LDS traffic between the lanes of ONE wave: the wave's DS operations complete in issue order; the fences keep the compiler
-// from moving accesses across
-__device__ __forceinline__ void blob_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ void k_blob_init(u64* __restrict__ table, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -115,7 +107,7 @@ __global__ void __launch_bounds__(DOT_THREADS) k_blob_threshold(const BlobParams
   const uint8_t* __restrict__ fp = P.frames + (int64_t)f * P.frame_pitch;
   u64* myrow = s_row[wave];
   for (int i = lane; i < P.ww; i += 64) myrow[i] = 0;
-  blob_wave_sync();
+  wave_lds_sync();
 
   for (int y = band_lo + wave; y < band_hi; y += DOT_WAVES) {
     u64* __restrict__ out = raw + ((size_t)f * P.height + y) * P.ww;
@@ -126,9 +118,9 @@ __global__ void __launch_bounds__(DOT_THREADS) k_blob_threshold(const BlobParams
       for (int i = lane; i < P.ww; i += 64) out[i] = 0;
       continue;
     }
-    blob_wave_sync();
+    wave_lds_sync();
     for (int i = lane; i < P.ww; i += 64) { out[i] = myrow[i]; myrow[i] = 0; }
-    blob_wave_sync();
+    wave_lds_sync();
   }
 }
 
@@ -621,10 +613,9 @@ inline int blob_call(int device, const uint8_t* frames, int64_t n_frames, int32_
   const int64_t tight_frame = (int64_t)width * channels * height;
   const int64_t px = (int64_t)height * width, words = (int64_t)height * P.ww;
   const int64_t per_frame = px * 5 + words * 16 + (int64_t)height * 8 + (int64_t)K * BLOB_NREC * 8 + 4;
-  int64_t chunk = std::max<int64_t>(1, BLOB_SCRATCH_BYTES / per_frame);
-  if (!on_device) chunk = std::min(chunk, std::max<int64_t>(1, DOT_STAGE_BYTES / tight_frame));
+  // chunk_frames is a cap here, not a request: the library's own choice, within the scratch budget, bounds it
+  int64_t chunk = std::min(frames_per_chunk(0, n_frames, on_device ? 0 : tight_frame), std::max<int64_t>(1, BLOB_SCRATCH_BYTES / per_frame));
   if (o.chunk_frames > 0) chunk = std::min<int64_t>(chunk, o.chunk_frames);
-  chunk = std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames);
 
   DevBuf<uint8_t> d_vals;
   DevBuf<u64> d_raw, d_mask, d_table;

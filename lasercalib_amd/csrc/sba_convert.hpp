@@ -216,30 +216,11 @@ inline void cv_launch(const CvParams& P, int fmt, int64_t nf, hipStream_t st) {
   HIPCHK(hipGetLastError());
 }
 
-// m frames of `rows` rows of `row_bytes` bytes from pitched memory on one side to pitched memory on the other
-inline void cv_copy(uint8_t* dst, int64_t d_row, int64_t d_frame, const uint8_t* src, int64_t s_row, int64_t s_frame, int64_t row_bytes,
-                    int64_t rows, int64_t m, hipMemcpyKind kind, hipStream_t st) {
-  if (row_bytes == 0 || rows == 0) return;
-  const int64_t tight = row_bytes * rows;
-  if (d_row == row_bytes && s_row == row_bytes && d_frame == tight && s_frame == tight)
-    HIPCHK(hipMemcpyAsync(dst, src, (size_t)(m * tight), kind, st));
-  else if (d_row == row_bytes && s_row == row_bytes)                      // packed rows, frames apart: a plane of a stacked frame
-    for (int64_t i = 0; i < m; ++i) HIPCHK(hipMemcpyAsync(dst + i * d_frame, src + i * s_frame, (size_t)tight, kind, st));
-  else if (d_frame == d_row * rows && s_frame == s_row * rows)
-    HIPCHK(hipMemcpy2DAsync(dst, (size_t)d_row, src, (size_t)s_row, (size_t)row_bytes, (size_t)(m * rows), kind, st));
-  else
-    for (int64_t i = 0; i < m; ++i)
-      HIPCHK(hipMemcpy2DAsync(dst + i * d_frame, (size_t)d_row, src + i * s_frame, (size_t)s_row, (size_t)row_bytes, (size_t)rows, kind, st));
-}
-
-// Arguments are checked by the caller (sba_api.hip).  Planes on the device are read, and an output on the device is written,
-// where they are.  Host planes go through two staging buffers of a chunk each, rows packed: the luma plane, then the chroma --
-// ONE plane of 2 ceil(width / 2) bytes a row when u and v are the two halves of an interleaved plane (NV12, NV21), else two
-// planes of c_step (ceil(width / 2) - 1) + 1 bytes a row.  A host output goes through one packed device buffer of a chunk,
-// fetched into the caller's pitches before the chunk is drained.  The order of copies and kernels is that of frames_in_chunks
-// (sba_frames.hpp): the copy of chunk k + 1 is queued on a second stream behind the kernel of chunk k and in front of anything
-// that can make the host wait.  A chunk is chunk_frames frames, by default what fits DOT_STAGE_BYTES on the larger side when
-// one of them is host memory.  Which chunk or buffer a frame passes through does not enter its arithmetic.
+// Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (frames_per_chunk
+// on the larger side when one of them is host memory, frames_in_chunks, FrameOutput).  What is staged is the luma plane, then
+// the chroma: ONE plane of 2 ceil(width / 2) bytes a row when u and v are the two halves of an interleaved plane (NV12, NV21),
+// else two planes of c_step (ceil(width / 2) - 1) + 1 bytes a row.  Which chunk or buffer a frame passes through does not
+// enter its arithmetic.
 inline int convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height, int32_t width,
                         int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step,
                         const sba_yuv_matrix& M, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& o, uint8_t* out) {
@@ -256,51 +237,23 @@ inline int convert_call(int device, const uint8_t* y, const uint8_t* u, const ui
   const bool paired = P.c_mode == CV_UV || P.c_mode == CV_VU;
   const uint8_t* c_lo = P.c_mode == CV_VU ? v : u;                        // the plane the kernel's `u` stands for
 
-  const int64_t y_tight = (int64_t)width * height;
-  const int64_t c_row = paired ? 2 * cw : (int64_t)c_step * (cw - 1) + 1, c_tight = c_row * ch;
-  const int64_t in_tight = y_tight + (paired ? 1 : 2) * c_tight, out_row = (int64_t)width * C, out_tight = out_row * height;
-  int64_t chunk = DOT_MAX_CHUNK;
-  if (o.chunk_frames > 0) chunk = o.chunk_frames;
-  else if (!in_dev || !out_dev) chunk = std::max<int64_t>(1, DOT_STAGE_BYTES / std::max(in_tight, out_tight));
-  chunk = std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames);
-
-  DotStream s_run, s_copy;
-  DotEvent ev_copied[2];
-  DevBuf<uint8_t> d_stage[2], d_out;
-  if (!in_dev)
-    for (int b = 0; b < (n_frames > chunk ? 2 : 1); ++b) d_stage[b].alloc((size_t)(chunk * in_tight));
-  if (!out_dev) d_out.alloc((size_t)(chunk * out_tight));
-  auto stage = [&](int64_t lo, int b) {            // host frames [lo, lo + m) -> d_stage[b]: [m luma][m chroma]([m chroma])
-    const int64_t m = std::min(chunk, n_frames - lo);
-    uint8_t* d = d_stage[b].p;
-    cv_copy(d, width, y_tight, y + lo * y_frame_pitch, y_row_pitch, y_frame_pitch, width, height, m, hipMemcpyHostToDevice, s_copy.s);
-    d += chunk * y_tight;
-    cv_copy(d, c_row, c_tight, c_lo + lo * c_frame_pitch, c_row_pitch, c_frame_pitch, c_row, ch, m, hipMemcpyHostToDevice, s_copy.s);
-    if (!paired) cv_copy(d + chunk * c_tight, c_row, c_tight, v + lo * c_frame_pitch, c_row_pitch, c_frame_pitch, c_row, ch, m, hipMemcpyHostToDevice, s_copy.s);
-    HIPCHK(hipEventRecord(ev_copied[b].e, s_copy.s));
-  };
-
-  if (!in_dev) stage(0, 0);
-  int b = 0;
-  for (int64_t lo = 0; lo < n_frames; lo += chunk, b ^= 1) {
-    const int64_t m = std::min(chunk, n_frames - lo);
-    if (in_dev) {
-      P.y = y + lo * y_frame_pitch; P.u = c_lo + lo * c_frame_pitch; P.v = v + lo * c_frame_pitch;
-      P.y_row_pitch = y_row_pitch; P.y_frame_pitch = y_frame_pitch; P.c_row_pitch = c_row_pitch; P.c_frame_pitch = c_frame_pitch;
-    } else {
-      P.y = d_stage[b].p; P.u = P.y + chunk * y_tight; P.v = P.u + chunk * c_tight;     // paired: v is not read
-      P.y_row_pitch = width; P.y_frame_pitch = y_tight; P.c_row_pitch = c_row; P.c_frame_pitch = c_tight;
-      HIPCHK(hipStreamWaitEvent(s_run.s, ev_copied[b].e, 0));
-    }
-    if (out_dev) { P.out = out + lo * out_frame_pitch; P.out_row_pitch = out_row_pitch; P.out_frame_pitch = out_frame_pitch; }
-    else { P.out = d_out.p; P.out_row_pitch = out_row; P.out_frame_pitch = out_tight; }
-    cv_launch(P, o.out_format, m, s_run.s);
-    if (!in_dev && lo + chunk < n_frames) stage(lo + chunk, b ^ 1);
-    if (!out_dev)
-      cv_copy(out + lo * out_frame_pitch, out_row_pitch, out_frame_pitch, d_out.p, out_row, out_tight, out_row, height, m, hipMemcpyDeviceToHost, s_run.s);
-    HIPCHK(hipStreamSynchronize(s_run.s));
-  }
-  HIPCHK(hipStreamSynchronize(s_copy.s));
+  const int64_t c_row = paired ? 2 * cw : (int64_t)c_step * (cw - 1) + 1, out_row = (int64_t)width * C;
+  const int n_planes = paired ? 2 : 3;                                    // luma, the kernel's u, and v when it is a plane of its own
+  const FramePlane planes[3] = {{y, y_row_pitch, y_frame_pitch, width, height},
+                                {c_lo, c_row_pitch, c_frame_pitch, c_row, ch},
+                                {v, c_row_pitch, c_frame_pitch, c_row, ch}};
+  const int64_t in_tight = (int64_t)width * height + (n_planes - 1) * c_row * ch;
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(in_tight, out_row * height));
+  FrameOutput O(out, out_row_pitch, out_frame_pitch, out_row, height, out_dev, chunk);
+  frames_in_chunks(
+      planes, n_planes, n_frames, in_dev, chunk,
+      [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {
+        P.y = c[0].base; P.u = c[1].base; P.v = c[n_planes - 1].base;      // paired: v is not read
+        P.y_row_pitch = c[0].row_pitch; P.y_frame_pitch = c[0].frame_pitch; P.c_row_pitch = c[1].row_pitch; P.c_frame_pitch = c[1].frame_pitch;
+        O.target(lo, P.out, P.out_row_pitch, P.out_frame_pitch);
+        cv_launch(P, o.out_format, m, st);
+      },
+      [&](int64_t lo, int64_t m, hipStream_t st) { O.fetch(lo, m, st); });
   return SBA_OK;
 }
 

@@ -213,13 +213,7 @@ inline int dot_call(int device, const uint8_t* frames, int64_t n_frames, int32_t
   P.min_area = o.min_area; P.max_area = o.max_area; P.max_extent = o.max_extent;
 
   const bool on_device = o.frames_on_device != 0;
-  int64_t chunk = DOT_MAX_CHUNK;
-  if (!on_device) {
-    const int64_t tight_frame = (int64_t)width * channels * height;
-    chunk = o.chunk_frames > 0 ? o.chunk_frames : std::max<int64_t>(1, DOT_STAGE_BYTES / std::max<int64_t>(1, tight_frame));
-    chunk = std::min(chunk, DOT_MAX_CHUNK);
-  }
-  chunk = std::min(chunk, n_frames);
+  const int64_t chunk = frames_per_chunk(on_device ? 0 : o.chunk_frames, n_frames, on_device ? 0 : (int64_t)width * channels * height);
 
   DevBuf<unsigned long long> d_sums;
   DevBuf<int> d_box, d_st;
@@ -236,8 +230,7 @@ inline int dot_call(int device, const uint8_t* frames, int64_t n_frames, int32_t
         if (box) HIPCHK(hipMemcpyAsync(box + lo * 4, d_box.p, sizeof(int32_t) * m * 4, hipMemcpyDeviceToHost, st));
         if (centroid) HIPCHK(hipMemcpyAsync(centroid + lo * 4, d_cen.p, sizeof(double) * m * 4, hipMemcpyDeviceToHost, st));
         if (status) HIPCHK(hipMemcpyAsync(status + lo, d_st.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-      },
-      [](int64_t, int64_t) {});
+      });
   return SBA_OK;
 }
 

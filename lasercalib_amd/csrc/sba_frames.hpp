@@ -1,9 +1,12 @@
-// sba_frames.hpp -- how the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp: connected components) read a batch
-// of 8-bit frames with interleaved channels: any base address, any pitches, from the host or the device, with a rectangle and a
-// circle of interest.  Everything between "such a batch" and "the bytes of row y that count" is here, once: the description a
-// kernel gets (FrameView), the pixels of a row inside both regions (frame_row_span), one wave's walk over them (scan_row), the
-// rows of a workgroup (frame_rows_per_band) and the host's loop over chunks of frames with its staging (frames_in_chunks).
-// What is done with a pixel once it is found is the consumer's sink (DotSink, BlobSink).
+// sba_frames.hpp -- what the frame functions share.  How the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
+// connected components) read a batch of 8-bit frames with interleaved channels -- any base address, any pitches, from the host
+// or the device, with a rectangle and a circle of interest -- is here, once: the description a kernel gets (FrameView), the
+// pixels of a row inside both regions (frame_row_span), one wave's walk over them (scan_row), the rows of a workgroup
+// (frame_rows_per_band); what is done with a pixel once it is found is the consumer's sink (DotSink, BlobSink).  So are the
+// device helpers that more than one kernel uses (wave_lds_sync, channel_words / channel_byte) and ALL host-side plumbing of
+// every frame function (the "host side" below): chunk size, pitched copies, the loop over chunks with its staging, the output.
+// (The store of a finished LDS row at any alignment stays written out in k_undistort and k_resize: as a shared function it
+// compiled to other instructions in both.)
 #pragma once
 #include "sba_common.hpp"
 
@@ -66,16 +69,19 @@ __device__ __forceinline__ bool frame_row_span(const FrameView& V, int y, int& x
   return xa < xb;
 }
 
-// The 16 bytes `v` start at byte s of the row.  Hands the values of the pixels whose thresholded channel lies in them to the
-// sink; returns false, having done nothing else, when no lane of the wave has one above the threshold (the usual case: frames
-// are dark but for the dot).  A byte shifted in from beyond the 16 is zero and never above a threshold >= 0.
-template <int C, class Sink>
-__device__ __forceinline__ bool scan_vector(const uint4& v, uint32_t s, uint32_t channel, uint32_t thr, Sink& sink) {
-  constexpr int NPIX = (16 + C - 1) / C;
-  const uint32_t q = s / C, r = s - q * C;
-  const uint32_t j0 = channel >= r ? channel - r : channel + C - r;      // first byte of the channel at or after s
-  const uint32_t xq = q + (channel < r ? 1u : 0u);
-  uint32_t d[4];
+// LDS traffic between the lanes of ONE wave: the wave's DS operations complete in issue order; the fences keep the compiler
+// from moving accesses across
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The channel bytes of a 16-byte group v of pixels with C channels, in two steps.  channel_words: the group shifted so that the
+// channel's first byte, j0 (0..3) bytes into v, is byte 0; a byte shifted in from beyond the 16 is 0.  channel_byte: value k of
+// the channel, byte k C of those words -- a constant shift once k is one.
+template <int C>
+__device__ __forceinline__ void channel_words(const uint4& v, uint32_t j0, uint32_t (&d)[4]) {
   if (C == 1) { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
   else {
     d[0] = __builtin_amdgcn_alignbyte(v.y, v.x, j0);
@@ -83,10 +89,25 @@ __device__ __forceinline__ bool scan_vector(const uint4& v, uint32_t s, uint32_t
     d[2] = __builtin_amdgcn_alignbyte(v.w, v.z, j0);
     d[3] = __builtin_amdgcn_alignbyte(0u, v.w, j0);
   }
+}
+template <int C>
+__device__ __forceinline__ uint32_t channel_byte(const uint32_t (&d)[4], int k) { return (d[(k * C) >> 2] >> (8 * ((k * C) & 3))) & 0xffu; }
+
+// The 16 bytes `v` start at byte s of the row.  Hands the values of the pixels whose thresholded channel lies in them to the
+// sink; returns false, having done nothing else, when no lane of the wave has one above the threshold (the usual case: frames
+// are dark but for the dot).  A byte from beyond the 16 is zero and never above a threshold >= 0.
+template <int C, class Sink>
+__device__ __forceinline__ bool scan_vector(const uint4& v, uint32_t s, uint32_t channel, uint32_t thr, Sink& sink) {
+  constexpr int NPIX = (16 + C - 1) / C;
+  const uint32_t q = s / C, r = s - q * C;
+  const uint32_t j0 = channel >= r ? channel - r : channel + C - r;      // first byte of the channel at or after s
+  const uint32_t xq = q + (channel < r ? 1u : 0u);
+  uint32_t d[4];
+  channel_words<C>(v, j0, d);
   uint32_t b[NPIX], any = 0;
 #pragma unroll
-  for (int k = 0; k < NPIX; ++k) {                                       // byte k C of the 16: a constant after unrolling
-    b[k] = (d[(k * C) >> 2] >> (8 * ((k * C) & 3))) & 0xffu;
+  for (int k = 0; k < NPIX; ++k) {
+    b[k] = channel_byte<C>(d, k);
     any |= b[k] > thr ? 1u : 0u;
   }
   if (!__any(any != 0)) return false;
@@ -132,6 +153,9 @@ __device__ __forceinline__ bool scan_row(const uint8_t* __restrict__ rp, int xa,
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+// Everything between a caller's pointers and pitches and the kernels of a chunk: the size of a chunk (frames_per_chunk), the
+// one routine that moves pitched frames (copy_frames), the loop over chunks with its staging (frames_in_chunks) and the
+// output of a call that writes frames (FrameOutput).
 struct DotStream {
   hipStream_t s = nullptr;
   DotStream() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
@@ -143,39 +167,72 @@ struct DotEvent {
   ~DotEvent() { if (e) (void)hipEventDestroy(e); }
 };
 
-// Takes the n_frames > 0 frames of V in chunks of `chunk` frames (1 <= chunk <= DOT_MAX_CHUNK, the caller's choice).  V is
-// a copy, so a caller may write a chunk's view over its own.  Of the chunk [lo, lo + m) it calls
-//   launch(view, lo, m, stream)   queues the kernels; view.frames points at the chunk's first frame
+// The frames of a chunk: `requested` (an entry point's chunk_frames) when > 0, else as many as fit DOT_STAGE_BYTES at
+// `staged_bytes` a frame -- the larger of what a frame takes in a staging buffer and in the packed buffer of a host output;
+// 0 = neither exists (or the frame has no bytes), and only the launch limits the chunk.  At most DOT_MAX_CHUNK and n_frames,
+// at least 1.
+inline int64_t frames_per_chunk(int64_t requested, int64_t n_frames, int64_t staged_bytes) {
+  int64_t chunk = DOT_MAX_CHUNK;
+  if (requested > 0) chunk = requested;
+  else if (staged_bytes > 0) chunk = std::max<int64_t>(1, DOT_STAGE_BYTES / staged_bytes);
+  return std::max<int64_t>(1, std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames));
+}
+
+// m frames of `rows` rows of `row_bytes` bytes from one pitched layout to another, in either direction, queued on st.  Four
+// classes of layout: both sides packed (one copy); packed rows with frames apart, such as a plane of a stacked frame or frames
+// with a gap (one plain copy per frame -- not a 2-D copy of `rows` rows: the bytes are the same); padded rows with frames of
+// rows x row pitch (one 2-D copy of m x rows rows); anything else (one 2-D copy per frame).
+inline void copy_frames(uint8_t* dst, int64_t d_row, int64_t d_frame, const uint8_t* src, int64_t s_row, int64_t s_frame, int64_t row_bytes,
+                        int64_t rows, int64_t m, hipMemcpyKind kind, hipStream_t st) {
+  if (row_bytes == 0 || rows == 0) return;
+  const int64_t tight = row_bytes * rows;
+  if (d_row == row_bytes && s_row == row_bytes && d_frame == tight && s_frame == tight)
+    HIPCHK(hipMemcpyAsync(dst, src, (size_t)(m * tight), kind, st));
+  else if (d_row == row_bytes && s_row == row_bytes)
+    for (int64_t i = 0; i < m; ++i) HIPCHK(hipMemcpyAsync(dst + i * d_frame, src + i * s_frame, (size_t)tight, kind, st));
+  else if (d_frame == d_row * rows && s_frame == s_row * rows)
+    HIPCHK(hipMemcpy2DAsync(dst, (size_t)d_row, src, (size_t)s_row, (size_t)row_bytes, (size_t)(m * rows), kind, st));
+  else
+    for (int64_t i = 0; i < m; ++i)
+      HIPCHK(hipMemcpy2DAsync(dst + i * d_frame, (size_t)d_row, src + i * s_frame, (size_t)s_row, (size_t)row_bytes, (size_t)rows, kind, st));
+}
+
+// One plane of a batch of frames: frame f, row r at base + f frame_pitch + r row_pitch, row_bytes bytes of it count
+struct FramePlane {
+  const uint8_t* base;
+  int64_t row_pitch, frame_pitch, row_bytes, rows;
+};
+constexpr int FRAME_MAX_PLANES = 3;
+struct FrameNoDone { void operator()(int64_t, int64_t) const {} };
+
+// Takes the n_frames > 0 frames of 1 <= n_planes <= FRAME_MAX_PLANES planes in chunks of `chunk` frames (1 <= chunk <=
+// DOT_MAX_CHUNK: frames_per_chunk).  Of the chunk [lo, lo + m) it calls
+//   launch(planes, lo, m, stream) queues the kernels; planes[p].base points at the chunk's first frame, with its pitches
 //   fetch(lo, m, stream)          queues the copies of the results to the host
-//   done(lo, m)                   after the stream has been drained: the results are on the host
+//   done(lo, m)                   after the stream has been drained: the results are on the host (optional)
 // in that order, so one set of result buffers serves every chunk.  Device frames are read where they are.  Host frames go
-// through two staging buffers of `chunk` frames each, rows packed, filled on a second stream.
+// through two staging buffers of `chunk` frames each, filled on a second stream (one buffer when one chunk is all there is):
+// the frames of plane 0, rows packed, then those of plane 1, ...
 // THE ORDER: the copy of chunk k + 1 is issued after the kernels of chunk k are queued and before anything that can make the
 // host wait for them (a read-back into pageable memory may, the drain does), so the two overlap whether or not the runtime
 // makes a copy from pageable memory wait on the host; the kernels of chunk k + 1 wait on that copy's event.  The buffer the
 // copy writes is free: its kernels were drained with chunk k - 1.  Device memory: the two staging buffers, whatever n_frames is.
-template <class Launch, class Fetch, class Done>
-inline void frames_in_chunks(const FrameView V, int32_t channels, int64_t n_frames, bool on_device, int64_t chunk, Launch&& launch,
-                             Fetch&& fetch, Done&& done) {
-  const int64_t row_bytes = (int64_t)V.width * channels, tight_frame = row_bytes * V.height;
+template <class Launch, class Fetch, class Done = FrameNoDone>
+inline void frames_in_chunks(const FramePlane* planes, int n_planes, int64_t n_frames, bool on_device, int64_t chunk, Launch&& launch,
+                             Fetch&& fetch, Done&& done = Done()) {
+  int64_t tight[FRAME_MAX_PLANES], tight_frame = 0;
+  for (int p = 0; p < n_planes; ++p) tight_frame += tight[p] = planes[p].row_bytes * planes[p].rows;
   DotStream s_run, s_copy;
   DotEvent ev_copied[2];
   DevBuf<uint8_t> d_stage[2];
   if (!on_device)
     for (int b = 0; b < (n_frames > chunk ? 2 : 1); ++b) d_stage[b].alloc((size_t)std::max<int64_t>(16, chunk * tight_frame));
-  auto stage = [&](int64_t lo, int b) {            // host frames [lo, lo + m) -> d_stage[b], rows packed
+  auto stage = [&](int64_t lo, int b) {            // host frames [lo, lo + m) -> d_stage[b]
     const int64_t m = std::min(chunk, n_frames - lo);
-    const uint8_t* src = V.frames + lo * V.frame_pitch;
-    if (tight_frame == 0) { /* nothing to copy */ }
-    else if (V.row_pitch == row_bytes && V.frame_pitch == tight_frame)
-      HIPCHK(hipMemcpyAsync(d_stage[b].p, src, (size_t)(m * tight_frame), hipMemcpyHostToDevice, s_copy.s));
-    else if (V.frame_pitch == V.row_pitch * V.height)
-      HIPCHK(hipMemcpy2DAsync(d_stage[b].p, (size_t)row_bytes, src, (size_t)V.row_pitch, (size_t)row_bytes, (size_t)(m * V.height),
-                              hipMemcpyHostToDevice, s_copy.s));
-    else
-      for (int64_t i = 0; i < m; ++i)
-        HIPCHK(hipMemcpy2DAsync(d_stage[b].p + i * tight_frame, (size_t)row_bytes, src + i * V.frame_pitch, (size_t)V.row_pitch,
-                                (size_t)row_bytes, (size_t)V.height, hipMemcpyHostToDevice, s_copy.s));
+    uint8_t* d = d_stage[b].p;
+    for (int p = 0; p < n_planes; d += chunk * tight[p], ++p)
+      copy_frames(d, planes[p].row_bytes, tight[p], planes[p].base + lo * planes[p].frame_pitch, planes[p].row_pitch,
+                  planes[p].frame_pitch, planes[p].row_bytes, planes[p].rows, m, hipMemcpyHostToDevice, s_copy.s);
     HIPCHK(hipEventRecord(ev_copied[b].e, s_copy.s));
   };
 
@@ -183,13 +240,15 @@ inline void frames_in_chunks(const FrameView V, int32_t channels, int64_t n_fram
   int b = 0;
   for (int64_t lo = 0; lo < n_frames; lo += chunk, b ^= 1) {
     const int64_t m = std::min(chunk, n_frames - lo);
-    FrameView Vc = V;
-    if (on_device) Vc.frames = V.frames + lo * V.frame_pitch;
-    else {
-      Vc.frames = d_stage[b].p; Vc.row_pitch = row_bytes; Vc.frame_pitch = tight_frame;
-      HIPCHK(hipStreamWaitEvent(s_run.s, ev_copied[b].e, 0));
+    FramePlane c[FRAME_MAX_PLANES];
+    uint8_t* d = d_stage[b].p;
+    for (int p = 0; p < n_planes; d += chunk * tight[p], ++p) {
+      c[p] = planes[p];
+      if (on_device) c[p].base += lo * c[p].frame_pitch;
+      else { c[p].base = d; c[p].row_pitch = c[p].row_bytes; c[p].frame_pitch = tight[p]; }
     }
-    launch(Vc, lo, m, s_run.s);
+    if (!on_device) HIPCHK(hipStreamWaitEvent(s_run.s, ev_copied[b].e, 0));
+    launch(c, lo, m, s_run.s);
     if (!on_device && lo + chunk < n_frames) stage(lo + chunk, b ^ 1);
     fetch(lo, m, s_run.s);
     HIPCHK(hipStreamSynchronize(s_run.s));
@@ -197,5 +256,46 @@ inline void frames_in_chunks(const FrameView V, int32_t channels, int64_t n_fram
   }
   HIPCHK(hipStreamSynchronize(s_copy.s));
 }
+
+// The same for frames with interleaved channels, one plane: launch(view, lo, m, stream) gets V with the chunk's first frame
+// and its pitches.  V is a copy, so a caller may write a chunk's view over its own.
+template <class Launch, class Fetch, class Done = FrameNoDone>
+inline void frames_in_chunks(const FrameView V, int32_t channels, int64_t n_frames, bool on_device, int64_t chunk, Launch&& launch,
+                             Fetch&& fetch, Done&& done = Done()) {
+  const FramePlane plane{V.frames, V.row_pitch, V.frame_pitch, (int64_t)V.width * channels, V.height};
+  frames_in_chunks(
+      &plane, 1, n_frames, on_device, chunk,
+      [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {
+        FrameView Vc = V;
+        Vc.frames = c->base; Vc.row_pitch = c->row_pitch; Vc.frame_pitch = c->frame_pitch;
+        launch(Vc, lo, m, st);
+      },
+      fetch, done);
+}
+
+// Where a call that turns frames into frames writes them: n frames of `rows` rows of `row_bytes` bytes.  An output on the
+// device is written where it is, at the caller's pitches.  One on the host goes through ONE packed device buffer of a chunk,
+// owned here: the kernels of a chunk write it, and it is fetched into the caller's pitches on the run stream before the chunk
+// is drained (frames_in_chunks has queued the copy of the next chunk's frames by then, so the two copies run side by side).
+struct FrameOutput {
+  uint8_t* out;
+  int64_t row_pitch, frame_pitch, row_bytes, rows;
+  bool on_device;
+  DevBuf<uint8_t> d_packed;
+  FrameOutput(uint8_t* out_, int64_t row_pitch_, int64_t frame_pitch_, int64_t row_bytes_, int64_t rows_, bool on_device_, int64_t chunk)
+      : out(out_), row_pitch(row_pitch_), frame_pitch(frame_pitch_), row_bytes(row_bytes_), rows(rows_), on_device(on_device_) {
+    if (!on_device) d_packed.alloc((size_t)(chunk * row_bytes * rows));
+  }
+  // what the kernels of the chunk that starts at frame lo write: its first frame and the two pitches
+  void target(int64_t lo, uint8_t*& p, int64_t& row, int64_t& frame) const {
+    if (on_device) { p = out + lo * frame_pitch; row = row_pitch; frame = frame_pitch; }
+    else { p = d_packed.p; row = row_bytes; frame = row_bytes * rows; }
+  }
+  // frames_in_chunks' fetch
+  void fetch(int64_t lo, int64_t m, hipStream_t st) const {
+    if (!on_device)
+      copy_frames(out + lo * frame_pitch, row_pitch, frame_pitch, d_packed.p, row_bytes, row_bytes * rows, row_bytes, rows, m, hipMemcpyDeviceToHost, st);
+  }
+};
 
 }  // namespace sba_detect

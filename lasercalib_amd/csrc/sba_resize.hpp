@@ -20,7 +20,7 @@
 //   * Out: the bytes of the output row are placed in LDS at the alignment of their destination address and leave as 16-byte
 //     stores, with single bytes only in front of the first and behind the last 16-byte boundary of the ADDRESS, as in
 //     sba_undistort.hpp: bases and pitches may be anything, padding is never written.
-// The LDS traffic is between the lanes of one wave (rs_wave_sync); the waves of a workgroup take neighbouring output rows and
+// The LDS traffic is between the lanes of one wave (wave_lds_sync); the waves of a workgroup take neighbouring output rows and
 // never wait for each other.  How frames are staged chunk by chunk is frames_in_chunks (sba_frames.hpp).
 #pragma once
 #include "sba_convert.hpp"
@@ -43,14 +43,6 @@ struct RsParams {
   int32_t half_up;                           // fx == 2 && fy == 2
   float scale;                               // fl32(1.0f / (fx fy)), formed on the host
 };
-
-// LDS traffic between the lanes of ONE wave: the wave's DS operations complete in issue order; the fences keep the compiler
-// from moving accesses across
-__device__ __forceinline__ void rs_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The bytes [off, off + 16) of a row of which [0, nb) may be read; a byte that may not is zero
 __device__ __forceinline__ uint4 rs_load(const uint8_t* __restrict__ rp, int off, int nb) {
@@ -121,14 +113,14 @@ __global__ void __launch_bounds__(DOT_THREADS) k_resize(const RsParams P) {
         for (int q = 0; q < C; ++q) v[q] = rs_load(p, (q * 64 + lane) * 16, nb);
 #pragma unroll
         for (int q = 0; q < C; ++q) *reinterpret_cast<uint4*>(raw + (q * 64 + lane) * 16) = v[q];
-        rs_wave_sync();
+        wave_lds_sync();
         uint32_t w[4 * C];                                   // the lane's 16 pixels
 #pragma unroll
         for (int q = 0; q < C; ++q) {
           const uint4 t = *reinterpret_cast<const uint4*>(raw + lane * (16 * C) + 16 * q);
           w[4 * q] = t.x; w[4 * q + 1] = t.y; w[4 * q + 2] = t.z; w[4 * q + 3] = t.w;
         }
-        rs_wave_sync();                                      // read before the next row overwrites it
+        wave_lds_sync();                                      // read before the next row overwrites it
 #pragma unroll
         for (int k = 0; k < RS_RUN; ++k) {                   // byte k C + c of the 16 C: constants after unrolling
           const uint32_t c0 = cv_byte(w[(k * C) >> 2], (k * C) & 3), c1 = cv_byte(w[(k * C + 1) >> 2], (k * C + 1) & 3),
@@ -139,7 +131,7 @@ __global__ void __launch_bounds__(DOT_THREADS) k_resize(const RsParams P) {
     }
     *reinterpret_cast<uint4*>(sum + lane * RS_RUN) = make_uint4(acc[0], acc[1], acc[2], acc[3]);
     *reinterpret_cast<uint4*>(sum + lane * RS_RUN + 8) = make_uint4(acc[4], acc[5], acc[6], acc[7]);
-    rs_wave_sync();
+    wave_lds_sync();
 
     uint8_t* dst = P.out + (f * P.out_frame_pitch + (int64_t)y * P.out_row_pitch + (int64_t)px0 * IC);
     const int a = (int)(reinterpret_cast<uintptr_t>(dst) & 15u);          // the LDS row lies as the destination does, modulo 16
@@ -149,12 +141,12 @@ __global__ void __launch_bounds__(DOT_THREADS) k_resize(const RsParams P) {
       for (int dx = 0; dx < P.fx; ++dx) s += sum[first + dx * IC];       // first + (fx - 1) IC < nitems
       srow[a + j] = (uint8_t)rs_round(P, s);
     }
-    rs_wave_sync();
+    wave_lds_sync();
     const int head = min(nout, (16 - a) & 15), nv = (nout - head) >> 4, tail = head + nv * 16;   // nv <= 64: a vector per lane
     if (lane < nv) *reinterpret_cast<uint4*>(dst + head + 16 * lane) = *reinterpret_cast<const uint4*>(srow + a + head + 16 * lane);
     const int b = lane < 32 ? lane : tail + (lane - 32);                  // lanes 0..14: in front of the vectors; 32..46: behind
     if (b < (lane < 32 ? head : nout)) dst[b] = srow[a + b];
-    rs_wave_sync();                                          // read before the next row's sums and bytes overwrite them
+    wave_lds_sync();                                          // read before the next row's sums and bytes overwrite them
   }
 }
 
@@ -183,43 +175,31 @@ inline void rs_launch(RsParams P, int channels, bool gray, int64_t nf, hipStream
   HIPCHK(hipGetLastError());
 }
 
-// Arguments are checked by the caller (sba_api.hip): n_frames > 0, both output sizes > 0, the weights set.  Frames on the
-// device are read, and an output on the device is written, where they are.  Host frames go through the two staging buffers of
-// frames_in_chunks; a host output through one packed device buffer of a chunk, fetched into the caller's pitches before the
-// chunk is drained.  A chunk is chunk_frames frames, by default what fits DOT_STAGE_BYTES on the source side when one of the
-// two sides is host memory.  Which chunk, workgroup or buffer a frame passes through does not enter its arithmetic.
+// Arguments are checked by the caller (sba_api.hip): n_frames > 0, both output sizes > 0, the weights set.  Chunks, staging
+// and output are those of sba_frames.hpp (frames_per_chunk on the source side, never the smaller one, when one of the two
+// sides is host memory; frames_in_chunks; FrameOutput).  Which chunk, workgroup or buffer a frame passes through does not
+// enter its arithmetic.
 inline int resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                        int64_t row_pitch, int64_t frame_pitch, int32_t fx, int32_t fy, int64_t out_row_pitch, int64_t out_frame_pitch,
                        const sba_resize_opts& o, uint8_t* out) {
   HIPCHK(hipSetDevice(device));
-  static const int32_t whole[4] = {0, 0, 0, 0};
   const bool gray = o.gray != 0, in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
   RsParams P{};
   P.out_h = height / fy; P.out_w = width / fx; P.fx = fx; P.fy = fy;
   P.w0 = o.gray_w[0]; P.w1 = o.gray_w[1]; P.w2 = o.gray_w[2];
   P.half_up = fx == 2 && fy == 2;
   P.scale = 1.0f / (float)(fx * fy);
-  const int64_t out_row = (int64_t)P.out_w * (gray ? 1 : channels), out_tight = out_row * P.out_h;
-  int64_t chunk = DOT_MAX_CHUNK;
-  if (o.chunk_frames > 0) chunk = o.chunk_frames;
-  else if (!in_dev || !out_dev) chunk = std::max<int64_t>(1, DOT_STAGE_BYTES / ((int64_t)width * channels * height));
-  chunk = std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames);
-
-  DevBuf<uint8_t> d_out;
-  if (!out_dev) d_out.alloc((size_t)(chunk * out_tight));
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : (int64_t)width * channels * height);
+  FrameOutput O(out, out_row_pitch, out_frame_pitch, (int64_t)P.out_w * (gray ? 1 : channels), P.out_h, out_dev, chunk);
+  const FramePlane plane{frames, row_pitch, frame_pitch, (int64_t)width * channels, height};
   frames_in_chunks(
-      frame_view(frames, row_pitch, frame_pitch, height, width, 0, 0, whole, whole), channels, n_frames, in_dev, chunk,
-      [&](const FrameView& V, int64_t lo, int64_t m, hipStream_t st) {
-        P.src = V.frames; P.row_pitch = V.row_pitch; P.frame_pitch = V.frame_pitch;
-        if (out_dev) { P.out = out + lo * out_frame_pitch; P.out_row_pitch = out_row_pitch; P.out_frame_pitch = out_frame_pitch; }
-        else { P.out = d_out.p; P.out_row_pitch = out_row; P.out_frame_pitch = out_tight; }
+      &plane, 1, n_frames, in_dev, chunk,
+      [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {
+        P.src = c->base; P.row_pitch = c->row_pitch; P.frame_pitch = c->frame_pitch;
+        O.target(lo, P.out, P.out_row_pitch, P.out_frame_pitch);
         rs_launch(P, channels, gray, m, st);
       },
-      [&](int64_t lo, int64_t m, hipStream_t st) {
-        if (!out_dev)
-          cv_copy(out + lo * out_frame_pitch, out_row_pitch, out_frame_pitch, d_out.p, out_row, out_tight, out_row, P.out_h, m, hipMemcpyDeviceToHost, st);
-      },
-      [](int64_t, int64_t) {});
+      [&](int64_t lo, int64_t m, hipStream_t st) { O.fetch(lo, m, st); });
   return SBA_OK;
 }
 

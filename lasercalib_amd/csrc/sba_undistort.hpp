@@ -210,25 +210,9 @@ inline void ud_launch(const UdParams& P, int channels, int64_t nf, hipStream_t s
   HIPCHK(hipGetLastError());
 }
 
-// rows of `row_bytes` bytes, `rows` per frame, m frames, between a packed device buffer and pitched host memory
-inline void ud_fetch(uint8_t* dst, int64_t row_pitch, int64_t frame_pitch, const uint8_t* d_src, int64_t row_bytes, int64_t rows, int64_t m,
-                     hipStream_t st) {
-  if (row_pitch == row_bytes && frame_pitch == row_bytes * rows)
-    HIPCHK(hipMemcpyAsync(dst, d_src, (size_t)(m * rows * row_bytes), hipMemcpyDeviceToHost, st));
-  else if (frame_pitch == row_pitch * rows)
-    HIPCHK(hipMemcpy2DAsync(dst, (size_t)row_pitch, d_src, (size_t)row_bytes, (size_t)row_bytes, (size_t)(m * rows), hipMemcpyDeviceToHost, st));
-  else
-    for (int64_t i = 0; i < m; ++i)
-      HIPCHK(hipMemcpy2DAsync(dst + i * frame_pitch, (size_t)row_pitch, d_src + i * rows * row_bytes, (size_t)row_bytes, (size_t)row_bytes,
-                              (size_t)rows, hipMemcpyDeviceToHost, st));
-}
-
-// Arguments are checked by the caller (sba_api.hip).  Frames on the device are read, and an output on the device is written,
-// where they are.  Host frames go through the two staging buffers of frames_in_chunks; a host output through one packed device
-// buffer of a chunk, fetched row by row into the caller's pitches before the chunk is drained (the copy of the next chunk's
-// frames is already queued by then, so input and output copies run side by side).  A chunk is chunk_frames frames, by default
-// what fits DOT_STAGE_BYTES on the larger of the two sides when one of them is host memory.  Which chunk, workgroup or buffer
-// a frame passes through does not enter its arithmetic: any chunk_frames gives the same bytes.
+// Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (frames_per_chunk
+// on the larger of the two sides when one of them is host memory, frames_in_chunks, FrameOutput).  Which chunk, workgroup or
+// buffer a frame passes through does not enter its arithmetic: any chunk_frames gives the same bytes.
 inline int undistort_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                           int64_t row_pitch, int64_t frame_pitch, const sba_lens& L, const double* new_k, int32_t out_height,
                           int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& o, uint8_t* out,
@@ -258,26 +242,18 @@ inline int undistort_call(int device, const uint8_t* frames, int64_t n_frames, i
   if (n_frames == 0 || !out) return SBA_OK;
 
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
-  const int64_t out_row = (int64_t)out_width * channels, out_tight = out_row * out_height;
-  int64_t chunk = DOT_MAX_CHUNK;
-  if (o.chunk_frames > 0) chunk = o.chunk_frames;
-  else if (!in_dev || !out_dev) chunk = std::max<int64_t>(1, DOT_STAGE_BYTES / std::max<int64_t>({1, (int64_t)width * channels * height, out_tight}));
-  chunk = std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames);
-
-  DevBuf<uint8_t> d_out;
-  if (!out_dev) d_out.alloc((size_t)(chunk * out_tight));
+  const int64_t out_row = (int64_t)out_width * channels;
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames,
+                                         in_dev && out_dev ? 0 : std::max((int64_t)width * channels * height, out_row * out_height));
+  FrameOutput O(out, out_row_pitch, out_frame_pitch, out_row, out_height, out_dev, chunk);
   frames_in_chunks(
       P.src, channels, n_frames, in_dev, chunk,
       [&](const FrameView& V, int64_t lo, int64_t m, hipStream_t st) {
         P.src = V;
-        if (out_dev) { P.out = out + lo * out_frame_pitch; P.out_row_pitch = out_row_pitch; P.out_frame_pitch = out_frame_pitch; }
-        else { P.out = d_out.p; P.out_row_pitch = out_row; P.out_frame_pitch = out_tight; }
+        O.target(lo, P.out, P.out_row_pitch, P.out_frame_pitch);
         ud_launch(P, channels, m, st);
       },
-      [&](int64_t lo, int64_t m, hipStream_t st) {
-        if (!out_dev) ud_fetch(out + lo * out_frame_pitch, out_row_pitch, out_frame_pitch, d_out.p, out_row, out_height, m, st);
-      },
-      [](int64_t, int64_t) {});
+      [&](int64_t lo, int64_t m, hipStream_t st) { O.fetch(lo, m, st); });
   return SBA_OK;
 }
 

@@ -183,6 +183,19 @@ def test_any_chunking_and_any_split_give_the_same_bits(torch, side):
         assert_same(accumulate(torch, src, threshold=100, chunk_frames=chunk), want, what=f"chunk_frames={chunk}")
         got = _native.background_suppress(src, level=level, chunk_frames=chunk)
         assert np.array_equal(got if side == "host" else got.cpu().numpy(), clean), f"suppress chunk_frames={chunk}"
+    # each class of layout a pitched copy tells apart -- packed, padded rows, a gap between packed frames, both -- on the frames
+    # and on the output, in four chunks, the last one short: both staging buffers are used twice, the padding stays
+    for row_slack, frame_slack in ((0, 0), (3, 0), (0, 7), (3, 7)):
+        buf, view, strides = padded(f, 1, row_slack, frame_slack)
+        obuf, oview, ostrides = padded(np.full(clean.shape + (1,), 0x5A, np.uint8), 3, row_slack and row_slack + 2, frame_slack and frame_slack + 4, fill=0x5A)
+        expect = obuf.copy()
+        np.lib.stride_tricks.as_strided(expect[3:], shape=clean.shape, strides=ostrides[:3])[...] = clean
+        src, out = view, oview[..., 0]
+        if side == "device":
+            (_t, src), (dobuf, out) = on_device(torch, buf, f.shape, strides, 1), on_device(torch, obuf, clean.shape, ostrides[:3], 3)
+        assert_same(accumulate(torch, src, threshold=100, chunk_frames=2), want, what=f"slack {row_slack}, {frame_slack}")
+        assert _native.background_suppress(src, level=level, out=out, chunk_frames=2) is out
+        assert np.array_equal(obuf if side == "host" else dobuf.cpu().numpy(), expect), f"suppress, slack {row_slack}, {frame_slack}: bytes or padding"
     # 0-2 then 3-6, and the other way round
     for first, second in ((slice(0, 3), slice(3, 7)), (slice(3, 7), slice(0, 3))):
         part = accumulate(torch, src[first], threshold=100)

@@ -257,7 +257,13 @@ def test_chunking_and_repeatability(torch):
             got = fd.find_laser_blobs(src, max_blobs=16, chunk_frames=chunk, want_mask=True, want_labels=True)
             assert blob_diff(got, want) is None, (blob_diff(got, want), chunk)
             runs.append(got)
-    again = fd.find_laser_blobs(dev, max_blobs=16, want_mask=True, want_labels=True)
+    # host frames in each class of layout a pitched copy tells apart -- packed, padded rows, a gap between packed frames, both --
+    # in four chunks, the last one short: both staging buffers are used again; the padding is bright
+    for row_slack, frame_slack in ((0, 0), (5, 0), (0, 13), (5, 13)):
+        _buf, view, _fp = pitched(frames, 70 * 3 + row_slack, frame_slack)
+        got = fd.find_laser_blobs(view, max_blobs=16, chunk_frames=2, want_mask=True, want_labels=True)
+        assert blob_diff(got, want) is None, (blob_diff(got, want), row_slack, frame_slack)
+    again =fd.find_laser_blobs(dev, max_blobs=16, want_mask=True, want_labels=True)
     for got in runs:
         assert again.blobs.tobytes() == got.blobs.tobytes() and again.centroid.tobytes() == got.centroid.tobytes()
         assert again.labels.tobytes() == got.labels.tobytes() and again.status.tobytes() == got.status.tobytes()

@@ -265,6 +265,11 @@ def test_any_chunking_gives_the_same_bytes(torch, device):
         for chunk in (1, 2, 3, n - 1, n, n + 1):
             check(torch, fmt, planes, out_format, want, slack=(5, 3, 13), bases=(1, 5, 15), out_slack=(7, 9), out_base=5, device=device,
                   chunk_frames=chunk)
+        # the other classes of layout a pitched copy tells apart -- packed, padded rows without a gap, a gap between packed
+        # frames -- on every plane and on the output, in three chunks, the last one short
+        for slack, out_slack in (((0, 0, 0), (0, 0)), ((5, 3, 0), (7, 0)), ((0, 0, 13), (0, 9))):
+            check(torch, fmt, planes, out_format, want, slack=slack, bases=(1, 5, 15), out_slack=out_slack, out_base=5, device=device,
+                  chunk_frames=2)
     # host planes into a device output and device planes into a host output, in chunks
     parts = source("nv12", planes)
     host, dev = tuple(p[1] for p in parts), to_device(torch, parts)[1]

@@ -226,6 +226,11 @@ def test_chunking_and_repeatability(torch):
     assert same_dots(one, want)
     for chunk in (2, 1, 4, 0):
         assert same_dots(fd.find_laser_dots(frames, max_extent=40, chunk_frames=chunk), want), chunk
+    # host frames in each class of layout a pitched copy tells apart -- packed, padded rows, a gap between packed frames, both --
+    # in five chunks, the last one short: both staging buffers are used again; the padding is bright
+    for row_slack, frame_slack in ((0, 0), (5, 0), (0, 13), (5, 13)):
+        _buf, view, _fp = pitched(frames, 45 * 3 + row_slack, frame_slack)
+        assert same_dots(fd.find_laser_dots(view, max_extent=40, chunk_frames=2), want), (row_slack, frame_slack)
     dev = torch.from_numpy(frames).cuda()
     assert same_dots(fd.find_laser_dots(dev, max_extent=40), want)
     again = fd.find_laser_dots(dev, max_extent=40)

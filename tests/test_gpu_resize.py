@@ -202,6 +202,18 @@ def test_memory_sides_and_chunks(C, fx, fy, gray, torch):
                 got = _native.resize_frames(src, fx, fy, gray_w=gray_weights(gray), out_on_device=out_dev, chunk_frames=chunk)
                 assert _native._is_tensor(got) == out_dev
                 assert np.array_equal(got.cpu().numpy() if out_dev else got, want), (src_dev, out_dev, chunk)
+    # host frames into a host output in each class of layout a pitched copy tells apart -- packed, padded rows, a gap between
+    # packed frames, both -- in three chunks, the last one short: both staging buffers are used twice, the padding stays
+    oshape = want.shape if want.ndim == 4 else want.shape + (1,)
+    for row_slack, frame_slack in ((0, 0), (7, 0), (0, 29), (7, 29)):
+        sbuf = aligned_bytes(view_in(None, f.shape, row_slack, frame_slack, 3)[1], 0xFF)
+        obuf = aligned_bytes(view_in(None, oshape, row_slack and row_slack - 2, frame_slack and frame_slack + 2, 5)[1], SENTINEL)
+        view_in(sbuf, f.shape, row_slack, frame_slack, 3)[0][...] = f
+        expect = obuf.copy()
+        view_in(expect, oshape, row_slack and row_slack - 2, frame_slack and frame_slack + 2, 5)[0][...] = want.reshape(oshape)
+        dst = view_in(obuf, oshape, row_slack and row_slack - 2, frame_slack and frame_slack + 2, 5)[0]
+        imaging.resize_frames(view_in(sbuf, f.shape, row_slack, frame_slack, 3)[0], (fx, fy), gray=gray_arg(gray), out=dst, chunk_frames=2)
+        assert np.array_equal(obuf, expect), (row_slack, frame_slack)
     assert isinstance(imaging.resize_frames(f, (fx, fy)), np.ndarray) and _native._is_tensor(imaging.resize_frames(fd, (fx, fy)))
     host_out = np.empty(want.shape, np.uint8)
     assert imaging.resize_frames(fd, (fx, fy), gray=gray_arg(gray), out=host_out) is host_out and np.array_equal(host_out, want)

@@ -183,6 +183,14 @@ def test_any_chunk_size_gives_the_same_bits(torch, C):
     sbuf, sview, _ = padded(frames.shape, 5, 13, 3, frames)
     assert np.array_equal(imaging.undistort_frames(sview, Lens(*lens9), nk, chunk_frames=2), want)
     assert np.array_equal(imaging.undistort_frames(frames[3:4], Lens(*lens9), nk), want[3:4])
+    # host frames into a host output in each class of layout a pitched copy tells apart -- packed, padded rows, a gap between
+    # packed frames, both -- in three chunks, the last one short: both staging buffers are used twice, the padding stays
+    for row_slack, frame_slack in ((0, 0), (5, 0), (0, 13), (5, 13)):
+        sbuf, sview, _ = padded(frames.shape, row_slack, frame_slack, 3, frames)
+        obuf, oview, _ = padded(want.shape, row_slack and row_slack + 2, frame_slack and frame_slack - 4, 5)
+        expect = padded(want.shape, row_slack and row_slack + 2, frame_slack and frame_slack - 4, 5, want)[0]
+        assert imaging.undistort_frames(sview, Lens(*lens9), nk, out=oview, chunk_frames=2) is oview
+        assert np.array_equal(obuf, expect), (row_slack, frame_slack)
 
 
 # ----------------------------------------------------------------------------- 4. edge cases
