@@ -1,0 +1,318 @@
+"""EXACT reference of the camera model and of the sums the LM step is made of -- test infrastructure, NOT product code.
+
+Written from the DEFINITION of the model, in mpmath at a fixed precision: Rodrigues through sin / cos of theta (identity at
+theta = 0), pinhole divide, two radial terms, OpenCV's tangential term for the 13-parameter rows, one focal length, principal
+point; residual = w * (project - uv).  The derivatives are central differences IN MPMATH with a step far below float64
+resolution (default: 80 digits, h = 1e-25; truncation ~ h^2 = 1e-50 relative, rounding ~ 1e-80 / h = 1e-55), so none of
+the a / b / a2 / b2 series and none of the closed-form derivative formulas of sba_model.hpp or oracle/lm_schur_model.py is
+in here: an error shared by those two cannot agree with this file.  Inputs are taken as the exact float64 values they
+are; every returned number is rounded to float64 once.
+
+What it pins (tests/test_exact_model_host.py pins this file first; tests/test_gpu_exact_model.py then pins the device):
+  exact_blocks   r (M,2), Jc (M,2,NCP), Jp (M,2,3)
+  robust_rows    the header's IRLS rule: rows and residual components scaled by sqrt(rho'(z)), z = (r / f_scale)^2
+  normal_sums    diagU, g_c, g_p, V, cost, each with the sum of the magnitudes of its terms
+  wt_dc          W_p^T dc = sum over the point's observations of Jp^T (Jc dc), with its term magnitudes
+  point_step     (V_p + lam diag D_p) dp = -(g_p + W_p^T dc), fixed points exactly zero
+About 1 ms per observation (the seven rotations a camera needs are built once per camera).
+"""
+from __future__ import annotations
+
+import mpmath as mp
+import numpy as np
+
+DPS = 80            # decimal digits of every mpmath evaluation
+H_DIGITS = 25       # central-difference step h = 10^-H_DIGITS
+ZERO_DIGITS = 30    # a difference quotient below 10^-ZERO_DIGITS of the pixel value is an exact zero of the derivative
+SUM_DPS = 50        # products of two float64 values (106 bits) and their sums are exact at this precision
+
+
+def _mpf(v):
+    return v if isinstance(v, mp.mpf) else mp.mpf(float(v))
+
+
+# ----------------------------------------------------------------------------- the model, from its definition
+def rotation(rho):
+    """(cos t, sin t, unit axis) of the rotation vector rho, or None for rho = 0 (the identity)."""
+    th2 = rho[0] * rho[0] + rho[1] * rho[1] + rho[2] * rho[2]
+    if th2 == 0:
+        return None
+    th = mp.sqrt(th2)
+    return mp.cos(th), mp.sin(th), [r / th for r in rho]
+
+
+def rotate(rot, X):
+    """Rodrigues: cos t X + sin t (k x X) + (1 - cos t) (k . X) k."""
+    if rot is None:
+        return list(X)
+    c, s, k = rot
+    kx = [k[1] * X[2] - k[2] * X[1], k[2] * X[0] - k[0] * X[2], k[0] * X[1] - k[1] * X[0]]
+    kd = k[0] * X[0] + k[1] * X[1] + k[2] * X[2]
+    return [c * X[i] + s * kx[i] + (1 - c) * kd * k[i] for i in range(3)]
+
+
+def pixel(p, intr):
+    """Camera-frame point p -> pixel.  intr = [f, k1, k2, cx, cy] or [f, k1, k2, p1, p2, cx, cy]."""
+    f, k1, k2 = intr[0], intr[1], intr[2]
+    p1, p2 = (intr[3], intr[4]) if len(intr) == 7 else (0, 0)
+    cx, cy = intr[-2], intr[-1]
+    x, y = p[0] / p[2], p[1] / p[2]
+    n = x * x + y * y
+    d = 1 + k1 * n + k2 * n * n
+    xd = x * d + 2 * p1 * x * y + p2 * (n + 2 * x * x)
+    yd = y * d + p1 * (n + 2 * y * y) + 2 * p2 * x * y
+    return f * xd + cx, f * yd + cy
+
+
+def project(cam_row, X):
+    """One 11- or 13-parameter camera row and one world point -> (u, v), in mpmath at the CURRENT precision."""
+    cam = [_mpf(v) for v in cam_row]
+    X = [_mpf(v) for v in X]
+    if len(cam) not in (11, 13):
+        raise ValueError("camera rows have 11 or 13 parameters")
+    P = rotate(rotation(cam[0:3]), X)
+    return pixel([P[i] + cam[3 + i] for i in range(3)], cam[6:])
+
+
+def series_digits(dps=DPS, h_digits=H_DIGITS):
+    """Correct decimal digits of (1 - cos h) / h^2 at this precision and step (the rotation term that cancels hardest)."""
+    with mp.workdps(dps):
+        h = mp.mpf(10) ** -h_digits
+        got = (1 - mp.cos(h)) / (h * h)
+    with mp.workdps(4 * dps):
+        h = mp.mpf(10) ** -h_digits
+        ref = (1 - mp.cos(h)) / (h * h)
+        err = abs(got - ref) / ref
+        return float(-mp.log10(err)) if err != 0 else float(dps)
+
+
+def _indices(ci, pi):
+    return np.asarray(ci).reshape(-1).astype(np.int64), np.asarray(pi).reshape(-1).astype(np.int64)
+
+
+def _weights(w, M):
+    wv = np.ones(M) if w is None else np.asarray(w, dtype=np.float64).reshape(-1)
+    return np.full(M, wv[0]) if wv.size == 1 else wv
+
+
+def exact_residual(cams, pts, uv, ci, pi, w=None, dps=DPS):
+    """r (M,2) = w (project - uv) alone."""
+    ci, pi = _indices(ci, pi)
+    wv = _weights(w, ci.size)
+    r = np.zeros((ci.size, 2))
+    with mp.workdps(dps):
+        rots = {}
+        for m in range(ci.size):
+            c = int(ci[m])
+            if c not in rots:
+                cam = [_mpf(v) for v in cams[c]]
+                rots[c] = (cam, rotation(cam[0:3]))
+            cam, rot = rots[c]
+            P = rotate(rot, [_mpf(v) for v in pts[pi[m]]])
+            u, v = pixel([P[i] + cam[3 + i] for i in range(3)], cam[6:])
+            wm = _mpf(wv[m])
+            r[m] = float(wm * (u - _mpf(uv[m, 0]))), float(wm * (v - _mpf(uv[m, 1])))
+    return r
+
+
+def camera_points(cams, pts, ci, pi, dps=DPS):
+    """(M,3) camera-frame points R X + t."""
+    ci, pi = _indices(ci, pi)
+    out = np.zeros((ci.size, 3))
+    with mp.workdps(dps):
+        for m in range(ci.size):
+            cam = [_mpf(v) for v in cams[ci[m]]]
+            P = rotate(rotation(cam[0:3]), [_mpf(v) for v in pts[pi[m]]])
+            out[m] = [float(P[i] + cam[3 + i]) for i in range(3)]
+    return out
+
+
+def exact_blocks(cams, pts, uv, ci, pi, w=None, dps=DPS, h_digits=H_DIGITS):
+    """r (M,2), Jc (M,2,NCP), Jp (M,2,3) of w (project - uv): central differences in mpmath, rounded once to float64."""
+    cams = np.asarray(cams, dtype=np.float64)
+    pts = np.asarray(pts, dtype=np.float64)
+    ci, pi = _indices(ci, pi)
+    M, ncp = ci.size, cams.shape[1]
+    wv = _weights(w, M)
+    r, Jc, Jp = np.zeros((M, 2)), np.zeros((M, 2, ncp)), np.zeros((M, 2, 3))
+    with mp.workdps(dps):
+        h = mp.mpf(10) ** -h_digits
+        inv2h = 1 / (2 * h)
+        zero_below = mp.mpf(10) ** -ZERO_DIGITS
+        percam = {}
+        for m in range(M):
+            c = int(ci[m])
+            if c not in percam:         # the rotation and its six displaced neighbours depend on the camera alone
+                cam = [_mpf(v) for v in cams[c]]
+                rots = []
+                for k in range(3):
+                    ra, rb = list(cam[0:3]), list(cam[0:3])
+                    ra[k] += h
+                    rb[k] -= h
+                    rots.append((rotation(ra), rotation(rb)))
+                percam[c] = (cam, rotation(cam[0:3]), rots)
+            cam, rot0, rots = percam[c]
+            t, intr = cam[3:6], cam[6:]
+            X = [_mpf(v) for v in pts[pi[m]]]
+            wm = _mpf(wv[m])
+            P = rotate(rot0, X)
+            p = [P[i] + t[i] for i in range(3)]
+            u, v = pixel(p, intr)
+            r[m] = float(wm * (u - _mpf(uv[m, 0]))), float(wm * (v - _mpf(uv[m, 1])))
+            for k in range(ncp + 3):
+                if k < 3:
+                    Pa, Pb = rotate(rots[k][0], X), rotate(rots[k][1], X)
+                    a = pixel([Pa[i] + t[i] for i in range(3)], intr)
+                    b = pixel([Pb[i] + t[i] for i in range(3)], intr)
+                elif k < 6:             # p = R X + t: a step in t is the same step in p
+                    pa, pb = list(p), list(p)
+                    pa[k - 3] += h
+                    pb[k - 3] -= h
+                    a, b = pixel(pa, intr), pixel(pb, intr)
+                elif k < ncp:
+                    ia, ib = list(intr), list(intr)
+                    ia[k - 6] += h
+                    ib[k - 6] -= h
+                    a, b = pixel(p, ia), pixel(p, ib)
+                else:
+                    Xa, Xb = list(X), list(X)
+                    Xa[k - ncp] += h
+                    Xb[k - ncp] -= h
+                    Pa, Pb = rotate(rot0, Xa), rotate(rot0, Xb)
+                    a = pixel([Pa[i] + t[i] for i in range(3)], intr)
+                    b = pixel([Pb[i] + t[i] for i in range(3)], intr)
+                du, dv = wm * (a[0] - b[0]) * inv2h, wm * (a[1] - b[1]) * inv2h
+                # an exact zero of the derivative (a point on the optical axis) comes out as the difference's truncation, ~h^2 of
+                # the third derivative: anything below 10^-ZERO_DIGITS of the pixel's own size per unit step is that zero
+                du = 0.0 if abs(du) < zero_below * abs(u) else float(du)
+                dv = 0.0 if abs(dv) < zero_below * abs(v) else float(dv)
+                if k < ncp:
+                    Jc[m, 0, k], Jc[m, 1, k] = du, dv
+                else:
+                    Jp[m, 0, k - ncp], Jp[m, 1, k - ncp] = du, dv
+    return r, Jc, Jp
+
+
+# ----------------------------------------------------------------------------- robust loss (scipy's rho, the header's IRLS rows)
+def rho_functions(z, loss):
+    """(rho(z), rho'(z)) of scipy.optimize.least_squares' losses, from their definitions, in mpmath."""
+    z = _mpf(z)
+    if loss == "linear":
+        return z, mp.mpf(1)
+    if loss == "huber":
+        return (z, mp.mpf(1)) if z <= 1 else (2 * mp.sqrt(z) - 1, 1 / mp.sqrt(z))
+    if loss == "soft_l1":
+        return 2 * (mp.sqrt(1 + z) - 1), 1 / mp.sqrt(1 + z)
+    if loss == "cauchy":
+        return mp.log(1 + z), 1 / (1 + z)
+    raise ValueError("loss must be 'linear', 'huber', 'soft_l1' or 'cauchy'")
+
+
+def robust_rows(r, Jc, Jp, loss, f_scale):
+    """Rows and residual components scaled by sqrt(rho'((r / f_scale)^2)).
+    Returns r_s, Jc_s, Jp_s, cost_terms (M,2) with cost = 0.5 sum cost_terms (f_scale^2 rho(z); r^2 for the linear loss),
+    and the scale (M,2) itself."""
+    r = np.asarray(r, dtype=np.float64)
+    if loss in (None, "linear") or not f_scale > 0:
+        with mp.workdps(SUM_DPS):
+            terms = np.array([[float(_mpf(v) ** 2) for v in row] for row in r])
+        return r.copy(), Jc.copy(), Jp.copy(), terms, np.ones_like(r)
+    rs, Jcs, Jps = r.copy(), Jc.copy(), Jp.copy()
+    terms, scale = np.zeros_like(r), np.ones_like(r)
+    with mp.workdps(SUM_DPS):
+        delta = _mpf(f_scale)
+        for m in range(r.shape[0]):
+            for k in range(2):
+                rho, drho = rho_functions((_mpf(r[m, k]) / delta) ** 2, loss)
+                s = mp.sqrt(drho)
+                terms[m, k] = float(delta * delta * rho)
+                scale[m, k] = float(s)
+                if s != 1:
+                    rs[m, k] = float(s * _mpf(r[m, k]))
+                    Jcs[m, k] = [float(s * _mpf(v)) for v in Jc[m, k]]
+                    Jps[m, k] = [float(s * _mpf(v)) for v in Jp[m, k]]
+    return rs, Jcs, Jps, terms, scale
+
+
+# ----------------------------------------------------------------------------- sums of products
+def _dot(a, b):
+    return float(mp.fdot([_mpf(x) for x in a], [_mpf(y) for y in b]))
+
+
+def normal_sums(r, Jc, Jp, ci, pi, n_cams, n_pts, cost_terms=None, r_slack=None):
+    """diagU (C,NCP), gc (C,NCP), gp (N,3), V (N,3,3) and cost of the given blocks, summed exactly and rounded once, with the
+    magnitudes of their terms: gc_mag / gp_mag = sum |J_ij| (|r_i| + r_slack_i), V_mag = sum |J_ij J_ik| (diagU and diag V are
+    their own), cost_mag = 0.5 sum |r_i| (|r_i| + r_slack_i) ... for the robust losses 0.5 sum of the cost terms."""
+    ci, pi = _indices(ci, pi)
+    M, ncp = ci.size, Jc.shape[2]
+    slack = np.zeros((M, 2)) if r_slack is None else np.broadcast_to(np.asarray(r_slack, dtype=np.float64).reshape(M, -1), (M, 2))
+    ra = np.abs(r) + slack
+    out = dict(diagU=np.zeros((n_cams, ncp)), gc=np.zeros((n_cams, ncp)), gc_mag=np.zeros((n_cams, ncp)),
+               gp=np.zeros((n_pts, 3)), gp_mag=np.zeros((n_pts, 3)), V=np.zeros((n_pts, 3, 3)), V_mag=np.zeros((n_pts, 3, 3)))
+    with mp.workdps(SUM_DPS):
+        for c in range(n_cams):
+            sel = np.nonzero(ci == c)[0]
+            rr, aa = r[sel].ravel(), ra[sel].ravel()
+            for k in range(ncp):
+                col = Jc[sel, :, k].ravel()
+                out["diagU"][c, k] = _dot(col, col)
+                out["gc"][c, k] = _dot(col, rr)
+                out["gc_mag"][c, k] = _dot(np.abs(col), aa)
+        for p in range(n_pts):
+            sel = np.nonzero(pi == p)[0]
+            rr, aa = r[sel].ravel(), ra[sel].ravel()
+            for k in range(3):
+                col = Jp[sel, :, k].ravel()
+                out["gp"][p, k] = _dot(col, rr)
+                out["gp_mag"][p, k] = _dot(np.abs(col), aa)
+                for j in range(k, 3):
+                    cj = Jp[sel, :, j].ravel()
+                    out["V"][p, k, j] = out["V"][p, j, k] = _dot(col, cj)
+                    out["V_mag"][p, k, j] = out["V_mag"][p, j, k] = _dot(np.abs(col), np.abs(cj))
+        if cost_terms is None:
+            out["cost"] = 0.5 * _dot(r.ravel(), r.ravel())
+        else:
+            out["cost"] = 0.5 * float(mp.fsum([_mpf(v) for v in np.asarray(cost_terms).ravel()]))
+        out["cost_mag"] = 0.5 * _dot(np.abs(r).ravel(), ra.ravel())
+    return out
+
+
+def wt_dc(Jc, Jp, ci, pi, dc, n_pts):
+    """t (N,3) = sum over each point's observations of Jp^T (Jc dc_cam), and t_mag = sum |Jp|^T (|Jc| |dc_cam|)."""
+    ci, pi = _indices(ci, pi)
+    dc = np.asarray(dc, dtype=np.float64).reshape(-1, Jc.shape[2])
+    t, t_mag = np.zeros((n_pts, 3)), np.zeros((n_pts, 3))
+    with mp.workdps(SUM_DPS):
+        s = [[mp.fdot([_mpf(x) for x in Jc[m, k]], [_mpf(y) for y in dc[ci[m]]]) for k in range(2)] for m in range(ci.size)]
+        sa = [[mp.fdot([_mpf(abs(x)) for x in Jc[m, k]], [_mpf(abs(y)) for y in dc[ci[m]]]) for k in range(2)] for m in range(ci.size)]
+        for p in range(n_pts):
+            sel = np.nonzero(pi == p)[0]
+            for j in range(3):
+                t[p, j] = float(mp.fsum([_mpf(Jp[m, k, j]) * s[m][k] for m in sel for k in range(2)]))
+                t_mag[p, j] = float(mp.fsum([_mpf(abs(Jp[m, k, j])) * sa[m][k] for m in sel for k in range(2)]))
+    return t, t_mag
+
+
+def damping_diagonal(V):
+    """D (N,3) of the FIRST linearisation: diag V with zeros replaced by 1 (ModelEngine.linearize)."""
+    d = np.einsum("nii->ni", V)
+    return np.where(d > 0, d, 1.0)
+
+
+def point_step(V, gp, wtdc, lam, D, fixed=None):
+    """dp (N,3): (V_p + lam diag D_p) dp = -(g_p + W_p^T dc), solved in mpmath; fixed points get exactly zero."""
+    N = V.shape[0]
+    dp = np.zeros((N, 3))
+    with mp.workdps(SUM_DPS):
+        lam = _mpf(lam)
+        for p in range(N):
+            if fixed is not None and fixed[p]:
+                continue
+            A = mp.matrix(3, 3)
+            for i in range(3):
+                for j in range(3):
+                    A[i, j] = _mpf(V[p, i, j]) + (lam * _mpf(D[p, i]) if i == j else 0)
+            b = mp.matrix([-(_mpf(gp[p, i]) + _mpf(wtdc[p, i])) for i in range(3)])
+            x = mp.lu_solve(A, b)
+            dp[p] = [float(x[i]) for i in range(3)]
+    return dp

@@ -7,10 +7,13 @@ replacement algorithm in plain numpy so the tests can check the HIP kernels'
 intermediate quantities (Jacobian blocks, U/V/W, reduced camera system, step)
 one by one, and so the multi-rank driver can be exercised on CPU with gloo.
 
-It is validated two ways in tests/: (1) its analytic Jacobian against the
+It is validated three ways in tests/: (1) its analytic Jacobian against the
 reference's scipy 3-point finite-difference Jacobian fixture (f3_jacobian.npz),
 (2) its converged cost/RMS against the reference's converged solves
-(f4_solves.npz).  Nothing under lasercalib_amd/ imports it.
+(f4_solves.npz), (3) its blocks, per column kind, and its damped point step
+against oracle/exact_model.py -- the model evaluated from its definition in
+mpmath, with none of the series or closed-form derivatives used here
+(tests/test_exact_model_host.py).  Nothing under lasercalib_amd/ imports it.
 """
 from __future__ import annotations
 
@@ -42,10 +45,13 @@ def rodrigues_coeffs(theta2):
 
 
 def residual_jacobian(cams, pts, uv, ci, pi, w):
-    """Analytic residual (M,2) and Jacobian blocks Jc (M,2,11), Jp (M,2,3) of w*(project-uv).
+    """Analytic residual (M,2) and Jacobian blocks Jc (M,2,NCP), Jp (M,2,3) of w*(project-uv).
 
-    Model: pySBA.py:61-89 (Rodrigues, pinhole, two radial terms, one focal length).
+    Model: pySBA.py:61-89 (Rodrigues, pinhole, two radial terms, one focal length); 13-column camera rows add OpenCV's
+    tangential term (p1, p2 before cx, cy: oracle/sba_oracle_tangential.py).
     """
+    ncp = cams.shape[1]
+    tang = ncp == 13
     cam = cams[ci]
     X = pts[pi]
     rho = cam[:, 0:3]
@@ -62,8 +68,16 @@ def residual_jacobian(cams, pts, uv, ci, pi, w):
     n = x * x + y * y
     d = 1 + k1 * n + k2 * n * n
     dn = k1 + 2 * k2 * n
-    u = f * d * x + cam[:, 9]
-    v = f * d * y + cam[:, 10]
+    xd, yd = d * x, d * y
+    if tang:
+        tp1, tp2 = cam[:, 9], cam[:, 10]
+        xd = xd + 2 * tp1 * x * y + tp2 * (n + 2 * x * x)
+        yd = yd + tp1 * (n + 2 * y * y) + 2 * tp2 * x * y
+        u = f * xd + cam[:, 11]
+        v = f * yd + cam[:, 12]
+    else:                               # the reference's model, operation order unchanged (the LM trajectories of the tests depend on it)
+        u = f * d * x + cam[:, 9]
+        v = f * d * y + cam[:, 10]
     M = ci.shape[0]
     wv = np.asarray(w, dtype=np.float64).reshape(-1)
     if wv.size == 1:
@@ -72,9 +86,12 @@ def residual_jacobian(cams, pts, uv, ci, pi, w):
     res = res * wv[:, None]
 
     # A = d(u,v)/dp  (2x3)
-    ux = f * (d + 2 * x * x * dn)
-    uy = f * (2 * x * y * dn)
-    vy = f * (d + 2 * y * y * dn)
+    gxx, gxy, gyy = d + 2 * x * x * dn, 2 * x * y * dn, d + 2 * y * y * dn
+    if tang:
+        gxx = gxx + 2 * tp1 * y + 6 * tp2 * x
+        gxy = gxy + 2 * (tp1 * x + tp2 * y)
+        gyy = gyy + 6 * tp1 * y + 2 * tp2 * x
+    ux, uy, vy = f * gxx, f * gxy, f * gyy
     A = np.zeros((M, 2, 3))
     A[:, 0, 0] = ux * iz
     A[:, 0, 1] = uy * iz
@@ -104,14 +121,17 @@ def residual_jacobian(cams, pts, uv, ci, pi, w):
             + b[:, None, None] * (rho[:, :, None] * X[:, None, :])
             + (b * rdX)[:, None, None] * eye)
 
-    Jc = np.zeros((M, 2, NCP))
+    Jc = np.zeros((M, 2, ncp))
     Jc[:, :, 0:3] = A @ dPdr
     Jc[:, :, 3:6] = A
-    Jc[:, 0, 6], Jc[:, 1, 6] = d * x, d * y
+    Jc[:, 0, 6], Jc[:, 1, 6] = xd, yd
     Jc[:, 0, 7], Jc[:, 1, 7] = f * x * n, f * y * n
     Jc[:, 0, 8], Jc[:, 1, 8] = f * x * n * n, f * y * n * n
-    Jc[:, 0, 9] = 1.0
-    Jc[:, 1, 10] = 1.0
+    if tang:
+        Jc[:, 0, 9], Jc[:, 1, 9] = f * 2 * x * y, f * (n + 2 * y * y)
+        Jc[:, 0, 10], Jc[:, 1, 10] = f * (n + 2 * x * x), f * 2 * x * y
+    Jc[:, 0, ncp - 2] = 1.0
+    Jc[:, 1, ncp - 1] = 1.0
     Jp = A @ R
     Jc *= wv[:, None, None]
     Jp *= wv[:, None, None]
@@ -121,20 +141,22 @@ def residual_jacobian(cams, pts, uv, ci, pi, w):
 def jacobian_csr(Jc, Jp, ci, pi, n_cams, n_pts):
     """Assemble blocks into the (2M, 11C+3N) CSR layout scipy uses (pySBA.py:110-116)."""
     from scipy.sparse import csr_matrix
-    M = ci.shape[0]
-    cols_c = (ci[:, None] * NCP + np.arange(NCP)[None, :])
-    cols_p = (n_cams * NCP + pi[:, None] * 3 + np.arange(3)[None, :])
+    M, ncp = ci.shape[0], Jc.shape[2]
+    nb = ncp + 3
+    cols_c = (ci[:, None] * ncp + np.arange(ncp)[None, :])
+    cols_p = (n_cams * ncp + pi[:, None] * 3 + np.arange(3)[None, :])
     cols = np.concatenate([cols_c, cols_p], axis=1)                  # (M,14)
-    cols = np.repeat(cols[:, None, :], 2, axis=1).reshape(2 * M, 14)
-    data = np.concatenate([Jc, Jp], axis=2).reshape(2 * M, 14)
-    indptr = np.arange(0, 2 * M * 14 + 1, 14)
-    J = csr_matrix((data.ravel(), cols.ravel(), indptr), shape=(2 * M, n_cams * NCP + n_pts * 3))
+    cols = np.repeat(cols[:, None, :], 2, axis=1).reshape(2 * M, nb)
+    data = np.concatenate([Jc, Jp], axis=2).reshape(2 * M, nb)
+    indptr = np.arange(0, 2 * M * nb + 1, nb)
+    J = csr_matrix((data.ravel(), cols.ravel(), indptr), shape=(2 * M, n_cams * ncp + n_pts * 3))
     J.sort_indices()
     return J
 
 
 def normal_blocks(res, Jc, Jp, ci, pi, n_cams, n_pts):
-    """U (C,11,11), gc (C,11), V (N,3,3), gp (N,3), W (M,11,3) -- blocks of J^T J and J^T r."""
+    """U (C,NCP,NCP), gc (C,NCP), V (N,3,3), gp (N,3), W (M,NCP,3) -- blocks of J^T J and J^T r."""
+    NCP = Jc.shape[2]
     U = np.zeros((n_cams, NCP, NCP))
     gc = np.zeros((n_cams, NCP))
     V = np.zeros((n_pts, 3, 3))
@@ -153,7 +175,7 @@ def reduced_system(U, gc, V, gp, W, ci, pi, lam, D2p):
     V' = V + lam*diag(D2p).  The camera damping lam*D2c is added by the caller AFTER the
     cross-rank sum (it needs the global diag(U)).
     """
-    C = U.shape[0]
+    C, NCP = U.shape[0], U.shape[1]
     n = C * NCP
     Vd = V + lam * (D2p[:, :, None] * np.eye(3)[None])
     Vinv = np.linalg.inv(Vd)
@@ -209,8 +231,10 @@ class ModelEngine:
         self.uv, self.ci, self.pi = uv, ci, pi_local
         self.w = np.ones(ci.shape[0]) if w is None else np.asarray(w, dtype=np.float64).reshape(-1)
         self.C, self.N = self.cams.shape[0], self.pts.shape[0]
-        self.n = self.C * NCP
+        self.ncp = self.cams.shape[1]                   # 11, or 13 with the tangential term
+        self.n = self.C * self.ncp
         if self.shared:     # pySBA.py:252-325: [f,k1,k2 | 6 extrinsics x C | 2 centre x C]
+            assert self.ncp == NCP, "shared intrinsics are modelled for the 11-parameter rows only"
             C = self.C
             self.ns = 3 + 8 * C
             self.T = np.zeros((self.n, self.ns))
@@ -300,9 +324,9 @@ class ModelEngine:
         self.dc = dc
         # back-substitution: dp = V'^-1 ( -gp - W^T dc )
         Wt_dc = np.zeros((self.N, 3))
-        np.add.at(Wt_dc, self.pi, np.einsum("mij,mi->mj", self.W, dc.reshape(self.C, NCP)[self.ci]))
+        np.add.at(Wt_dc, self.pi, np.einsum("mij,mi->mj", self.W, dc.reshape(self.C, self.ncp)[self.ci]))
         self.dp = np.einsum("nij,nj->ni", self.Vinv, -self.gp - Wt_dc)
-        self.cams_new = self.cams + dc.reshape(self.C, NCP)
+        self.cams_new = self.cams + dc.reshape(self.C, self.ncp)
         self.pts_new = self.pts + self.dp
         res_new, _, _ = residual_jacobian(self.cams_new, self.pts_new, self.uv, self.ci, self.pi, self.w)
         self.res_new = res_new
