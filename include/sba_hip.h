@@ -903,6 +903,67 @@ int sba_resize_frames(int device, const uint8_t* frames, int64_t n_frames, int32
                       int32_t fy /*1..16*/, int64_t out_row_pitch, int64_t out_frame_pitch,
                       const sba_resize_opts* opts /*NULL: all zero*/, uint8_t* out);
 
+/* ---------------------------------------------------------------- encoder frames: BGR or one plane to YUV 4:2:0
+ * The way back of sba_convert_frames.  Whoever stores or streams what the frame functions produce hands 8-bit YUV 4:2:0 to an
+ * encoder (libx264 and ffmpeg's rawvideo pipe take yuv420p / nv12, a hardware encoder NV12 surfaces in device memory).
+ * sba_frames_to_yuv converts a batch of interleaved frames into such planes on the device: 1.5 bytes per pixel leave it instead
+ * of 3, and no pass over the pixels is left to the host.  Stateless: no handle.
+ *
+ * The source is described as for sba_detect_dots and sba_resize_frames: 8-bit, channels 1, 3 or 4 interleaved, any base, any
+ * pitches that hold a row, host memory or with frames_on_device device memory read in place.  in_format (sba_pixel_format) says
+ * which byte of a pixel is which: BGR or RGB with channels = 3, BGRA or RGBA with channels = 4 (the fourth byte is ignored);
+ * with channels = 1 it is not looked at and R = G = B = the byte, by the same rule as every other pixel.
+ * The destination is described exactly as the SOURCE of sba_convert_frames: three plane pointers; luma sample (x, y) of frame f
+ * is y[f y_frame_pitch + y y_row_pitch + x]; the chroma planes have (height + 1) / 2 rows of (width + 1) / 2 samples (odd sizes
+ * are allowed) and share their pitches and c_step: sample (i, j) is u[f c_frame_pitch + j c_row_pitch + i c_step], v likewise.
+ *   NV12: u = uv, v = uv + 1, c_step = 2       NV21: u = vu + 1, v = vu, c_step = 2       I420 / YV12: three planes, c_step = 1
+ * With c_step = 2 and u, v not one byte apart only every second byte of each plane is written; the bytes in between stay
+ * untouched.  The planes are all host memory, or with out_on_device all device memory of `device`, written in place.  The
+ * padding between the samples' rows and frames is never written.  The samples of the three planes must not overlap.
+ *
+ * The rule -- this is the function's definition.  R, G, B are the bytes of a pixel; >> is the arithmetic shift (floor);
+ * clip255(s) = min(max(s, 0), 255):
+ *   Y = clip255((cry*R  + cgy*G  + cby*B  + 2^19 + (y_offset << 20)) >> 20)          at every pixel (x, y)
+ *   U = clip255((cru*R' + cgu*G' + cbu*B' + 2^19 + (128 << 20)) >> 20)               at every chroma sample (i, j)
+ *   V = clip255((crv*R' + cgv*G' + cbv*B' + 2^19 + (128 << 20)) >> 20)
+ * chroma = 0 (nearest): R', G', B' are the bytes of pixel (2i, 2j), the top-left one of the sample's block.  This is the
+ *   choice of OpenCV's cvtColor(COLOR_BGR2YUV_I420).
+ * chroma = 1 (average): with SR, SG, SB the sums of the bytes at the four positions (min(2i + a, width - 1),
+ *   min(2j + b, height - 1)), a, b in {0, 1} -- at an odd edge the existing pixel is repeated --,
+ *   U = clip255((cru*SR + cgu*SG + cbu*SB + 2^21 + (128 << 22)) >> 22), V likewise: ONE rounding, of the sum.  On a block of
+ *   four equal pixels both modes give the same bytes: 4 s + 2^21 + 128 2^22 = 4 (s + 2^19 + 128 2^20).
+ * The ten integers are those of *matrix; NULL is the table of OpenCV's cvtColor(COLOR_BGR2YUV_I420) (BT.601, limited range),
+ * {16, 269484, 528482, 102760, -155188, -305135, 460324, 460324, -385875, -74448}: every (R, G, B) goes to Y in 16..235 and
+ * U, V in 16..240 without a clip, and grey to U = V = 128.
+ * A matrix must have y_offset in 0..255 and, for each of its three rows (a, b, c), 255 (|a| + |b| + |c|) < 2^28.  Then every
+ * sum above fits 32 bits, which is what the kernel computes in: a luma sum is in magnitude below 2^28 + 2^19 + 255 2^20 < 2^31,
+ * a chroma sum of the average mode -- its sums of bytes reach 4 * 255 -- below 4 2^28 + 2^21 + 2^29 < 2^31, one of the nearest
+ * mode a quarter of that.  (A full-range luma row, whose coefficients sum to 2^20, lies just inside: 255 2^20 < 2^28.)
+ * Frames pass through the device in chunks (host frames through two staging buffers, every host plane through one more);
+ * device memory does not grow with n_frames, and any chunk_frames gives the same bytes.  n_frames = 0 returns SBA_OK and
+ * writes nothing.
+ * Errors, all checked before any device work (text in sba_last_error(NULL)), the planes left untouched: the frame errors of
+ * sba_detect_dots for the source; as sba_convert_frames for its source, SBA_ERR_INVALID for a NULL plane with n_frames > 0, a
+ * c_step that is not 1 or 2, y_row_pitch < width, c_row_pitch < c_step ((width + 1) / 2 - 1) + 1 and a frame pitch smaller
+ * than the plane's rows times its row pitch; SBA_ERR_INVALID for an unknown in_format or one whose bytes per pixel are not
+ * `channels` (channels 3 or 4), a chroma that is not 0 or 1 and a matrix outside the bound; SBA_ERR_UNSUPPORTED for width or
+ * height above 16384; SBA_ERR_NO_DEVICE as everywhere. */
+typedef struct { int32_t y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv; } sba_rgb_matrix;
+typedef enum { SBA_CHROMA_NEAREST = 0, SBA_CHROMA_AVERAGE = 1 } sba_chroma_mode;
+typedef struct {
+  int32_t frames_on_device;  /* as sba_dot_opts */
+  int32_t out_on_device;     /* 1: y, u and v are device pointers on `device` */
+  int32_t in_format;         /* sba_pixel_format: BGR, RGB, BGRA or RGBA        */
+  int32_t chroma;            /* sba_chroma_mode                                 */
+  int32_t chunk_frames;      /* frames per chunk at most; <= 0 = library default */
+  int32_t reserved[7];
+} sba_to_yuv_opts;
+int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width,
+                      int32_t channels /*1, 3 or 4*/, int64_t row_pitch, int64_t frame_pitch, uint8_t* y, uint8_t* u, uint8_t* v,
+                      int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch,
+                      int32_t c_step /*1 or 2*/, const sba_rgb_matrix* matrix /*NULL: OpenCV's BT.601 table*/,
+                      const sba_to_yuv_opts* opts /*NULL: all zero*/);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

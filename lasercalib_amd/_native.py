@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
     "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames", "sba_resize_frames",
+    "sba_frames_to_yuv",
 )
 
 
@@ -193,6 +194,29 @@ GRAY_SHIFT = 15                                                           # the 
 # the items (source bytes, or source pixels with gray) of a row that a wave takes in one step (csrc/sba_resize.hpp), for the
 # tests that straddle a segment
 RESIZE_ITEMS = 1024
+
+
+class RgbMatrix(C.Structure):                                             # sba_rgb_matrix
+    _fields_ = [(n, C.c_int32) for n in ("y_offset", "cry", "cgy", "cby", "cru", "cgu", "cbu", "crv", "cgv", "cbv")]
+
+
+class ToYuvOpts(C.Structure):                                             # sba_to_yuv_opts
+    _fields_ = [("frames_on_device", C.c_int32), ("out_on_device", C.c_int32), ("in_format", C.c_int32), ("chroma", C.c_int32),
+                ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+RGB_BT601 = (16, 269484, 528482, 102760, -155188, -305135, 460324, 460324, -385875, -74448)   # OpenCV's table: a NULL matrix
+CHROMA_MODES = {"nearest": 0, "average": 1}                               # sba_chroma_mode
+IN_FORMATS = {"bgr": 3, "rgb": 3, "bgra": 4, "rgba": 4, "gray": 1}        # what frames_to_yuv reads: the channels of each
+
+
+def rgb_matrix_in_bound(m):
+    """Whether the ten integers (y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv) are a matrix sba_frames_to_yuv accepts:
+    32-bit values, y_offset in 0..255 and 255 (|a| + |b| + |c|) < 2^28 for each of the three rows."""
+    vals = [int(v) for v in m]
+    if len(vals) != 10 or any(not -(1 << 31) <= v < (1 << 31) for v in vals[1:]) or not 0 <= vals[0] <= 255:
+        return False
+    return all(255 * sum(abs(c) for c in vals[i:i + 3]) < (1 << 28) for i in (1, 4, 7))
 
 
 def yuv_matrix_in_bound(m):
@@ -497,6 +521,9 @@ def load():
         "sba_convert_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                          C.c_int64, C.c_int64, C.c_int32, C.POINTER(YuvMatrix), C.c_int64, C.c_int64,
                                          C.POINTER(ConvertOpts), C.c_void_p]),
+        "sba_frames_to_yuv": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                        C.POINTER(RgbMatrix), C.POINTER(ToYuvOpts)]),
         "sba_resize_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_int64, C.c_int64, C.POINTER(ResizeOpts), C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
@@ -779,13 +806,14 @@ def detect_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=
 
 
 def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", border_value=0, out=None, want_flags=False,
-                     want_map=False, want_frames=True, chunk_frames=0, device=0):
+                     want_map=False, want_frames=True, chunk_frames=0, device=0, out_on_device=None):
     """sba_undistort_frames (include/sba_hip.h): ``frames`` as for ``detect_dots`` (numpy, or a torch tensor on ``device`` read in
     place) resampled through the lens ``lens9`` = (fx, fy, cx, cy, k1, k2, p1, p2, k3) into the pinhole image of ``new_k`` = (fxn,
     fyn, cxn, cyn) of ``out_size`` = (height, width).  Returns (out, flags, map): ``out`` is a numpy array for numpy frames and a
     device tensor for tensor frames -- allocated here, or the caller's ``out``, which may be a strided view with contiguous
     pixels --, None with ``want_frames=False`` (then no frame is read); ``flags`` (height, width) uint8 and ``map`` (height, width, 2) int32 are numpy
-    or None.  ``lasercalib_amd.imaging`` is the public face of this call."""
+    or None.  ``out_on_device`` True / False puts the result on that side whatever side the frames are on (an ``out`` may then be of
+    either kind); None keeps it with the frames.  ``lasercalib_amd.imaging`` is the public face of this call."""
     lib = load()
     if interpolation not in UNDIST_INTERPOLATION:
         raise ValueError(f"interpolation must be one of {sorted(UNDIST_INTERPOLATION)}, not {interpolation!r}")
@@ -798,7 +826,7 @@ def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", bor
     lens = LensStruct(*(float(v) for v in lens9))
     nk = np.ascontiguousarray([float(v) for v in new_k], dtype=np.float64)
     opts = UndistortOpts()
-    opts.frames_on_device = opts.out_on_device = 1 if tensor else 0
+    opts.frames_on_device = 1 if tensor else 0
     opts.interpolation, opts.border_value, opts.chunk_frames = UNDIST_INTERPOLATION[interpolation], int(border_value), int(chunk_frames)
     shapes = ((B, Ho, Wo, Cn), (B, Ho, Wo) if Cn == 1 else None)            # a one-channel result may drop the last axis
     osr, osf, optr = Wo * Cn, Ho * Wo * Cn, None
@@ -808,10 +836,13 @@ def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", bor
         if not (want_flags or want_map):
             raise ValueError("nothing asked for: neither frames nor flags nor map")
     else:
-        out, _t, optr, osr, osf = _frames_out(out, shapes if len(frames.shape) == 4 else shapes[::-1], tensor, device, like_frames=tensor)
+        out, out_tensor, optr, osr, osf = _frames_out(out, shapes if len(frames.shape) == 4 else shapes[::-1],
+                                                      tensor if out_on_device is None else bool(out_on_device), device,
+                                                      like_frames=tensor if out_on_device is None else None)
+        opts.out_on_device = 1 if out_tensor else 0
     flags = np.zeros((Ho, Wo), np.uint8) if want_flags else None
     qmap = np.zeros((Ho, Wo, 2), np.int32) if want_map else None
-    _check(lib.sba_undistort_frames(device, C.c_void_p(_synced(device, frames)), B, H, W, Cn, sr, sf, C.byref(lens), _dptr(nk), Ho, Wo, osr, osf,
+    _check(lib.sba_undistort_frames(device, C.c_void_p(_synced(device, frames, also=bool(opts.out_on_device))), B, H, W, Cn, sr, sf, C.byref(lens), _dptr(nk), Ho, Wo, osr, osf,
                                     C.byref(opts), C.c_void_p(optr), None if flags is None else flags.ctypes.data,
                                     None if qmap is None else qmap.ctypes.data))
     return out, flags, qmap
@@ -1053,6 +1084,68 @@ def convert_frames(frames, pixel_format, out_format="bgr", matrix=None, out=None
     _check(lib.sba_convert_frames(device, C.c_void_p(L.y), C.c_void_p(L.u), C.c_void_p(L.v), B, H, W, L.y_row_pitch, L.y_frame_pitch,
                                   L.c_row_pitch, L.c_frame_pitch, L.c_step, None if m is None else C.byref(m), osr, osf, C.byref(opts),
                                   C.c_void_p(optr)))
+    return out
+
+
+def yuv_planes_alloc(pixel_format, B, H, W, on_device, device=0):
+    """Uninitialised memory for ``B`` YUV 4:2:0 frames of ``W`` x ``H`` in ``pixel_format``, as ``_yuv_layout`` reads it: the stacked
+    (B, H + H / 2, W) array of ffmpeg's rawvideo pipe when W and H are even, else the tuple of planes in the format's order
+    -- ``(y, uv)``, or ``(y, u, v)`` (yv12: ``(y, v, u)``).  numpy, or torch on ``device`` with ``on_device``."""
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    if W % 2 == 0 and H % 2 == 0:
+        shapes = [(B, H + ch, W)]
+    else:
+        shapes = [(B, H, W), (B, ch, cw, 2)] if pixel_format in ("nv12", "nv21") else [(B, H, W), (B, ch, cw), (B, ch, cw)]
+    if on_device:
+        import torch
+        planes = [torch.empty(s, dtype=torch.uint8, device=f"cuda:{device}") for s in shapes]
+    else:
+        planes = [np.empty(s, np.uint8) for s in shapes]
+    return planes[0] if len(planes) == 1 else tuple(planes)
+
+
+def frames_to_yuv(frames, pixel_format="nv12", in_format="bgr", matrix=None, chroma="nearest", out=None, out_on_device=None,
+                  chunk_frames=0, device=0):
+    """sba_frames_to_yuv (include/sba_hip.h): ``frames`` as for ``detect_dots`` (uint8, (B, H, W, C) with C in (1, 3, 4) or
+    (B, H, W); numpy, or a torch tensor on ``device`` read in place) -> 8-bit YUV 4:2:0 in ``pixel_format`` "nv12", "nv21",
+    "i420" or "yv12".  ``in_format``: "bgr", "rgb" (C = 3), "bgra", "rgba" (C = 4) or "gray" (C = 1); frames with one channel
+    are grey whatever it says.  ``matrix``: the ten integers (y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv) or None for
+    OpenCV's BT.601 table; ``chroma``: "nearest" or "average".  The result is described as ``_yuv_layout`` reads a source: it
+    is ``out`` -- a stacked array or a tuple of planes, numpy (writeable) or tensors on ``device``, any strides that layout
+    allows, what lies between the samples left untouched -- or is allocated by ``yuv_planes_alloc`` on the side the frames are
+    on (``out_on_device`` True / False overrides that).  ``lasercalib_amd.imaging.frames_to_yuv`` is the public face."""
+    fmt, pix = str(in_format).lower(), str(pixel_format).lower()
+    if fmt not in IN_FORMATS:
+        raise ValueError(f"in_format must be one of {sorted(IN_FORMATS)}, not {in_format!r}")
+    if pix not in YUV_FORMATS:
+        raise ValueError(f"pixel_format must be one of {YUV_FORMATS}, not {pixel_format!r}")
+    if chroma not in CHROMA_MODES:
+        raise ValueError(f"chroma must be one of {sorted(CHROMA_MODES)}, not {chroma!r}")
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    if Cn != 1 and IN_FORMATS[fmt] != Cn:
+        raise ValueError(f"in_format {fmt!r} has {IN_FORMATS[fmt]} byte(s) per pixel, the frames have {Cn}")
+    m = None
+    if matrix is not None:
+        vals = [int(v) for v in matrix]
+        if len(vals) != 10 or any(not -(1 << 31) <= v < (1 << 31) for v in vals):
+            raise ValueError(f"matrix must be ten 32-bit integers (y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv), got {matrix!r}")
+        m = RgbMatrix(*vals)
+    if out is None:
+        out = yuv_planes_alloc(pix, B, H, W, tensor if out_on_device is None else bool(out_on_device), device)
+    L = _yuv_layout(out, pix, device)
+    if (L.n_frames, L.height, L.width) != (B, H, W):
+        raise ValueError(f"out holds {L.n_frames} frames of {L.width} x {L.height}, the frames are {B} of {W} x {H}")
+    if not L.tensor and any(not (isinstance(a, np.ndarray) and a.flags.writeable) for a in L.keep):
+        raise ValueError("out must be writeable numpy arrays or tensors on the device")
+    lib = load()
+    opts = ToYuvOpts()
+    opts.frames_on_device, opts.out_on_device = 1 if tensor else 0, 1 if L.tensor else 0
+    opts.in_format = PIXEL_FORMATS.get(fmt, 0)                             # "gray": one channel, the format is not looked at
+    opts.chroma, opts.chunk_frames = CHROMA_MODES[chroma], int(chunk_frames)
+    ptr = _synced(device, frames, also=L.tensor)
+    _check(lib.sba_frames_to_yuv(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.c_void_p(L.y), C.c_void_p(L.u), C.c_void_p(L.v),
+                                 L.y_row_pitch, L.y_frame_pitch, L.c_row_pitch, L.c_frame_pitch, L.c_step,
+                                 None if m is None else C.byref(m), C.byref(opts)))
     return out
 
 

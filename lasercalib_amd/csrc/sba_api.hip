@@ -37,6 +37,9 @@ int sba_convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8
 int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, int32_t fx, int32_t fy, int64_t out_row_pitch, int64_t out_frame_pitch,
                     const sba_resize_opts& opts, uint8_t* out);
+int sba_to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
+                    int64_t frame_pitch, uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_row_pitch, int64_t y_frame_pitch,
+                    int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -607,6 +610,43 @@ int sba_resize_frames(int device, const uint8_t* frames, int64_t n_frames, int32
   return guarded(nullptr, [&] {
     return sba_resize_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, fx, fy, out_row_pitch, out_frame_pitch,
                            o, out);
+  });
+}
+
+int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                      int64_t row_pitch, int64_t frame_pitch, uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_row_pitch, int64_t y_frame_pitch,
+                      int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step, const sba_rgb_matrix* matrix, const sba_to_yuv_opts* opts) {
+  const char* fn = "sba_frames_to_yuv";
+  sba_to_yuv_opts o{};
+  if (opts) o = *opts;
+  sba_rgb_matrix m{16, 269484, 528482, 102760, -155188, -305135, 460324, 460324, -385875, -74448};   // OpenCV's cvtColor(COLOR_BGR2YUV_I420)
+  if (matrix) m = *matrix;
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
+  if (rc) return rc;
+  if (n_frames > 0 && (!y || !u || !v)) return detect_invalid(fn, "null plane");
+  if (c_step != 1 && c_step != 2) return detect_invalid(fn, "c_step must be 1 (planar) or 2 (interleaved)");
+  if (o.in_format < SBA_PIX_BGR || o.in_format > SBA_PIX_RGBA) return detect_invalid(fn, "in_format must be BGR, RGB, BGRA or RGBA");
+  if (channels != 1 && channels != (o.in_format <= SBA_PIX_RGB ? 3 : 4)) return detect_invalid(fn, "in_format does not have `channels` bytes per pixel");
+  if (o.chroma != SBA_CHROMA_NEAREST && o.chroma != SBA_CHROMA_AVERAGE) return detect_invalid(fn, "chroma must be 0 (nearest) or 1 (average)");
+  {   // every sum of the rule fits 32 bits: 255 (|a| + |b| + |c|) < 2^28 for each row (the derivation is in the header)
+    auto mag = [](int32_t c) { return c < 0 ? -(int64_t)c : (int64_t)c; };
+    const int64_t rows[3] = {mag(m.cry) + mag(m.cgy) + mag(m.cby), mag(m.cru) + mag(m.cgu) + mag(m.cbu), mag(m.crv) + mag(m.cgv) + mag(m.cbv)};
+    if (m.y_offset < 0 || m.y_offset > 255) return detect_invalid(fn, "matrix: y_offset must be in 0..255");
+    for (int64_t abc : rows)
+      if (255 * abc >= ((int64_t)1 << 28)) return detect_invalid(fn, "matrix: 255 (|a| + |b| + |c|) must stay below 2^28 for every row");
+  }
+  const int64_t cw = ((int64_t)width + 1) / 2, ch = ((int64_t)height + 1) / 2;
+  if (y_row_pitch < width) return detect_invalid(fn, "y_row_pitch is smaller than width");
+  if ((__int128)height * y_row_pitch > y_frame_pitch) return detect_invalid(fn, "y_frame_pitch is smaller than height * y_row_pitch");
+  if (cw > 0 && c_row_pitch < c_step * (cw - 1) + 1) return detect_invalid(fn, "c_row_pitch is smaller than c_step * ((width + 1) / 2 - 1) + 1");
+  if (c_row_pitch < 0 || (__int128)ch * c_row_pitch > c_frame_pitch) return detect_invalid(fn, "c_frame_pitch is smaller than ((height + 1) / 2) * c_row_pitch");
+  if ((__int128)n_frames * y_frame_pitch > INT64_MAX || (__int128)n_frames * c_frame_pitch > INT64_MAX)
+    return detect_invalid(fn, "n_frames * a frame pitch overflows");
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc || n_frames == 0) return rc;
+  return guarded(nullptr, [&] {
+    return sba_to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, y, u, v, y_row_pitch, y_frame_pitch,
+                           c_row_pitch, c_frame_pitch, c_step, m, o);
   });
 }
 

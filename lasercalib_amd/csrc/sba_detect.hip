@@ -1,11 +1,13 @@
 // sba_detect.hip -- the kernels that work on video frames: the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
 // connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp), the
-// conversion of decoder frames (sba_convert.hpp) and the area-averaged previews (sba_resize.hpp).  They do not depend on the
+// conversion of decoder frames (sba_convert.hpp), its way back to encoder frames (sba_yuv.hpp) and the area-averaged previews
+// (sba_resize.hpp).  They do not depend on the
 // engine's camera model, so they are compiled once, in a translation unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
 #include "sba_background.hpp"
 #include "sba_convert.hpp"
+#include "sba_yuv.hpp"
 #include "sba_resize.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -56,4 +58,11 @@ int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t
                     const sba_resize_opts& opts, uint8_t* out) {
   return sba_detect::resize_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, fx, fy, out_row_pitch,
                                  out_frame_pitch, opts, out);
+}
+
+int sba_to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
+                    int64_t frame_pitch, uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_row_pitch, int64_t y_frame_pitch,
+                    int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts) {
+  return sba_detect::to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, y, u, v, y_row_pitch,
+                                 y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, matrix, opts);
 }

@@ -12,6 +12,9 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
   removal of the light that is always there (sba_background_suppress), for rigs that cannot be made dark
 * :func:`convert_frames`, :class:`YuvMatrix` -- a decoder's YUV 4:2:0 frames (NV12, NV21, I420, YV12) into BGR / RGB frames or the
   one plane the detectors read (sba_convert_frames): ``cv.cvtColor(frame, cv.COLOR_YUV2BGR_NV12)`` for a batch, on the GPU
+* :func:`frames_to_yuv`, :class:`RgbMatrix` -- the way back: BGR / RGB frames or one plane into the YUV 4:2:0 an encoder takes
+  (sba_frames_to_yuv): ``cv.cvtColor(frame, cv.COLOR_BGR2YUV_I420)`` for a batch, on the GPU; ``undistort_frames`` can hand its
+  result over in that form (``out_pixel_format``), so that 1.5 bytes per pixel leave the device instead of 3
 * :func:`resize_frames`, :func:`mosaic` -- previews: ``cv2.resize(frame, size, interpolation=cv2.INTER_AREA)`` at an integer factor
   and ``cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)`` for a batch (sba_resize_frames), and the cameras of a rig side by side in one canvas
 
@@ -29,7 +32,7 @@ from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE
 SBA_UNDIST_OUTSIDE, SBA_UNDIST_FOLDED, SBA_UNDIST_RANGE = UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE
 
 __all__ = ["Lens", "undistort_frames", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
-           "YuvMatrix", "convert_frames", "resize_frames", "mosaic", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
+           "YuvMatrix", "convert_frames", "RgbMatrix", "frames_to_yuv", "resize_frames", "mosaic", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
 
 
 class Lens:
@@ -154,7 +157,8 @@ def _size(size, name):
 
 
 def undistort_frames(frames, lens, new_camera_matrix=None, out_size=None, interpolation="linear", border_value=0, out=None,
-                     want_flags=False, want_map=False, chunk_frames=0, device=0):
+                     want_flags=False, want_map=False, chunk_frames=0, device=0, out_pixel_format=None, out_matrix="bt601",
+                     out_chroma="nearest", in_format="bgr"):
     """``cv.undistort(frame, K, dist, None, new_camera_matrix)`` for every frame of a batch of one camera.
 
     ``frames``: uint8, (B, H, W, C) with C in (1, 3, 4) or (B, H, W); a numpy array in any layout with contiguous pixels, or a
@@ -163,11 +167,37 @@ def undistort_frames(frames, lens, new_camera_matrix=None, out_size=None, interp
     left untouched).  ``new_camera_matrix=None`` means the lens's own matrix; ``out_size=(width, height)`` defaults to the size
     of the frames.  ``interpolation`` is "linear" or "nearest"; ``border_value`` (0..255) fills what lies outside the source.
     With ``want_flags`` / ``want_map`` returns ``(frames, flags, map)``: ``flags`` (height, width) uint8 of SBA_UNDIST_OUTSIDE |
-    FOLDED | RANGE, ``map`` (height, width, 2) int32, the source position in 1/32 pixels; whichever was not asked for is None."""
+    FOLDED | RANGE, ``map`` (height, width, 2) int32, the source position in 1/32 pixels; whichever was not asked for is None.
+    With an ``out_pixel_format`` ("nv12", "nv21", "i420", "yv12") the result is YUV 4:2:0 as :func:`frames_to_yuv` returns it,
+    under ``out_matrix`` and ``out_chroma``, with ``in_format`` saying which channel of the frames is which: the frames are
+    undistorted chunk by chunk (``chunk_frames`` frames; 0 = as many as ``CONVERT_CHUNK_BYTES`` of undistorted pixels hold) into
+    device memory and each chunk is converted there, so only YUV leaves the device; ``out`` is then what ``frames_to_yuv``
+    takes.  The bytes are those of ``frames_to_yuv(undistort_frames(frames, ...))``."""
     lens = _lens(lens)
     nk = _new_k(lens, new_camera_matrix)
-    _t, _f, _B, H, W, _C, _sr, _sf = _native._frame_layout(frames, device)
+    tensor, arr, B, H, W, Cn, _sr, _sf = _native._frame_layout(frames, device)
     w, h = (W, H) if out_size is None else _size(out_size, "out_size")
+    if out_pixel_format is not None:
+        pix = str(out_pixel_format).lower()
+        if pix not in _native.YUV_FORMATS:
+            raise ValueError(f"out_pixel_format must be one of {_native.YUV_FORMATS}, not {out_pixel_format!r}")
+        m = _rgb_matrix(out_matrix)
+        if out is None:
+            out = _native.yuv_planes_alloc(pix, B, h, w, tensor, device)
+        L = _native._yuv_layout(out, pix, device)
+        if (L.n_frames, L.height, L.width) != (B, h, w):
+            raise ValueError(f"out holds {L.n_frames} frames of {L.width} x {L.height}, the result is {B} of {w} x {h}")
+        step = int(chunk_frames) if chunk_frames > 0 else max(1, CONVERT_CHUNK_BYTES // max(1, Cn * h * w))
+        flags = qmap = None
+        for lo in range(0, max(B, 1), step):                 # a batch without frames: one call, for the diagnostics
+            hi = min(lo + step, B)
+            bgr, fl, qm = _native.undistort_frames(arr[lo:hi], lens.as_tuple(), nk, (h, w), interpolation=interpolation,
+                                                   border_value=border_value, want_flags=want_flags and lo == 0,
+                                                   want_map=want_map and lo == 0, device=device, out_on_device=True)
+            flags, qmap = (fl, qm) if lo == 0 else (flags, qmap)
+            _native.frames_to_yuv(bgr, pix, in_format=in_format, matrix=m, chroma=out_chroma,
+                                  out=_native.yuv_frame_slice(out, lo, hi), device=device)
+        return (out, flags, qmap) if (want_flags or want_map) else out
     res, flags, qmap = _native.undistort_frames(frames, lens.as_tuple(), nk, (h, w), interpolation=interpolation, border_value=border_value,
                                                 out=out, want_flags=want_flags, want_map=want_map, chunk_frames=chunk_frames, device=device)
     return (res, flags, qmap) if (want_flags or want_map) else res
@@ -308,6 +338,93 @@ def convert_frames(frames, pixel_format, out_format="bgr", matrix="bt601", out=N
     a numpy array for numpy frames and a device tensor for tensors, or ``out`` (either kind, any row and frame strides)."""
     return _native.convert_frames(frames, pixel_format, out_format=out_format, matrix=_matrix(matrix), out=out,
                                   chunk_frames=chunk_frames, device=device)
+
+
+class RgbMatrix:
+    """The ten integers of sba_frames_to_yuv's rule (include/sba_hip.h), coefficients times 2^20: ``Y = cry R + cgy G + cby B``
+    plus ``y_offset``, ``U = cru R' + cgu G' + cbu B'`` plus 128, ``V = crv R' + cgv G' + cbv B'`` plus 128, each sum rounded by
+    ``(s + 2^19) >> 20`` and clipped to 0..255.  The mirror of :class:`YuvMatrix`: the kernel knows nothing of standards,
+    ``from_standard`` and the presets compute the integers here, on the host."""
+
+    __slots__ = ("y_offset", "cry", "cgy", "cby", "cru", "cgu", "cbu", "crv", "cgv", "cbv")
+    SHIFT = 20
+
+    def __init__(self, y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv):
+        vals = (y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv)
+        if any(int(v) != v for v in vals):
+            raise ValueError(f"RgbMatrix: the ten values must be integers, got {vals}")
+        for name, v in zip(self.__slots__, vals):
+            setattr(self, name, int(v))
+        if not _native.rgb_matrix_in_bound(self.as_tuple()):
+            raise ValueError(f"RgbMatrix{self.as_tuple()}: y_offset must be in 0..255 and 255 (|a| + |b| + |c|) below 2^28 for every "
+                             "row (a, b, c) (the bound under which the sums fit 32 bits)")
+
+    @classmethod
+    def from_standard(cls, kr, kb, full_range=False):
+        """From the luma weights of a standard (BT.601: 0.299, 0.114; BT.709: 0.2126, 0.0722), each coefficient c as
+        ``round(c * 2**20)``.  With kg = 1 - kr - kb the rows are Y: (kr, kg, kb) sy; U: (-kr, -kg, 1 - kb) sc / (2 (1 - kb));
+        V: (1 - kr, -kg, -kb) sc / (2 (1 - kr)).  Limited range: sy = 219/255, sc = 224/255, y_offset = 16; full range: sy = sc =
+        1, y_offset = 0.  The exact coefficients of a chroma row sum to 0, so the rounded ones sum to -1, 0 or 1, and grey g maps
+        to exactly 128 in both chroma modes (|255 sum| < 2^19, |4 * 255 sum| < 2^21): plain rounding needs no adjustment."""
+        kr, kb = float(kr), float(kb)
+        kg = 1.0 - kr - kb
+        if not (0.0 < kr < 1.0 and 0.0 < kb < 1.0 and kg > 0.0):
+            raise ValueError(f"kr, kb and 1 - kr - kb must lie in (0, 1), got kr = {kr}, kb = {kb}")
+        sy, sc = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+        su, sv = sc / (2.0 * (1.0 - kb)), sc / (2.0 * (1.0 - kr))
+        coeff = (kr * sy, kg * sy, kb * sy, -kr * su, -kg * su, (1.0 - kb) * su, (1.0 - kr) * sv, -kg * sv, -kb * sv)
+        return cls(0 if full_range else 16, *(int(round(c * (1 << cls.SHIFT))) for c in coeff))
+
+    @classmethod
+    def preset(cls, name):
+        """"bt601": the table of OpenCV's ``cvtColor(COLOR_BGR2YUV_I420)`` (limited range, three-decimal constants); "bt709",
+        "bt601-full", "bt709-full": ``from_standard``."""
+        key = str(name).lower()
+        if key == "bt601":
+            return cls(*_native.RGB_BT601)
+        if key in ("bt709", "bt601-full", "bt709-full"):
+            kr, kb = (0.299, 0.114) if key.startswith("bt601") else (0.2126, 0.0722)
+            return cls.from_standard(kr, kb, full_range=key.endswith("-full"))
+        raise ValueError(f"unknown matrix {name!r}: one of 'bt601', 'bt709', 'bt601-full', 'bt709-full' or an RgbMatrix")
+
+    def as_tuple(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, RgbMatrix) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def __repr__(self):
+        return "RgbMatrix(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.__slots__) + ")"
+
+
+def _rgb_matrix(matrix):
+    """The ten integers of an RgbMatrix, a preset's name or a sequence of ten integers."""
+    if isinstance(matrix, RgbMatrix):
+        return matrix.as_tuple()
+    if isinstance(matrix, str):
+        return RgbMatrix.preset(matrix).as_tuple()
+    return RgbMatrix(*matrix).as_tuple()
+
+
+def frames_to_yuv(frames, pixel_format="nv12", in_format="bgr", matrix="bt601", chroma="nearest", out=None, chunk_frames=0, device=0):
+    """What the rest of the library produces -- BGR / RGB frames or one plane -- into what a video encoder takes, 8-bit YUV
+    4:2:0, on the GPU (sba_frames_to_yuv, include/sba_hip.h): ``cv.cvtColor(frame, cv.COLOR_BGR2YUV_I420)`` for a whole batch.
+
+    ``frames``: uint8, (B, H, W, C) with C in (1, 3, 4) or (B, H, W); a numpy array in any layout with contiguous pixels, or a
+    torch tensor on ``device``, read in place.  ``in_format``: "bgr", "rgb" (C = 3), "bgra", "rgba" (C = 4, the fourth channel is
+    ignored) or "gray"; frames with one channel are grey whatever it says.  ``pixel_format``: "nv12", "nv21", "i420" or "yv12".
+    ``matrix``: "bt601" (OpenCV's table, limited range), "bt709", "bt601-full", "bt709-full" or an :class:`RgbMatrix`.
+    ``chroma``: "nearest" takes a chroma sample from the top-left pixel of its 2 x 2 block, as OpenCV does; "average" from the
+    sum of the four (at an odd edge the existing pixel is repeated), with one rounding.
+    Returns, on the side the frames are on, the stacked (B, H + H / 2, W) array of ffmpeg's rawvideo pipe when W and H are even,
+    else the tuple of planes in the format's order -- ``(y, uv)`` with uv (B, ceil(H / 2), ceil(W / 2), 2), or ``(y, u, v)``
+    (yv12: ``(y, v, u)``); or ``out``, a stacked array or such a tuple, numpy or tensors on ``device`` whatever side the frames
+    are on, with any strides :func:`convert_frames` reads: what lies between the samples is left untouched."""
+    return _native.frames_to_yuv(frames, pixel_format, in_format=in_format, matrix=_rgb_matrix(matrix), chroma=chroma, out=out,
+                                 chunk_frames=chunk_frames, device=device)
 
 
 CONVERT_CHUNK_BYTES = 1 << 30       # bytes of the one-channel plane held at a time when decoder frames go to a detector or the model
