@@ -14,6 +14,11 @@ EXACT values (`ratios` below returns error / (eps_T * scale), to be held against
   cost             0.5 sum_i |r_i| (|r_i| + rho_i)
   dp per point     cond(V'_p) |dp_p| + |V'_p^-1| |term magnitudes of the right-hand side g_p + W_p^T dc|
   trial scalars    the sums of the magnitudes of their terms
+  S_ij             d_i d_j, d = sqrt(diag U) exact: Cauchy-Schwarz bounds every term sum of S by it, whatever the conditioning
+  rhs              g_c's scale + sum_p |W_p| |V'_p^-1| (g_p's scale)
+The camera step dc is compared with NO solve: it is held as a backward-stable solution of the system it was computed from,
+|A dc - rhs|_i <= B d_i sum_j d_j |dc_j| with A = S + lam diag(D) as read back from the device, d = sqrt(diag A) and B a-priori
+from Cholesky's error analysis (`solve_bound`, `device_solve_bound`): neither side depends on the condition number.
 A step read back as points_new - points_old carries the rounding of the stored sum, half an ulp of X + dp per coordinate
 whatever the engine's dtype (points are stored in float64): that absolute allowance is taken off the error before the ratio
 (`readback`).  On these rigs it is 1e-13 mm against steps of a few mm.
@@ -175,6 +180,84 @@ def gradient_scales(name, eps):
     return E.gc_mag + eps * gcs, E.gp_mag + eps * gps, E.cost_mag + eps * cs
 
 
+@functools.lru_cache(maxsize=None)
+def reduced(name, lam=LAMBDA0):
+    """The exact reduced camera system of a case at damping lam (oracle/exact_model.reduced_system on the robust-scaled blocks)."""
+    E = exact(name)
+    c = E.case
+    return SimpleNamespace(**ex.reduced_system(E.Jcs, E.Jps, E.rs, c.ci, c.pi, c.C, c.N, lam, c.fixed))
+
+
+def rhs_scale(name, eps, lam=LAMBDA0):
+    """rhs_mag = gc scale + sum over the free points' observations of |W| |V'^-1| gp scale (the residual slack rho_i is inside both)."""
+    c = case(name)
+    gc_s, gp_s, _ = gradient_scales(name, eps)
+    out = gc_s.copy()
+    np.add.at(out, c.ci, np.einsum("maj,mj->ma", reduced(name, lam).G, gp_s[c.pi]))
+    return out.ravel()
+
+
+def solve_bound(n, eps_fact, extra=0.0):
+    """B of |A dc - rhs|_i <= B d_i sum_j d_j |dc_j|, d = sqrt(diag A): Higham, Accuracy and Stability of Numerical Algorithms,
+    2nd ed., Thm 10.3 / 10.4 (|dA| <= gamma_{3n+1} |L||L^T| for the Cholesky solve) with |L||L^T|_ij <= d_i d_j / (1 - gamma_{n+1})
+    (eq. 10.7 and Cauchy-Schwarz on the rows of L), which gives (3n + 2) eps / (1 - (3n + 2) eps); `extra` is the sum of the
+    further relative perturbations of A the caller names (reciprocal square root of the pivots, narrowing to f32)."""
+    g = (3 * n + 2) * eps_fact
+    return g / (1.0 - g) + extra
+
+
+RSQ_F64_REFINED = 4e-15      # rsqrt_nr: hardware estimate + one Newton step (sba_chol_blocked.hpp:40-46)
+RSQ_F64_ESTIMATE = 5e-8      # the estimate used as it is by the fp32 engine's f64 pivots (sba_chol_blocked.hpp:647-651, sba_chol_ll.hpp:85)
+RSQ_F32 = EPS["f32"]         # v_rsq_f32: one ulp (sba_chol_blocked.hpp:178)
+
+
+def device_solve_bound(dtype, n, env=None):
+    """(B, what ran) of the factorisation the engine's route runs on n unknowns when no f64 repeat was taken (report.reserved == 0),
+    after chol_route and read_knobs (sba_engine.hpp:244-257, :83-86); env holds the SBA_CHOL / SBA_CHOL_BIG / SBA_CHOL_F32 switches.
+    A pivot 1/sqrt(a_kk) off by delta scales row and column k of the factored matrix by (1 + delta)^2: 2 delta of d_i d_j.
+      f64 engine, every kernel: f64, refined pivots.
+      f32 engine on f32 lanes (k_cholesky_blocked up to 256 unknowns, k_chol_big_dag<float> beyond): f32, one-ulp pivots, and S and
+        rhs narrowed to f32 on the way in (half an ulp each: eps32 together).
+      f32 engine, k_cholesky_blocked under SBA_CHOL_F32=0 and k_cholesky_ll under SBA_CHOL=ll: f64 with the unrefined estimate.
+      f32 engine, k_cholesky_stream and k_chol_big_prepare / k_chol_big_step: f64, refined pivots (chol16_wave's default)."""
+    env = env or {}
+    if dtype == "f64":
+        return solve_bound(n, EPS["f64"], 2 * RSQ_F64_REFINED), "f64 refined"
+    ll = env.get("SBA_CHOL") != "blocked"
+    ll_all = env.get("SBA_CHOL") == "ll"
+    f32 = env.get("SBA_CHOL_F32", "1") != "0"
+    dag = env.get("SBA_CHOL_BIG") != "launches"
+    if ll and (n > 176 or ll_all) and n <= 256:
+        lanes32, refined = f32 and not ll_all, False                 # LL_F32 / LL
+    elif n <= 176:
+        lanes32, refined = f32, False                                # BLOCKED
+    elif n <= 209:
+        lanes32, refined = False, True                               # STREAM
+    else:
+        lanes32, refined = dag and f32, True                         # BIG_DAG_F32 / BIG_DAG / BIG_LAUNCHES
+    if lanes32:
+        return solve_bound(n, EPS["f32"], 2 * RSQ_F32 + EPS["f32"]), "f32 lanes"
+    if refined:
+        return solve_bound(n, EPS["f64"], 2 * RSQ_F64_REFINED), "f64 refined"
+    return solve_bound(n, EPS["f64"], 2 * RSQ_F64_ESTIMATE), "f64 estimate"
+
+
+def backward_error(S, rhs, damp, dc):
+    """Componentwise backward error of dc in A = S + diag(damp), A dc = rhs, evaluated in np.longdouble:
+    (max_i |res_i| / (d_i sum_j d_j |dc_j|),  the same quotient for the bound of the evaluation's own rounding), d = sqrt(diag A).
+    The evaluation's rounding: n products and n + 1 additions per row in longdouble, (n + 2) eps_ld (|A| |dc| + |rhs|)_i."""
+    L = np.longdouble
+    A = np.asarray(S, dtype=L).copy()
+    n = A.shape[0]
+    A[np.diag_indices(n)] += np.asarray(damp, dtype=L)
+    x = np.asarray(dc, dtype=L).ravel()
+    res = A @ x - np.asarray(rhs, dtype=L)
+    d = np.sqrt(np.diag(A))
+    scale = d * (d @ np.abs(x))
+    own = (n + 2) * np.finfo(L).eps * (np.abs(A) @ np.abs(x) + np.abs(np.asarray(rhs, dtype=L)))
+    return float(np.max(np.abs(res) / scale)), float(np.max(own / scale))
+
+
 def exact_cost_at(name, cams, pts):
     """Exact (robust) cost at other parameters, same pixels and weights."""
     c = case(name)
@@ -186,9 +269,14 @@ def exact_cost_at(name, cams, pts):
 
 # ----------------------------------------------------------------------------- error / (eps * scale) of a set of quantities
 def ratios(name, q, eps, lam=LAMBDA0, readback=False):
-    """q: dict with any of r, Jc, Jp (raw blocks), diagU, gc, gp, cost, V, and for the step: dc, dp, cams_new, pts_new, scal.
+    """q: dict with any of r, Jc, Jp (raw blocks), diagU, gc, gp, cost, V, S, rhs, and for the step: dc, dp, cams_new, pts_new,
+    scal; S, rhs, diagU and dc together also give dc_bwd.
     Returns {quantity: max error / (eps * scale)}; 'r' is in pixels over the a-priori bound B (f32) and absolute (f64 callers
-    use r_abs)."""
+    use r_abs).  S: |S - S_x|_ij / (d_i d_j), d = sqrt(diag U) exact (Cauchy-Schwarz: |S_ij| <= d_i d_j), with S_terms the same
+    error over the term-magnitude matrix (information only); rhs: |rhs - rhs_x| / rhs_mag (`rhs_scale`).  dc_bwd is NOT over
+    eps: the componentwise backward error max_i |A dc - rhs|_i / (d_i sum_j d_j |dc_j|) of dc in the caller's OWN system
+    A = S + lam diag(D), D = diagU with zeros replaced by 1, d = sqrt(diag A), to be held against `solve_bound`; dc_bwd_host is
+    the bound of the host evaluation's own rounding in the same units."""
     E = exact(name)
     c = E.case
     out = {}
@@ -218,6 +306,18 @@ def ratios(name, q, eps, lam=LAMBDA0, readback=False):
         out["V"] = float(np.max(np.abs(q["V"] - E.V) / E.V_mag)) / eps
     if "cost" in q:
         out["cost"] = abs(q["cost"] - E.cost) / cost_s / eps
+    if "S" in q:
+        X = reduced(name, lam)
+        dd = np.outer(X.d, X.d)
+        err = np.abs((np.asarray(q["S"], dtype=np.longdouble) - X.S_ld).astype(np.float64))
+        out["S"] = float(np.max(err / dd)) / eps
+        out["S_terms"] = float(np.max(err[X.S_mag > 0] / X.S_mag[X.S_mag > 0])) / eps
+        out["S_outside"] = float(np.max(np.abs(q["S"])[X.S_mag == 0], initial=0.0))       # where no term exists: exactly zero
+    if "rhs" in q:
+        out["rhs"] = float(np.max(np.abs(np.ravel(q["rhs"]) - reduced(name, lam).rhs) / rhs_scale(name, eps, lam))) / eps
+    if "S" in q and "rhs" in q and "dc" in q and "diagU" in q:
+        dU = np.ravel(q["diagU"])
+        out["dc_bwd"], out["dc_bwd_host"] = backward_error(q["S"], q["rhs"], lam * np.where(dU > 0, dU, 1.0), q["dc"])
     if "gmax" in q:                                    # max |g| over the unknowns: the entry that attains it sets the scale
         g = np.concatenate([E.gc.ravel(), E.gp[free].ravel()])
         gs = np.concatenate([gc_s.ravel(), gp_s[free].ravel()])
@@ -291,6 +391,7 @@ def model_quantities(name, lam=LAMBDA0):
         idx = np.nonzero(c.pi == p)[0]
         rows = (c.ci[idx][:, None] * c.ncp + np.arange(c.ncp)[None, :]).ravel()
         S[np.ix_(rows, rows)] -= Y[idx].reshape(-1, 3) @ W[idx].reshape(-1, 3).T
+    q.update(S=S.copy(), rhs=rhs.copy())               # as the exchange buffer holds them: not damped in the cameras
     Dc = np.einsum("cii->ci", U).ravel()
     S[np.diag_indices(n)] += lam * np.where(Dc > 0, Dc, 1.0)
     L = np.linalg.cholesky(S)
@@ -331,5 +432,12 @@ MODEL_MAX = {
     "s_dx2": 1.0,       # 0.97   d16x24+huber (floor)
     "s_x2": 1.0,        # 0.93   g24x10   (floor)
     "s_gmax": 37.0,     # 36.54  edge11
+    # the reduced camera system as the exchange buffer holds it, over ALL_CASES.  Under the Huber loss every row is scaled by
+    # z^-1/4, z = (r / f_scale)^2, and r is a cancelled difference of ~1e3 px values: a residual of 1 .. 3 px carries 1e2 .. 1e3
+    # eps of itself into its rows and so into S.  S_lin is the same ratio over the cases with the linear loss alone and is held
+    # on those cases beside S.
+    "S": 970.0,         # 968.4  w18x15+huber
+    "S_lin": 22.0,      # 21.47  w18x15
+    "rhs": 150.0,       # 142.2  w18x15+huber
 }
 K = {k: 16.0 * max(1.0, v) for k, v in MODEL_MAX.items()}

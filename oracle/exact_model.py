@@ -14,6 +14,8 @@ What it pins (tests/test_exact_model_host.py pins this file first; tests/test_gp
   normal_sums    diagU, g_c, g_p, V, cost, each with the sum of the magnitudes of its terms
   wt_dc          W_p^T dc = sum over the point's observations of Jp^T (Jc dc), with its term magnitudes
   point_step     (V_p + lam diag D_p) dp = -(g_p + W_p^T dc), fixed points exactly zero
+  reduced_system S = blockdiag(U_c) - sum W_p V'_p^-1 W_p^T (not damped in the cameras) and rhs = -g_c + sum W_p V'_p^-1 g_p over the
+                 free points, V'_p = V_p + lam diag D_p, with d = sqrt(diag U) and the magnitudes of their terms
 About 1 ms per observation (the seven rotations a camera needs are built once per camera).
 """
 from __future__ import annotations
@@ -316,3 +318,117 @@ def point_step(V, gp, wtdc, lam, D, fixed=None):
             x = mp.lu_solve(A, b)
             dp[p] = [float(x[i]) for i in range(3)]
     return dp
+
+
+# ----------------------------------------------------------------------------- the reduced camera system
+def _ld(x):
+    """mpf -> np.longdouble (two float64 pieces: 64 mantissa bits survive)."""
+    hi = float(x)
+    return np.longdouble(hi) + np.longdouble(float(x - mp.mpf(hi)))
+
+
+def _chol3_inv(A):
+    """Inverse of the lower Cholesky factor of a 3 x 3 mpmath matrix (rows of L^-1)."""
+    return mp.inverse(mp.cholesky(A))
+
+
+def reduced_system(Jc, Jp, r, ci, pi, n_cams, n_pts, lam, fixed=None, full_mp=False):
+    """The reduced camera system of the given (robust-scaled) blocks, as the exchange buffer holds it (NOT damped in the cameras):
+        S   = blockdiag(U_c) - sum over free p of W_p V'_p^-1 W_p^T,    V'_p = V_p + lam diag D_p,  D_p = diag V_p (zeros -> 1)
+        rhs = -g_c + sum over free p of W_p V'_p^-1 g_p
+    (fixed points contribute nothing to the sums; their observations still count in U and g_c).  U, g_c, V, g_p, D, the W blocks
+    Jc^T Jp, the 3 x 3 Cholesky factor of V'_p, Z = W L^-T, x_p = V'^-1 g_p and the whole of rhs are formed in mpmath; the sum
+    S -= Z_i Z_j^T alone runs in np.longdouble.  Its terms are bounded by Cauchy-Schwarz: sum_p |Z_i| |Z_j|^T <= d_i d_j because
+    sum_p Z_i Z_i^T <= U_ii, so a sum of N three-term products in longdouble stays below (N + 3) 2^-63 d_i d_j, 0.03 eps64 d_i d_j
+    at 50 points (tests/test_exact_model_host.py holds it to 0.1 against full_mp=True, which forms V'^-1 by mpmath's LU inverse,
+    W V'^-1 W^T as it stands and every sum in mpmath: in common are only the sums of products of float64 values U, V, g and
+    W = Jc^T Jp, which are exact at this precision).
+    Returns dict: S (n,n) float64 and S_ld, the same before its one rounding, rhs (n,), d = sqrt(diag U) with zeros replaced by 1,
+    S_mag = sum |Jc_i||Jc_j| + sum |W||V'^-1||W^T|,
+    G (M,ncp,3) = |W_m| |V'^-1| per observation (rhs_mag = gc scale + sum_m G_m gp scale), share (C,C) bool: the two cameras
+    see a common free point."""
+    if np.finfo(np.longdouble).eps > 2e-19:
+        raise RuntimeError("reduced_system needs an extended-precision np.longdouble (64 mantissa bits)")
+    ci, pi = _indices(ci, pi)
+    M, ncp = ci.size, Jc.shape[2]
+    n = n_cams * ncp
+    free = np.ones(n_pts, bool) if fixed is None else ~np.asarray(fixed, bool)
+    S = np.zeros((n, n), dtype=np.longdouble)
+    S_mag = np.zeros((n, n))
+    rhs, d = np.zeros(n), np.ones(n)
+    G = np.zeros((M, ncp, 3))
+    share = np.eye(n_cams, dtype=bool)
+    with mp.workdps(SUM_DPS):
+        lam = _mpf(lam)
+        mJc = [[[_mpf(v) for v in Jc[m, k]] for k in range(2)] for m in range(M)]
+        mJp = [[[_mpf(v) for v in Jp[m, k]] for k in range(2)] for m in range(M)]
+        mr = [[_mpf(v) for v in r[m]] for m in range(M)]
+        acc = [[mp.mpf(0)] * ncp for _ in range(n_cams)]           # rhs, in mpmath throughout
+        Sx = mp.zeros(n, n) if full_mp else None
+        for c in range(n_cams):
+            sel = np.nonzero(ci == c)[0]
+            o = c * ncp
+            for a in range(ncp):
+                ca = [mJc[m][k][a] for m in sel for k in range(2)]
+                acc[c][a] = -mp.fdot(ca, [mr[m][k] for m in sel for k in range(2)])
+                for b in range(a, ncp):
+                    u = mp.fdot(ca, [mJc[m][k][b] for m in sel for k in range(2)])
+                    S[o + a, o + b] = S[o + b, o + a] = _ld(u)
+                    if full_mp:
+                        Sx[o + a, o + b] = Sx[o + b, o + a] = u
+                    if a == b and u > 0:
+                        d[o + a] = float(mp.sqrt(u))
+            A = np.abs(Jc[sel]).reshape(-1, ncp)
+            S_mag[o:o + ncp, o:o + ncp] = A.T @ A
+        for p in np.nonzero(free)[0]:
+            sel = np.nonzero(pi == p)[0]
+            if sel.size == 0:
+                continue
+            V = mp.matrix(3, 3)
+            g = [mp.mpf(0)] * 3
+            for i in range(3):
+                ci_ = [mJp[m][k][i] for m in sel for k in range(2)]
+                g[i] = mp.fdot(ci_, [mr[m][k] for m in sel for k in range(2)])
+                for j in range(i, 3):
+                    V[i, j] = V[j, i] = mp.fdot(ci_, [mJp[m][k][j] for m in sel for k in range(2)])
+            for i in range(3):
+                V[i, i] += lam * (V[i, i] if V[i, i] > 0 else 1)
+            cams_p = sorted(set(int(c) for c in ci[sel]))
+            W = {c: [[mp.mpf(0)] * 3 for _ in range(ncp)] for c in cams_p}      # one block per camera, duplicates summed
+            for m in sel:
+                Wc = W[int(ci[m])]
+                for a in range(ncp):
+                    for j in range(3):
+                        Wc[a][j] += mJc[m][0][a] * mJp[m][0][j] + mJc[m][1][a] * mJp[m][1][j]
+            rows = np.concatenate([c * ncp + np.arange(ncp) for c in cams_p])
+            Vinv = mp.inverse(V)
+            Vinv_abs = np.array([[abs(float(Vinv[i, j])) for j in range(3)] for i in range(3)])
+            Wabs = np.array([[[abs(float(v)) for v in row] for row in W[c]] for c in cams_p])          # (k, ncp, 3)
+            GW = Wabs @ Vinv_abs
+            S_mag[np.ix_(rows, rows)] += GW.reshape(-1, 3) @ Wabs.reshape(-1, 3).T
+            for m in sel:                                   # |W_m| |V'^-1| of the observation's own block
+                G[m] = np.abs(np.einsum("ka,kj->aj", Jc[m], Jp[m])) @ Vinv_abs
+            share[np.ix_(cams_p, cams_p)] = True
+            if full_mp:
+                x = Vinv * mp.matrix(g)
+                Wm = mp.matrix([row for c in cams_p for row in W[c]])
+                P = Wm * Vinv * Wm.T
+                for a, ra in enumerate(rows):
+                    for b, rb in enumerate(rows):
+                        Sx[int(ra), int(rb)] -= P[a, b]
+            else:
+                Li = _chol3_inv(V)                          # V' = L L^T: V'^-1 = Li^T Li, Z = W Li^T
+                x = Li.T * (Li * mp.matrix(g))
+                Z = np.array([[_ld(mp.fdot(row, [Li[j, i] for i in range(3)])) for j in range(3)] for c in cams_p for row in W[c]],
+                             dtype=np.longdouble)
+                S[np.ix_(rows, rows)] -= Z @ Z.T
+            for c in cams_p:
+                for a in range(ncp):
+                    acc[c][a] += mp.fdot(W[c][a], [x[j] for j in range(3)])
+        if full_mp:
+            for a in range(n):
+                for b in range(n):
+                    S[a, b] = _ld(Sx[a, b])
+        rhs[:] = [float(v) for row in acc for v in row]
+    S = 0.5 * (S + S.T)
+    return dict(S=S.astype(np.float64), S_ld=S, rhs=rhs, d=d, S_mag=S_mag, G=G, share=share)

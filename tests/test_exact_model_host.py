@@ -6,7 +6,9 @@ Here it is checked against itself at twice the precision, against the exact-rati
 reference's finite-difference Jacobian (F3) and against the closed form at zero rotation.  Then it checks the numpy models
 per column kind, the model's damped point step, and scipy's own robust-loss functions.  Last, the numpy model's error
 ratios on the cases of tests/test_gpu_exact_model.py are recomputed: they are where that file's K constants come from
-(oracle/exact_cases.py: K = 16 x the largest ratio, not below 16), so the constants' origin is executable.
+(oracle/exact_cases.py: K = 16 x the largest ratio, not below 16), so the constants' origin is executable.  The reference of the reduced camera system (exact_model.reduced_system) is held to
+0.1 eps64 d_i d_j of a full-mpmath evaluation, and numpy's float64 and LAPACK's float32 Cholesky solves of the model's own
+systems are held to the a-priori backward-error bound the GPU file's part (e) uses, with what that bar can see worked out.
 
 Mutation check of this file (scratch copy): the coefficient 1/30 of a2_s in lm_schur_model.rodrigues_coeffs changed to 1/31
 fails test_numpy_model_per_column_kind[edge11] on the rotation kinds (the cameras below the series switch).
@@ -176,7 +178,7 @@ def test_robust_rows_against_scipy_rho(loss):
     assert np.array_equal(lin[0], r) and np.array_equal(lin[1], Jc) and np.allclose(lin[3], r * r, rtol=2 * EPS64, atol=0)
 
 
-_QUANTITIES = ("blocks", "diagU", "gc", "gp", "cost", "gmax", "dp", "s_cost", "s_pred", "s_dx2", "s_x2", "s_gmax")
+_QUANTITIES = ("blocks", "diagU", "gc", "gp", "cost", "gmax", "dp", "s_cost", "s_pred", "s_dx2", "s_x2", "s_gmax", "S", "rhs")
 
 
 @pytest.mark.parametrize("name", xc.ALL_CASES)
@@ -193,6 +195,79 @@ def test_numpy_model_ratios_stay_under_K_over_16(name):
         if name in xc.VARIANT_CASES and k in ("diagU", "gc", "gp", "cost", "gmax"):
             continue
         assert R[k] <= xc.K[k] / 16.0, (k, R[k], xc.K[k] / 16.0)
+    if xc.case(name).loss == "linear":
+        assert R["S"] <= xc.K["S_lin"] / 16.0, (R["S"], xc.K["S_lin"] / 16.0)
+    assert R["S_outside"] == 0.0
     if "huber" in name:                                      # both branches of the loss are taken, on the exact residuals
         z = xc.exact(name).r ** 2
         assert np.sum(z > 1.0) >= 12 and np.sum(z <= 1.0) >= 12
+
+
+def test_reduced_system_reference_against_full_mpmath():
+    """exact_model.reduced_system sums S in np.longdouble from mpmath factors; on the smallest case (t5x30, n = 65) it must agree
+    with the evaluation that forms V'^-1 by mpmath's inverse and every sum in mpmath to 0.1 eps64 d_i d_j (observed: 1e-3), and the
+    right-hand sides, both in mpmath throughout, bit for bit.  The float64 S is the longdouble one rounded."""
+    E = xc.exact("t5x30")
+    c = E.case
+    X = xc.reduced("t5x30")
+    F = ex.reduced_system(E.Jcs, E.Jps, E.rs, c.ci, c.pi, c.C, c.N, xc.LAMBDA0, c.fixed, full_mp=True)
+    n = c.C * c.ncp
+    assert X.S.shape == (n, n) == (65, 65)
+    dd = np.outer(X.d, X.d)
+    assert np.max(np.abs((X.S_ld - F["S_ld"]).astype(np.float64)) / dd) <= 0.1 * EPS64
+    assert np.array_equal(X.rhs, F["rhs"]) and np.array_equal(X.S, X.S_ld.astype(np.float64)) and np.array_equal(X.S, X.S.T)
+    dU = np.sqrt(E.diagU).ravel()                                            # d is the root of the exact diag U, rounded once
+    assert np.all(np.abs(X.d - dU) <= np.spacing(dU))
+    # Cauchy-Schwarz, the reason d_i d_j is the scale: no entry of S and no term sum exceeds it by more than the damping allows
+    assert np.max(np.abs(X.S) / dd) <= 1.0 and np.all(np.abs(X.S) <= X.S_mag * (1 + 8 * EPS64))
+
+
+def test_reduced_system_of_fixed_points_and_damping():
+    """Fixed points leave the Schur sums but stay in U and g_c; the damping lam D_p sits inside V' (S moves with lam)."""
+    E = xc.exact("t5x30")
+    c = E.case
+    fixed = (np.arange(c.N) % 5) == 1
+    args = (E.Jcs, E.Jps, E.rs, c.ci, c.pi, c.C, c.N)
+    A = xc.reduced("t5x30")
+    Fx = ex.reduced_system(*args, xc.LAMBDA0, fixed)
+    keep = ~fixed[c.pi]
+    sub = ex.reduced_system(E.Jcs[keep], E.Jps[keep], E.rs[keep], c.ci[keep], c.pi[keep], c.C, c.N, xc.LAMBDA0)
+    dd = np.outer(A.d, A.d)
+    # (U - Schur over the free points) = (system of the free points' observations alone) + (U and g_c of the fixed points' observations)
+    s = ex.normal_sums(E.rs[~keep], E.Jcs[~keep], E.Jps[~keep], c.ci[~keep], c.pi[~keep], c.C, c.N)
+    assert np.max(np.abs(np.diag(Fx["S"]) - np.diag(sub["S"]) - s["diagU"].ravel()) / np.diag(dd)) <= 4 * EPS64
+    assert np.max(np.abs(Fx["rhs"] - sub["rhs"] + s["gc"].ravel()) / xc.rhs_scale("t5x30", EPS64)) <= 4 * EPS64
+    assert np.max(np.abs(Fx["S"] - A.S) / dd) > 1e-3                            # the fixed points' Schur terms are gone
+    undamped = ex.reduced_system(*args, 0.0)
+    assert np.max(np.abs(undamped["S"] - A.S) / dd) > 1e-4                      # lam = 1e-2 inside V' is visible at 1e-4 d_i d_j
+
+
+@pytest.mark.parametrize("name", xc.ALL_CASES)
+def test_numpy_cholesky_solves_stay_under_the_a_priori_bound(name):
+    """The bar of the GPU file's part (e) on the host: dc of numpy's float64 Cholesky (the model's) and of LAPACK's float32
+    Cholesky with triangular solves, each as a solution of the model's own damped system, under solve_bound(n, eps) (Higham Thm
+    10.3 / 10.4; the f32 run also narrows A and rhs: eps32).  Observed: at most 92 eps64 (t16x12) of 197 .. 1124, and 0.25 eps32.
+    The longdouble evaluation of the residual stays below 1 % of either bar."""
+    from scipy.linalg import cholesky, solve_triangular
+    q = xc.model_quantities(name)
+    n = q["S"].shape[0]
+    R = xc.ratios(name, {k: q[k] for k in ("S", "rhs", "diagU", "dc")}, EPS64)
+    B64 = xc.solve_bound(n, EPS64)
+    assert R["dc_bwd"] <= B64 and R["dc_bwd_host"] <= 0.01 * B64, (R["dc_bwd"] / EPS64, B64 / EPS64)
+    dU = q["diagU"].ravel()
+    damp = xc.LAMBDA0 * np.where(dU > 0, dU, 1.0)
+    A32 = (q["S"] + np.diag(damp)).astype(np.float32)
+    L = cholesky(A32, lower=True)
+    x = solve_triangular(L, solve_triangular(L, q["rhs"].astype(np.float32), lower=True), lower=True, trans="T")
+    assert L.dtype == np.float32 and x.dtype == np.float32
+    e32 = xc.EPS["f32"]
+    bwd, own = xc.backward_error(q["S"], q["rhs"], damp, x.astype(np.float64))
+    B32 = xc.solve_bound(n, e32, e32)
+    assert bwd <= B32 and own <= 0.01 * B32, (bwd / e32, B32 / e32)
+    # what the bars see: an error of e in the component with the largest d_k |dc_k| leaves e times that component's share of
+    # sum_j d_j |dc_j| (0.011 .. 0.071 on these cases) in row k.  1e-10 of it misses the f64 bar, 5 % the f32 bar.
+    k = int(np.argmax(np.abs(q["dc"].ravel()) * np.sqrt(np.diag(q["S"]) + damp)))
+    for rel, bar in ((1e-10, B64), (5e-2, B32)):
+        bad = q["dc"].ravel().copy()
+        bad[k] *= 1.0 + rel
+        assert xc.backward_error(q["S"], q["rhs"], damp, bad)[0] > bar
