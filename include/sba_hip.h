@@ -964,6 +964,73 @@ int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32
                       int32_t c_step /*1 or 2*/, const sba_rgb_matrix* matrix /*NULL: OpenCV's BT.601 table*/,
                       const sba_to_yuv_opts* opts /*NULL: all zero*/);
 
+/* ---------------------------------------------------------------- undistortion of YUV 4:2:0 frames, plane by plane
+ * What a calibration is used for on a VIDEO: decoder frames in, encoder frames out, with the lens taken out in between.
+ * Through sba_convert_frames, sba_undistort_frames and sba_frames_to_yuv that is three calls, 15 bytes moved per pixel and
+ * two colour-matrix round trips.  A video does not need the colour space (ffmpeg's lenscorrection works plane by plane
+ * too): the luma plane is a one-channel image under the lens, the chroma planes are half-size images under the same lens.
+ * sba_undistort_yuv does that in one call and one kernel launch per chunk: 1.5 bytes read and 1.5 written per pixel, no
+ * matrix, no clip, and an identity lens (new_k equal to the lens's own matrix) returns the input bit for bit.  Stateless.
+ *
+ * The source, *src, is three planes described exactly as the source of sba_convert_frames (NV12, NV21, I420, YV12 by u, v
+ * and c_step; any bases and pitches; odd sizes); all host memory, or with frames_on_device all device memory of `device`,
+ * read in place.  `width` x `height` is its luma size W x H; its chroma planes are cw x ch = (W + 1) / 2 x (H + 1) / 2.
+ * The destination, *out, is three planes described exactly as the destination of sba_frames_to_yuv, of the luma size
+ * out_width x out_height (each in 0..16384) and the chroma size (out_width + 1) / 2 x (out_height + 1) / 2; all host
+ * memory, or with out_on_device all device memory.  The two sides may be different formats.  Padding is never written, and
+ * with c_step = 2 the byte between two samples of a plane of its own is never written either.  Source and destination
+ * must not overlap.  The reserved members are not looked at.
+ *
+ * The rule -- this is the function's definition.  Every float64 operation is ONE IEEE operation, in the order written,
+ * never contracted; ifx = 1.0 / fxn and ify = 1.0 / fyn are formed once on the host.
+ * Luma sample (x, y) is the rule of sba_undistort_frames with channels = 1 on the Y plane, word for word: sx, sy, in_range,
+ *   qx, qy, the taps and weights, (sum w * tap + 512) >> 10, nearest's snapping, and border_y for a tap outside the plane.
+ *   flags_out and map_out are that call's flags and map -- the luma geometry -- and nothing else.
+ * Chroma sample (i, j), the same for U and V:
+ *   1. the same model at the centre of the sample's 2 x 2 block: x = 2.0*i + 0.5, y = 2.0*j + 0.5 (exact in float64), through
+ *      the same lines up to sx, sy and in_range;
+ *   2. the position in the chroma plane on its 1/32 grid: m = sx*16.0; m = m - 8.0; m = m + 0.5; qcx = floor(m), qcy likewise
+ *      from sy; both 0 when !in_range.  (This is (sx - 0.5) / 2 in units of 1/32 chroma sample.)
+ *   3. taps and weights from (qcx, qcy) exactly as luma takes them from (qx, qy), nearest's ((q + 16) >> 5) included;
+ *   4. a tap (tx, ty) is inside when 0 <= tx < cw and 0 <= ty < ch; a tap outside, and every tap when !in_range, has the
+ *      value border_u for U and border_v for V;
+ *   5. the value is (sum w * tap + 512) >> 10.
+ * Centre siting -- a chroma sample stands for the centre of its block -- is the siting under which the nearest chroma of
+ * sba_convert_frames (every pixel of a block takes the block's sample) and the averaged chroma of sba_frames_to_yuv (a
+ * sample is the mean of its block) are consistent with each other.  Other sitings are not offered.
+ * The borders are taken literally: (16, 128, 128) is limited-range black.
+ * out may be NULL when a diagnostic is asked for: then no frame is read.  The diagnostics are host memory, written once per
+ * call, also when n_frames == 0.  Frames pass through the device in chunks (host planes through two staging buffers, every
+ * host plane of the result through one more), the copy of chunk k + 1 to the device beside the copy of chunk k back; device
+ * memory does not grow with n_frames, and any chunk_frames gives the same bytes.
+ * Errors, all checked before any device work (text "sba_undistort_yuv: ..." in sba_last_error(NULL)), every output left
+ * untouched: SBA_ERR_INVALID for a NULL src and, for *src, the plane errors of sba_convert_frames (a negative size, a NULL
+ * plane with n_frames > 0, a c_step that is not 1 or 2, pitches too small for the planes' rows); for *out the plane errors
+ * of sba_frames_to_yuv at the output size; the lens, new_k, output-size and interpolation errors of sba_undistort_frames;
+ * a border outside 0..255; out == NULL with n_frames > 0 when neither diagnostic is asked for; SBA_ERR_UNSUPPORTED for width
+ * or height above 16384; SBA_ERR_NO_DEVICE as everywhere. */
+typedef struct {
+  uint8_t *y, *u, *v;        /* a source is only read */
+  int64_t y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch;
+  int32_t c_step;            /* 1 or 2 */
+  int32_t reserved;
+} sba_yuv_planes;
+typedef struct {
+  int32_t frames_on_device;  /* 1: the planes of src are device pointers on `device` */
+  int32_t out_on_device;     /* 1: the planes of out are device pointers on `device` */
+  int32_t interpolation;     /* 0 bilinear, 1 nearest */
+  int32_t border_y;          /* 0..255 each, taken literally */
+  int32_t border_u;
+  int32_t border_v;
+  int32_t chunk_frames;      /* <= 0: library default */
+  int32_t reserved[5];
+} sba_undistort_yuv_opts;
+int sba_undistort_yuv(int device, const sba_yuv_planes* src, int64_t n_frames, int32_t height, int32_t width,
+                      const sba_lens* lens, const double* new_k /*fxn, fyn, cxn, cyn*/, int32_t out_height, int32_t out_width,
+                      const sba_yuv_planes* out /*or NULL*/, const sba_undistort_yuv_opts* opts /*NULL: all zero*/,
+                      uint8_t* flags_out /*out_height*out_width, host, or NULL*/,
+                      int32_t* map_out /*out_height*out_width*2, host, or NULL*/);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

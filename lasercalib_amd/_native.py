@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = (
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
     "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames", "sba_resize_frames",
-    "sba_frames_to_yuv",
+    "sba_frames_to_yuv", "sba_undistort_yuv",
 )
 
 
@@ -208,6 +208,21 @@ class ToYuvOpts(C.Structure):                                             # sba_
 RGB_BT601 = (16, 269484, 528482, 102760, -155188, -305135, 460324, 460324, -385875, -74448)   # OpenCV's table: a NULL matrix
 CHROMA_MODES = {"nearest": 0, "average": 1}                               # sba_chroma_mode
 IN_FORMATS = {"bgr": 3, "rgb": 3, "bgra": 4, "rgba": 4, "gray": 1}        # what frames_to_yuv reads: the channels of each
+
+
+class YuvPlanes(C.Structure):                                             # sba_yuv_planes
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_row_pitch", C.c_int64), ("y_frame_pitch", C.c_int64),
+                ("c_row_pitch", C.c_int64), ("c_frame_pitch", C.c_int64), ("c_step", C.c_int32), ("reserved", C.c_int32)]
+
+
+class UndistortYuvOpts(C.Structure):                                      # sba_undistort_yuv_opts
+    _fields_ = [("frames_on_device", C.c_int32), ("out_on_device", C.c_int32), ("interpolation", C.c_int32), ("border_y", C.c_int32),
+                ("border_u", C.c_int32), ("border_v", C.c_int32), ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+# the tile of luma pixels one workgroup of k_undistort_yuv owns and the workgroups a launch aims at, above which a workgroup walks
+# more than one frame of its chunk (csrc/sba_undistort_yuv.hpp), for the tests that straddle them
+UNDIST_YUV_TILE_ROWS, UNDIST_YUV_TILE_COLS, UNDIST_YUV_GROUPS = 8, 128, 2048
 
 
 def rgb_matrix_in_bound(m):
@@ -524,6 +539,8 @@ def load():
         "sba_frames_to_yuv": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                         C.POINTER(RgbMatrix), C.POINTER(ToYuvOpts)]),
+        "sba_undistort_yuv": (C.c_int, [C.c_int, C.POINTER(YuvPlanes), C.c_int64, C.c_int32, C.c_int32, C.POINTER(LensStruct), dp, C.c_int32,
+                                        C.c_int32, C.POINTER(YuvPlanes), C.POINTER(UndistortYuvOpts), C.c_void_p, C.c_void_p]),
         "sba_resize_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_int64, C.c_int64, C.POINTER(ResizeOpts), C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
@@ -1147,6 +1164,73 @@ def frames_to_yuv(frames, pixel_format="nv12", in_format="bgr", matrix=None, chr
                                  L.y_row_pitch, L.y_frame_pitch, L.c_row_pitch, L.c_frame_pitch, L.c_step,
                                  None if m is None else C.byref(m), C.byref(opts)))
     return out
+
+
+def _yuv_planes_struct(L):
+    return YuvPlanes(L.y, L.u, L.v, L.y_row_pitch, L.y_frame_pitch, L.c_row_pitch, L.c_frame_pitch, L.c_step, 0)
+
+
+def undistort_yuv(frames, pixel_format, lens9, new_k, out_size, interpolation="linear", border=(16, 128, 128), out_pixel_format=None,
+                  out=None, out_on_device=None, want_flags=False, want_map=False, want_frames=True, chunk_frames=0, device=0):
+    """sba_undistort_yuv (include/sba_hip.h): 8-bit YUV 4:2:0 ``frames`` in ``pixel_format`` (see ``_yuv_layout``; numpy, or torch
+    tensors on ``device`` read in place) resampled plane by plane through the lens ``lens9`` = (fx, fy, cx, cy, k1, k2, p1, p2, k3)
+    into the pinhole image of ``new_k`` = (fxn, fyn, cxn, cyn) of ``out_size`` = (height, width), in ``out_pixel_format`` (None:
+    that of the frames).  ``border`` = (Y, U, V), each 0..255, fills what lies outside the source.  Returns (out, flags, map):
+    ``out`` is described as ``_yuv_layout`` reads a source -- the caller's ``out`` (a stacked array or a tuple of planes, numpy
+    (writeable) or tensors on ``device``, what lies between the samples left untouched) or allocated by ``yuv_planes_alloc`` on
+    the side the frames are on (``out_on_device`` True / False overrides that) --, None with ``want_frames=False`` (then no
+    frame is read); ``flags`` (height, width) uint8 and ``map`` (height, width, 2) int32 are those of ``undistort_frames`` for
+    the luma plane, numpy or None.  Every ValueError is raised before the library is loaded.
+    ``lasercalib_amd.imaging.undistort_yuv`` is the public face of this call."""
+    pix = str(pixel_format).lower()
+    if pix not in YUV_FORMATS:
+        raise ValueError(f"pixel_format must be one of {YUV_FORMATS}, not {pixel_format!r}")
+    opix = pix if out_pixel_format is None else str(out_pixel_format).lower()
+    if opix not in YUV_FORMATS:
+        raise ValueError(f"out_pixel_format must be one of {YUV_FORMATS}, not {out_pixel_format!r}")
+    if interpolation not in UNDIST_INTERPOLATION:
+        raise ValueError(f"interpolation must be one of {sorted(UNDIST_INTERPOLATION)}, not {interpolation!r}")
+    try:
+        by, bu, bv = border
+        if any(int(b) != b or not 0 <= int(b) <= 255 for b in (by, bu, bv)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"border must be three integers (Y, U, V) in 0..255, not {border!r}") from None
+    S = _yuv_layout(frames, pix, device)
+    Ho, Wo = (int(v) for v in out_size)
+    if not (0 <= Ho <= DOT_MAX_DIM and 0 <= Wo <= DOT_MAX_DIM):
+        raise ValueError(f"out_size must be (height, width) within 0..{DOT_MAX_DIM}, got {(Ho, Wo)}")
+    lens = LensStruct(*(float(v) for v in lens9))
+    nk = np.ascontiguousarray([float(v) for v in new_k], dtype=np.float64)
+    opts = UndistortYuvOpts()
+    opts.frames_on_device = 1 if S.tensor else 0
+    opts.interpolation, opts.chunk_frames = UNDIST_INTERPOLATION[interpolation], int(chunk_frames)
+    opts.border_y, opts.border_u, opts.border_v = int(by), int(bu), int(bv)
+    D = dst = None
+    if not want_frames:
+        if out is not None:
+            raise ValueError("out was given but no frames are asked for")
+        if not (want_flags or want_map):
+            raise ValueError("nothing asked for: neither frames nor flags nor map")
+    else:
+        if out is None:
+            out = yuv_planes_alloc(opix, S.n_frames, Ho, Wo, S.tensor if out_on_device is None else bool(out_on_device), device)
+        D = _yuv_layout(out, opix, device)
+        if (D.n_frames, D.height, D.width) != (S.n_frames, Ho, Wo):
+            raise ValueError(f"out holds {D.n_frames} frames of {D.width} x {D.height}, the result is {S.n_frames} of {Wo} x {Ho}")
+        if not D.tensor and any(not (isinstance(a, np.ndarray) and a.flags.writeable) for a in D.keep):
+            raise ValueError("out must be writeable numpy arrays or tensors on the device")
+        opts.out_on_device = 1 if D.tensor else 0
+        dst = _yuv_planes_struct(D)
+    lib = load()
+    src = _yuv_planes_struct(S)
+    flags = np.zeros((Ho, Wo), np.uint8) if want_flags else None
+    qmap = np.zeros((Ho, Wo, 2), np.int32) if want_map else None
+    _synced(device, also=S.tensor or bool(opts.out_on_device))             # the planes' addresses are in S and D
+    _check(lib.sba_undistort_yuv(device, C.byref(src), S.n_frames, S.height, S.width, C.byref(lens), _dptr(nk), Ho, Wo,
+                                 None if dst is None else C.byref(dst), C.byref(opts), None if flags is None else flags.ctypes.data,
+                                 None if qmap is None else qmap.ctypes.data))
+    return out, flags, qmap
 
 
 def resize_frames(frames, fx, fy, gray_w=None, out=None, out_on_device=None, chunk_frames=0, device=0):

@@ -40,6 +40,9 @@ int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t
 int sba_to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
                     int64_t frame_pitch, uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_row_pitch, int64_t y_frame_pitch,
                     int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts);
+int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,
+                           const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
+                           const sba_undistort_yuv_opts& opts, uint8_t* flags_out, int32_t* map_out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -647,6 +650,50 @@ int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32
   return guarded(nullptr, [&] {
     return sba_to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, y, u, v, y_row_pitch, y_frame_pitch,
                            c_row_pitch, c_frame_pitch, c_step, m, o);
+  });
+}
+
+// What sba_undistort_yuv checks of one side's planes of `width` x `height` luma samples; `side` ("src", "out") opens the text
+static int yuv_planes_invalid(const char* fn, const char* side, const sba_yuv_planes& p, int64_t n_frames, int32_t height, int32_t width) {
+  const std::string s = std::string(side) + ": ";
+  if (n_frames > 0 && (!p.y || !p.u || !p.v)) return detect_invalid(fn, (s + "null plane").c_str());
+  if (p.c_step != 1 && p.c_step != 2) return detect_invalid(fn, (s + "c_step must be 1 (planar) or 2 (interleaved)").c_str());
+  const int64_t cw = ((int64_t)width + 1) / 2, ch = ((int64_t)height + 1) / 2;
+  if (p.y_row_pitch < width) return detect_invalid(fn, (s + "y_row_pitch is smaller than the width").c_str());
+  if ((__int128)height * p.y_row_pitch > p.y_frame_pitch) return detect_invalid(fn, (s + "y_frame_pitch is smaller than the height times y_row_pitch").c_str());
+  if (cw > 0 && p.c_row_pitch < p.c_step * (cw - 1) + 1) return detect_invalid(fn, (s + "c_row_pitch is smaller than c_step * ((width + 1) / 2 - 1) + 1").c_str());
+  if (p.c_row_pitch < 0 || (__int128)ch * p.c_row_pitch > p.c_frame_pitch)
+    return detect_invalid(fn, (s + "c_frame_pitch is smaller than ((height + 1) / 2) * c_row_pitch").c_str());
+  if ((__int128)n_frames * p.y_frame_pitch > INT64_MAX || (__int128)n_frames * p.c_frame_pitch > INT64_MAX)
+    return detect_invalid(fn, (s + "n_frames * a frame pitch overflows").c_str());
+  return SBA_OK;
+}
+
+int sba_undistort_yuv(int device, const sba_yuv_planes* src, int64_t n_frames, int32_t height, int32_t width, const sba_lens* lens,
+                      const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
+                      const sba_undistort_yuv_opts* opts, uint8_t* flags_out, int32_t* map_out) {
+  const char* fn = "sba_undistort_yuv";
+  sba_undistort_yuv_opts o{};
+  if (opts) o = *opts;
+  if (n_frames < 0 || height < 0 || width < 0) return detect_invalid(fn, "negative size");
+  if (!src) return detect_invalid(fn, "null src");
+  int rc = yuv_planes_invalid(fn, "src", *src, n_frames, height, width);
+  if (rc) return rc;
+  if (!lens || !new_k) return detect_invalid(fn, "null lens or new_k");
+  const double lv[9] = {lens->fx, lens->fy, lens->cx, lens->cy, lens->k1, lens->k2, lens->p1, lens->p2, lens->k3};
+  for (double v : lv) if (!std::isfinite(v)) return detect_invalid(fn, "a lens value is not finite");
+  for (int k = 0; k < 4; ++k) if (!std::isfinite(new_k[k])) return detect_invalid(fn, "a new_k value is not finite");
+  if (!(lens->fx > 0.0) || !(lens->fy > 0.0) || !(new_k[0] > 0.0) || !(new_k[1] > 0.0)) return detect_invalid(fn, "a focal length is not > 0");
+  if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
+  if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
+  if (o.border_y < 0 || o.border_y > 255 || o.border_u < 0 || o.border_u > 255 || o.border_v < 0 || o.border_v > 255)
+    return detect_invalid(fn, "border_y, border_u and border_v must be in 0..255");
+  if (!out && n_frames > 0 && !flags_out && !map_out) return detect_invalid(fn, "null out and no diagnostic asked for");
+  if (out) rc = yuv_planes_invalid(fn, "out", *out, n_frames, out_height, out_width);
+  if (!rc) rc = frame_limit_invalid(fn, device, height, width, "");
+  if (rc) return rc;
+  return guarded(nullptr, [&] {
+    return sba_undistort_yuv_call(device, *src, n_frames, height, width, *lens, new_k, out_height, out_width, out, o, flags_out, map_out);
   });
 }
 

@@ -1,7 +1,7 @@
 // sba_detect.hip -- the kernels that work on video frames: the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
 // connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp), the
-// conversion of decoder frames (sba_convert.hpp), its way back to encoder frames (sba_yuv.hpp) and the area-averaged previews
-// (sba_resize.hpp).  They do not depend on the
+// conversion of decoder frames (sba_convert.hpp), its way back to encoder frames (sba_yuv.hpp), the area-averaged previews
+// (sba_resize.hpp) and the undistortion of YUV 4:2:0 frames plane by plane (sba_undistort_yuv.hpp).  They do not depend on the
 // engine's camera model, so they are compiled once, in a translation unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
@@ -9,6 +9,7 @@
 #include "sba_convert.hpp"
 #include "sba_yuv.hpp"
 #include "sba_resize.hpp"
+#include "sba_undistort_yuv.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -65,4 +66,11 @@ int sba_to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t
                     int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts) {
   return sba_detect::to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, y, u, v, y_row_pitch,
                                  y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, matrix, opts);
+}
+
+int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,
+                           const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
+                           const sba_undistort_yuv_opts& opts, uint8_t* flags_out, int32_t* map_out) {
+  return sba_detect::undistort_yuv_call(device, src, n_frames, height, width, lens, new_k, out_height, out_width, out, opts, flags_out,
+                                        map_out);
 }

@@ -210,6 +210,28 @@ inline void ud_launch(const UdParams& P, int channels, int64_t nf, hipStream_t s
   HIPCHK(hipGetLastError());
 }
 
+// The lens and the new camera matrix of a call; 1 / fxn and 1 / fyn are formed here, once
+inline void ud_set_lens(UdParams& P, const sba_lens& L, const double* new_k) {
+  P.fx = L.fx; P.fy = L.fy; P.cx = L.cx; P.cy = L.cy; P.k1 = L.k1; P.k2 = L.k2; P.p1 = L.p1; P.p2 = L.p2; P.k3 = L.k3;
+  P.ifx = 1.0 / new_k[0]; P.ify = 1.0 / new_k[1]; P.cxn = new_k[2]; P.cyn = new_k[3];
+}
+
+// The diagnostics of a call, once: flags and map of every destination pixel of P into host memory (either may be NULL)
+inline void ud_geometry_out(const UdParams& P, int channels, uint8_t* flags_out, int32_t* map_out) {
+  if (!flags_out && !map_out) return;
+  const int64_t out_px = (int64_t)P.out_height * P.out_width;
+  DotStream s;
+  DevBuf<uint8_t> d_flags;
+  DevBuf<int2> d_map;
+  if (flags_out) d_flags.alloc((size_t)out_px);
+  if (map_out) d_map.alloc((size_t)out_px);
+  hipLaunchKernelGGL(k_undistort_geometry, dim3((unsigned)((out_px + 255) / 256)), dim3(256), 0, s.s, P, channels, d_flags.p, d_map.p);
+  HIPCHK(hipGetLastError());
+  if (flags_out) HIPCHK(hipMemcpyAsync(flags_out, d_flags.p, (size_t)out_px, hipMemcpyDeviceToHost, s.s));
+  if (map_out) HIPCHK(hipMemcpyAsync(map_out, d_map.p, sizeof(int2) * (size_t)out_px, hipMemcpyDeviceToHost, s.s));
+  HIPCHK(hipStreamSynchronize(s.s));
+}
+
 // Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (frames_per_chunk
 // on the larger of the two sides when one of them is host memory, frames_in_chunks, FrameOutput).  Which chunk, workgroup or
 // buffer a frame passes through does not enter its arithmetic: any chunk_frames gives the same bytes.
@@ -223,22 +245,9 @@ inline int undistort_call(int device, const uint8_t* frames, int64_t n_frames, i
   static const int32_t whole[4] = {0, 0, 0, 0};
   UdParams P{};
   P.src = frame_view(frames, row_pitch, frame_pitch, height, width, 0, 0, whole, whole);
-  P.fx = L.fx; P.fy = L.fy; P.cx = L.cx; P.cy = L.cy; P.k1 = L.k1; P.k2 = L.k2; P.p1 = L.p1; P.p2 = L.p2; P.k3 = L.k3;
-  P.ifx = 1.0 / new_k[0]; P.ify = 1.0 / new_k[1]; P.cxn = new_k[2]; P.cyn = new_k[3];
+  ud_set_lens(P, L, new_k);
   P.out_height = out_height; P.out_width = out_width; P.nearest = o.interpolation == 1; P.border = o.border_value;
-
-  if (flags_out || map_out) {
-    DotStream s;
-    DevBuf<uint8_t> d_flags;
-    DevBuf<int2> d_map;
-    if (flags_out) d_flags.alloc((size_t)out_px);
-    if (map_out) d_map.alloc((size_t)out_px);
-    hipLaunchKernelGGL(k_undistort_geometry, dim3((unsigned)((out_px + 255) / 256)), dim3(256), 0, s.s, P, channels, d_flags.p, d_map.p);
-    HIPCHK(hipGetLastError());
-    if (flags_out) HIPCHK(hipMemcpyAsync(flags_out, d_flags.p, (size_t)out_px, hipMemcpyDeviceToHost, s.s));
-    if (map_out) HIPCHK(hipMemcpyAsync(map_out, d_map.p, sizeof(int2) * (size_t)out_px, hipMemcpyDeviceToHost, s.s));
-    HIPCHK(hipStreamSynchronize(s.s));
-  }
+  ud_geometry_out(P, channels, flags_out, map_out);
   if (n_frames == 0 || !out) return SBA_OK;
 
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;

@@ -15,6 +15,8 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
 * :func:`frames_to_yuv`, :class:`RgbMatrix` -- the way back: BGR / RGB frames or one plane into the YUV 4:2:0 an encoder takes
   (sba_frames_to_yuv): ``cv.cvtColor(frame, cv.COLOR_BGR2YUV_I420)`` for a batch, on the GPU; ``undistort_frames`` can hand its
   result over in that form (``out_pixel_format``), so that 1.5 bytes per pixel leave the device instead of 3
+* :func:`undistort_yuv`                -- the lens taken out of a video plane by plane: decoder YUV 4:2:0 in, encoder YUV 4:2:0
+  out, in one call and without a colour matrix (sba_undistort_yuv)
 * :func:`resize_frames`, :func:`mosaic` -- previews: ``cv2.resize(frame, size, interpolation=cv2.INTER_AREA)`` at an integer factor
   and ``cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)`` for a batch (sba_resize_frames), and the cameras of a rig side by side in one canvas
 
@@ -31,7 +33,7 @@ from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE
 
 SBA_UNDIST_OUTSIDE, SBA_UNDIST_FOLDED, SBA_UNDIST_RANGE = UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE
 
-__all__ = ["Lens", "undistort_frames", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
+__all__ = ["Lens", "undistort_frames", "undistort_yuv", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
            "YuvMatrix", "convert_frames", "RgbMatrix", "frames_to_yuv", "resize_frames", "mosaic", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
 
 
@@ -200,6 +202,32 @@ def undistort_frames(frames, lens, new_camera_matrix=None, out_size=None, interp
         return (out, flags, qmap) if (want_flags or want_map) else out
     res, flags, qmap = _native.undistort_frames(frames, lens.as_tuple(), nk, (h, w), interpolation=interpolation, border_value=border_value,
                                                 out=out, want_flags=want_flags, want_map=want_map, chunk_frames=chunk_frames, device=device)
+    return (res, flags, qmap) if (want_flags or want_map) else res
+
+
+def undistort_yuv(frames, pixel_format, lens, new_camera_matrix=None, out_size=None, interpolation="linear", border=(16, 128, 128),
+                  out_pixel_format=None, out=None, want_flags=False, want_map=False, chunk_frames=0, device=0):
+    """The lens taken out of a video without leaving its colour space: a decoder's 8-bit YUV 4:2:0 frames in, an encoder's out,
+    resampled plane by plane in one call (sba_undistort_yuv, include/sba_hip.h), as ffmpeg's ``lenscorrection`` works.
+
+    ``frames`` and ``pixel_format`` ("nv12", "nv21", "i420", "yv12") are what :func:`convert_frames` takes: a stacked array or a
+    tuple of planes, numpy or tensors on ``device`` read in place.  The luma plane goes through the rule of
+    :func:`undistort_frames` as a one-channel image; the chroma planes are half-size images under the same lens, their
+    samples sited at the centres of their 2 x 2 blocks.  No colour matrix is applied and nothing is clipped: with
+    ``new_camera_matrix=None`` and a lens without distortion the frames come back bit for bit.  ``out_size=(width, height)``
+    defaults to the size of the frames; ``interpolation`` is "linear" or "nearest"; ``border`` = (Y, U, V), each 0..255 and
+    taken literally, fills what lies outside the source (the default is limited-range black).  ``out_pixel_format=None``
+    means the format of the input.  The result is what :func:`frames_to_yuv` returns -- numpy for numpy frames, tensors for
+    tensors: the stacked array when width and height are even, else the tuple of planes -- or ``out``, which may be of either
+    kind and of any strides :func:`convert_frames` reads; what lies between its samples is left untouched.  With
+    ``want_flags`` / ``want_map`` returns ``(frames, flags, map)`` as :func:`undistort_frames` does, for the luma plane."""
+    lens = _lens(lens)
+    nk = _new_k(lens, new_camera_matrix)
+    L = _native._yuv_layout(frames, pixel_format, device)
+    w, h = (L.width, L.height) if out_size is None else _size(out_size, "out_size")
+    res, flags, qmap = _native.undistort_yuv(frames, pixel_format, lens.as_tuple(), nk, (h, w), interpolation=interpolation, border=border,
+                                             out_pixel_format=out_pixel_format, out=out, want_flags=want_flags, want_map=want_map,
+                                             chunk_frames=chunk_frames, device=device)
     return (res, flags, qmap) if (want_flags or want_map) else res
 
 
