@@ -961,6 +961,25 @@ class YuvLayout:
         for k in self.__slots__:
             setattr(self, k, kw[k])
 
+    def pitches(self):
+        return self.y_row_pitch, self.y_frame_pitch, self.c_row_pitch, self.c_frame_pitch, self.c_step
+
+    def planes_struct(self):
+        """The sba_yuv_planes of sba_undistort_yuv."""
+        return YuvPlanes(self.y, self.u, self.v, *self.pitches(), 0)
+
+    def loose_args(self):
+        """The same as the eight arguments of sba_convert_frames and sba_frames_to_yuv."""
+        return (C.c_void_p(self.y), C.c_void_p(self.u), C.c_void_p(self.v), *self.pitches())
+
+
+def _int32s(values, n, what):
+    """The ``n`` 32-bit integers ``values`` as a list; anything else is a ValueError that opens with ``what``."""
+    vals = [int(v) for v in values]
+    if len(vals) != n or any(not -(1 << 31) <= v < (1 << 31) for v in vals):
+        raise ValueError(f"{what}, got {values!r}")
+    return vals
+
 
 def _bytes_view(name, a, device):
     """(is a tensor, the object, base address, shape, strides in bytes) of a uint8 numpy array or tensor on ``device``."""
@@ -1087,19 +1106,14 @@ def convert_frames(frames, pixel_format, out_format="bgr", matrix=None, out=None
     Cn = PIXEL_BYTES[fmt]
     B, H, W = L.n_frames, L.height, L.width
     shape = (B, H, W) if Cn == 1 else (B, H, W, Cn)
-    m = None
-    if matrix is not None:
-        vals = [int(v) for v in matrix]
-        if len(vals) != 6 or any(not -(1 << 31) <= v < (1 << 31) for v in vals):
-            raise ValueError(f"matrix must be six 32-bit integers (y_offset, cy, cvr, cug, cvg, cub), got {matrix!r}")
-        m = YuvMatrix(*vals)
+    m = None if matrix is None else YuvMatrix(*_int32s(matrix, 6, "matrix must be six 32-bit integers (y_offset, cy, cvr, cug, cvg, cub)"))
     out, out_tensor, optr, osr, osf = _frames_out(out, (shape, (B, H, W, Cn)), L.tensor if out_on_device is None else bool(out_on_device), device)
     opts = ConvertOpts()
     opts.frames_on_device, opts.out_on_device = 1 if L.tensor else 0, 1 if out_tensor else 0
     opts.out_format, opts.chunk_frames = PIXEL_FORMATS[fmt], int(chunk_frames)
     _synced(device, also=L.tensor or out_tensor)             # the planes' addresses are in L
-    _check(lib.sba_convert_frames(device, C.c_void_p(L.y), C.c_void_p(L.u), C.c_void_p(L.v), B, H, W, L.y_row_pitch, L.y_frame_pitch,
-                                  L.c_row_pitch, L.c_frame_pitch, L.c_step, None if m is None else C.byref(m), osr, osf, C.byref(opts),
+    y, u, v, *pitches = L.loose_args()
+    _check(lib.sba_convert_frames(device, y, u, v, B, H, W, *pitches, None if m is None else C.byref(m), osr, osf, C.byref(opts),
                                   C.c_void_p(optr)))
     return out
 
@@ -1119,6 +1133,19 @@ def yuv_planes_alloc(pixel_format, B, H, W, on_device, device=0):
     else:
         planes = [np.empty(s, np.uint8) for s in shapes]
     return planes[0] if len(planes) == 1 else tuple(planes)
+
+
+def _yuv_out(out, pixel_format, B, H, W, on_device, device, wanted):
+    """(out, its YuvLayout) of a call that writes ``B`` YUV 4:2:0 frames of ``W`` x ``H``: the caller's ``out``, checked, or memory
+    from ``yuv_planes_alloc``.  ``wanted`` ("the frames are", "the result is") words the second half of the size error."""
+    if out is None:
+        out = yuv_planes_alloc(pixel_format, B, H, W, on_device, device)
+    L = _yuv_layout(out, pixel_format, device)
+    if (L.n_frames, L.height, L.width) != (B, H, W):
+        raise ValueError(f"out holds {L.n_frames} frames of {L.width} x {L.height}, {wanted} {B} of {W} x {H}")
+    if not L.tensor and any(not (isinstance(a, np.ndarray) and a.flags.writeable) for a in L.keep):
+        raise ValueError("out must be writeable numpy arrays or tensors on the device")
+    return out, L
 
 
 def frames_to_yuv(frames, pixel_format="nv12", in_format="bgr", matrix=None, chroma="nearest", out=None, out_on_device=None,
@@ -1141,33 +1168,18 @@ def frames_to_yuv(frames, pixel_format="nv12", in_format="bgr", matrix=None, chr
     tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
     if Cn != 1 and IN_FORMATS[fmt] != Cn:
         raise ValueError(f"in_format {fmt!r} has {IN_FORMATS[fmt]} byte(s) per pixel, the frames have {Cn}")
-    m = None
-    if matrix is not None:
-        vals = [int(v) for v in matrix]
-        if len(vals) != 10 or any(not -(1 << 31) <= v < (1 << 31) for v in vals):
-            raise ValueError(f"matrix must be ten 32-bit integers (y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv), got {matrix!r}")
-        m = RgbMatrix(*vals)
-    if out is None:
-        out = yuv_planes_alloc(pix, B, H, W, tensor if out_on_device is None else bool(out_on_device), device)
-    L = _yuv_layout(out, pix, device)
-    if (L.n_frames, L.height, L.width) != (B, H, W):
-        raise ValueError(f"out holds {L.n_frames} frames of {L.width} x {L.height}, the frames are {B} of {W} x {H}")
-    if not L.tensor and any(not (isinstance(a, np.ndarray) and a.flags.writeable) for a in L.keep):
-        raise ValueError("out must be writeable numpy arrays or tensors on the device")
+    m = None if matrix is None else RgbMatrix(*_int32s(
+        matrix, 10, "matrix must be ten 32-bit integers (y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv)"))
+    out, L = _yuv_out(out, pix, B, H, W, tensor if out_on_device is None else bool(out_on_device), device, "the frames are")
     lib = load()
     opts = ToYuvOpts()
     opts.frames_on_device, opts.out_on_device = 1 if tensor else 0, 1 if L.tensor else 0
     opts.in_format = PIXEL_FORMATS.get(fmt, 0)                             # "gray": one channel, the format is not looked at
     opts.chroma, opts.chunk_frames = CHROMA_MODES[chroma], int(chunk_frames)
     ptr = _synced(device, frames, also=L.tensor)
-    _check(lib.sba_frames_to_yuv(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.c_void_p(L.y), C.c_void_p(L.u), C.c_void_p(L.v),
-                                 L.y_row_pitch, L.y_frame_pitch, L.c_row_pitch, L.c_frame_pitch, L.c_step,
-                                 None if m is None else C.byref(m), C.byref(opts)))
+    _check(lib.sba_frames_to_yuv(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, *L.loose_args(), None if m is None else C.byref(m),
+                                 C.byref(opts)))
     return out
-
-
-def _yuv_planes_struct(L):
-    return YuvPlanes(L.y, L.u, L.v, L.y_row_pitch, L.y_frame_pitch, L.c_row_pitch, L.c_frame_pitch, L.c_step, 0)
 
 
 def undistort_yuv(frames, pixel_format, lens9, new_k, out_size, interpolation="linear", border=(16, 128, 128), out_pixel_format=None,
@@ -1213,17 +1225,11 @@ def undistort_yuv(frames, pixel_format, lens9, new_k, out_size, interpolation="l
         if not (want_flags or want_map):
             raise ValueError("nothing asked for: neither frames nor flags nor map")
     else:
-        if out is None:
-            out = yuv_planes_alloc(opix, S.n_frames, Ho, Wo, S.tensor if out_on_device is None else bool(out_on_device), device)
-        D = _yuv_layout(out, opix, device)
-        if (D.n_frames, D.height, D.width) != (S.n_frames, Ho, Wo):
-            raise ValueError(f"out holds {D.n_frames} frames of {D.width} x {D.height}, the result is {S.n_frames} of {Wo} x {Ho}")
-        if not D.tensor and any(not (isinstance(a, np.ndarray) and a.flags.writeable) for a in D.keep):
-            raise ValueError("out must be writeable numpy arrays or tensors on the device")
+        out, D = _yuv_out(out, opix, S.n_frames, Ho, Wo, S.tensor if out_on_device is None else bool(out_on_device), device, "the result is")
         opts.out_on_device = 1 if D.tensor else 0
-        dst = _yuv_planes_struct(D)
+        dst = D.planes_struct()
     lib = load()
-    src = _yuv_planes_struct(S)
+    src = S.planes_struct()
     flags = np.zeros((Ho, Wo), np.uint8) if want_flags else None
     qmap = np.zeros((Ho, Wo, 2), np.int32) if want_map else None
     _synced(device, also=S.tensor or bool(opts.out_on_device))             # the planes' addresses are in S and D
@@ -1249,10 +1255,7 @@ def resize_frames(frames, fx, fy, gray_w=None, out=None, out_on_device=None, chu
         raise ValueError(f"the factors must be in 1..{RESIZE_MAX_FACTOR}, got {(fx, fy)}")
     opts = ResizeOpts()
     if gray_w is not None:
-        vals = [int(v) for v in gray_w]
-        if len(vals) != 3 or any(not -(1 << 31) <= v < (1 << 31) for v in vals):
-            raise ValueError(f"gray_w must be three 32-bit integers, got {gray_w!r}")
-        opts.gray, opts.gray_w = 1, (C.c_int32 * 3)(*vals)
+        opts.gray, opts.gray_w = 1, (C.c_int32 * 3)(*_int32s(gray_w, 3, "gray_w must be three 32-bit integers"))
     Ho, Wo, Co = H // fy, W // fx, 1 if gray_w is not None else Cn
     shape = (B, Ho, Wo, Cn) if gray_w is None and len(frames.shape) == 4 else (B, Ho, Wo)
     shapes = (shape, (B, Ho, Wo, Co), (B, Ho, Wo) if Co == 1 else None)

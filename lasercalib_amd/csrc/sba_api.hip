@@ -30,16 +30,13 @@ int sba_bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frames, 
 int sba_bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                          int64_t row_pitch, int64_t frame_pitch, const uint8_t* level, const uint8_t* mask, int64_t out_row_pitch,
                          int64_t out_frame_pitch, const sba_background_suppress_opts& opts, uint8_t* out);
-int sba_convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height, int32_t width,
-                     int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step,
-                     const sba_yuv_matrix& matrix, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& opts,
-                     uint8_t* out);
+int sba_convert_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_yuv_matrix& matrix,
+                     int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& opts, uint8_t* out);
 int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, int32_t fx, int32_t fy, int64_t out_row_pitch, int64_t out_frame_pitch,
                     const sba_resize_opts& opts, uint8_t* out);
 int sba_to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
-                    int64_t frame_pitch, uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_row_pitch, int64_t y_frame_pitch,
-                    int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts);
+                    int64_t frame_pitch, const sba_yuv_planes& out, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts);
 int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,
                            const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
                            const sba_undistort_yuv_opts& opts, uint8_t* flags_out, int32_t* map_out);
@@ -438,6 +435,32 @@ static int out_pitch_invalid(const char* fn, int64_t n_frames, int64_t rows, int
   return SBA_OK;
 }
 
+// A set of YUV 4:2:0 planes of `width` x `height` luma samples, read or written; `side` ("src", "out") opens the text of a call
+// that has two sets and is empty for one that has one
+static int yuv_planes_invalid(const char* fn, const char* side, const sba_yuv_planes& p, int64_t n_frames, int32_t height, int32_t width) {
+  auto invalid = [&](const char* what) { return detect_invalid(fn, (*side ? std::string(side) + ": " + what : std::string(what)).c_str()); };
+  if (n_frames > 0 && (!p.y || !p.u || !p.v)) return invalid("null plane");
+  if (p.c_step != 1 && p.c_step != 2) return invalid("c_step must be 1 (planar) or 2 (interleaved)");
+  const int64_t cw = ((int64_t)width + 1) / 2, ch = ((int64_t)height + 1) / 2;
+  if (p.y_row_pitch < width) return invalid("y_row_pitch is smaller than width");
+  if ((__int128)height * p.y_row_pitch > p.y_frame_pitch) return invalid("y_frame_pitch is smaller than height * y_row_pitch");
+  if (cw > 0 && p.c_row_pitch < p.c_step * (cw - 1) + 1) return invalid("c_row_pitch is smaller than c_step * ((width + 1) / 2 - 1) + 1");
+  if (p.c_row_pitch < 0 || (__int128)ch * p.c_row_pitch > p.c_frame_pitch) return invalid("c_frame_pitch is smaller than ((height + 1) / 2) * c_row_pitch");
+  if ((__int128)n_frames * p.y_frame_pitch > INT64_MAX || (__int128)n_frames * p.c_frame_pitch > INT64_MAX)
+    return invalid("n_frames * a frame pitch overflows");
+  return SBA_OK;
+}
+
+// The lens and the new camera matrix of the two undistortions
+static int lens_invalid(const char* fn, const sba_lens* lens, const double* new_k) {
+  if (!lens || !new_k) return detect_invalid(fn, "null lens or new_k");
+  const double lv[9] = {lens->fx, lens->fy, lens->cx, lens->cy, lens->k1, lens->k2, lens->p1, lens->p2, lens->k3};
+  for (double v : lv) if (!std::isfinite(v)) return detect_invalid(fn, "a lens value is not finite");
+  for (int k = 0; k < 4; ++k) if (!std::isfinite(new_k[k])) return detect_invalid(fn, "a new_k value is not finite");
+  if (!(lens->fx > 0.0) || !(lens->fy > 0.0) || !(new_k[0] > 0.0) || !(new_k[1] > 0.0)) return detect_invalid(fn, "a focal length is not > 0");
+  return SBA_OK;
+}
+
 int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts* opts, uint64_t* sums, int32_t* box, double* centroid,
                     int32_t* status) {
@@ -487,12 +510,8 @@ int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, in
   sba_undistort_opts o{};
   if (opts) o = *opts;
   int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
+  if (!rc) rc = lens_invalid(fn, lens, new_k);
   if (rc) return rc;
-  if (!lens || !new_k) return detect_invalid(fn, "null lens or new_k");
-  const double lv[9] = {lens->fx, lens->fy, lens->cx, lens->cy, lens->k1, lens->k2, lens->p1, lens->p2, lens->k3};
-  for (double v : lv) if (!std::isfinite(v)) return detect_invalid(fn, "a lens value is not finite");
-  for (int k = 0; k < 4; ++k) if (!std::isfinite(new_k[k])) return detect_invalid(fn, "a new_k value is not finite");
-  if (!(lens->fx > 0.0) || !(lens->fy > 0.0) || !(new_k[0] > 0.0) || !(new_k[1] > 0.0)) return detect_invalid(fn, "a focal length is not > 0");
   if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
   if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
   if (o.border_value < 0 || o.border_value > 255) return detect_invalid(fn, "border_value must be in 0..255");
@@ -559,9 +578,7 @@ int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uin
   sba_yuv_matrix m{16, 1220542, 1673527, -409993, -852492, 2116026};      // OpenCV's cvtColor(COLOR_YUV2BGR_NV12 / _I420)
   if (matrix) m = *matrix;
   if (n_frames < 0 || height < 0 || width < 0) return detect_invalid(fn, "negative size");
-  if (n_frames > 0 && (!y || !u || !v)) return detect_invalid(fn, "null plane");
   if (n_frames > 0 && !out) return detect_invalid(fn, "null out");
-  if (c_step != 1 && c_step != 2) return detect_invalid(fn, "c_step must be 1 (planar) or 2 (interleaved)");
   if (o.out_format < SBA_PIX_BGR || o.out_format > SBA_PIX_R) return detect_invalid(fn, "unknown out_format");
   {   // every sum of the rule fits 32 bits: 255 |cy| + 128 (|a| + |b|) + 2^19 < 2^31 for each output row
     auto mag = [](int32_t c) { return c < 0 ? -(int64_t)c : (int64_t)c; };
@@ -571,22 +588,15 @@ int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uin
       if (255 * mag(m.cy) + 128 * ab + ((int64_t)1 << 19) >= ((int64_t)1 << 31))
         return detect_invalid(fn, "matrix: 255 |cy| + 128 (|a| + |b|) + 2^19 must stay below 2^31 for every output row");
   }
-  const int64_t cw = ((int64_t)width + 1) / 2, ch = ((int64_t)height + 1) / 2, px = o.out_format <= SBA_PIX_RGB ? 3 : o.out_format <= SBA_PIX_RGBA ? 4 : 1;
-  if (y_row_pitch < width) return detect_invalid(fn, "y_row_pitch is smaller than width");
-  if ((__int128)height * y_row_pitch > y_frame_pitch) return detect_invalid(fn, "y_frame_pitch is smaller than height * y_row_pitch");
-  if (cw > 0 && c_row_pitch < c_step * (cw - 1) + 1) return detect_invalid(fn, "c_row_pitch is smaller than c_step * ((width + 1) / 2 - 1) + 1");
-  if (c_row_pitch < 0 || (__int128)ch * c_row_pitch > c_frame_pitch) return detect_invalid(fn, "c_frame_pitch is smaller than ((height + 1) / 2) * c_row_pitch");
-  const char* overflows = "n_frames * a frame pitch overflows";           // one text for the three pitches
-  int rc = out_pitch_invalid(fn, n_frames, height, width * px, out_row_pitch, out_frame_pitch,
-                             "out_row_pitch is smaller than width * bytes of a pixel", "height", overflows);
-  if (rc) return rc;
-  if ((__int128)n_frames * y_frame_pitch > INT64_MAX || (__int128)n_frames * c_frame_pitch > INT64_MAX) return detect_invalid(fn, overflows);
-  rc = frame_limit_invalid(fn, device, height, width, "");
+  const int64_t px = o.out_format <= SBA_PIX_RGB ? 3 : o.out_format <= SBA_PIX_RGBA ? 4 : 1;
+  const sba_yuv_planes src{const_cast<uint8_t*>(y), const_cast<uint8_t*>(u), const_cast<uint8_t*>(v), y_row_pitch, y_frame_pitch, c_row_pitch,
+                           c_frame_pitch, c_step, 0};
+  int rc = yuv_planes_invalid(fn, "", src, n_frames, height, width);
+  if (!rc) rc = out_pitch_invalid(fn, n_frames, height, width * px, out_row_pitch, out_frame_pitch,
+                                  "out_row_pitch is smaller than width * bytes of a pixel", "height", "n_frames * a frame pitch overflows");
+  if (!rc) rc = frame_limit_invalid(fn, device, height, width, "");
   if (rc || n_frames == 0) return rc;
-  return guarded(nullptr, [&] {
-    return sba_convert_call(device, y, u, v, n_frames, height, width, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, m,
-                            out_row_pitch, out_frame_pitch, o, out);
-  });
+  return guarded(nullptr, [&] { return sba_convert_call(device, src, n_frames, height, width, m, out_row_pitch, out_frame_pitch, o, out); });
 }
 
 int sba_resize_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -626,8 +636,6 @@ int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32
   if (matrix) m = *matrix;
   int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
   if (rc) return rc;
-  if (n_frames > 0 && (!y || !u || !v)) return detect_invalid(fn, "null plane");
-  if (c_step != 1 && c_step != 2) return detect_invalid(fn, "c_step must be 1 (planar) or 2 (interleaved)");
   if (o.in_format < SBA_PIX_BGR || o.in_format > SBA_PIX_RGBA) return detect_invalid(fn, "in_format must be BGR, RGB, BGRA or RGBA");
   if (channels != 1 && channels != (o.in_format <= SBA_PIX_RGB ? 3 : 4)) return detect_invalid(fn, "in_format does not have `channels` bytes per pixel");
   if (o.chroma != SBA_CHROMA_NEAREST && o.chroma != SBA_CHROMA_AVERAGE) return detect_invalid(fn, "chroma must be 0 (nearest) or 1 (average)");
@@ -638,35 +646,11 @@ int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32
     for (int64_t abc : rows)
       if (255 * abc >= ((int64_t)1 << 28)) return detect_invalid(fn, "matrix: 255 (|a| + |b| + |c|) must stay below 2^28 for every row");
   }
-  const int64_t cw = ((int64_t)width + 1) / 2, ch = ((int64_t)height + 1) / 2;
-  if (y_row_pitch < width) return detect_invalid(fn, "y_row_pitch is smaller than width");
-  if ((__int128)height * y_row_pitch > y_frame_pitch) return detect_invalid(fn, "y_frame_pitch is smaller than height * y_row_pitch");
-  if (cw > 0 && c_row_pitch < c_step * (cw - 1) + 1) return detect_invalid(fn, "c_row_pitch is smaller than c_step * ((width + 1) / 2 - 1) + 1");
-  if (c_row_pitch < 0 || (__int128)ch * c_row_pitch > c_frame_pitch) return detect_invalid(fn, "c_frame_pitch is smaller than ((height + 1) / 2) * c_row_pitch");
-  if ((__int128)n_frames * y_frame_pitch > INT64_MAX || (__int128)n_frames * c_frame_pitch > INT64_MAX)
-    return detect_invalid(fn, "n_frames * a frame pitch overflows");
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  const sba_yuv_planes dst{y, u, v, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, 0};
+  rc = yuv_planes_invalid(fn, "", dst, n_frames, height, width);
+  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
   if (rc || n_frames == 0) return rc;
-  return guarded(nullptr, [&] {
-    return sba_to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, y, u, v, y_row_pitch, y_frame_pitch,
-                           c_row_pitch, c_frame_pitch, c_step, m, o);
-  });
-}
-
-// What sba_undistort_yuv checks of one side's planes of `width` x `height` luma samples; `side` ("src", "out") opens the text
-static int yuv_planes_invalid(const char* fn, const char* side, const sba_yuv_planes& p, int64_t n_frames, int32_t height, int32_t width) {
-  const std::string s = std::string(side) + ": ";
-  if (n_frames > 0 && (!p.y || !p.u || !p.v)) return detect_invalid(fn, (s + "null plane").c_str());
-  if (p.c_step != 1 && p.c_step != 2) return detect_invalid(fn, (s + "c_step must be 1 (planar) or 2 (interleaved)").c_str());
-  const int64_t cw = ((int64_t)width + 1) / 2, ch = ((int64_t)height + 1) / 2;
-  if (p.y_row_pitch < width) return detect_invalid(fn, (s + "y_row_pitch is smaller than the width").c_str());
-  if ((__int128)height * p.y_row_pitch > p.y_frame_pitch) return detect_invalid(fn, (s + "y_frame_pitch is smaller than the height times y_row_pitch").c_str());
-  if (cw > 0 && p.c_row_pitch < p.c_step * (cw - 1) + 1) return detect_invalid(fn, (s + "c_row_pitch is smaller than c_step * ((width + 1) / 2 - 1) + 1").c_str());
-  if (p.c_row_pitch < 0 || (__int128)ch * p.c_row_pitch > p.c_frame_pitch)
-    return detect_invalid(fn, (s + "c_frame_pitch is smaller than ((height + 1) / 2) * c_row_pitch").c_str());
-  if ((__int128)n_frames * p.y_frame_pitch > INT64_MAX || (__int128)n_frames * p.c_frame_pitch > INT64_MAX)
-    return detect_invalid(fn, (s + "n_frames * a frame pitch overflows").c_str());
-  return SBA_OK;
+  return guarded(nullptr, [&] { return sba_to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, dst, m, o); });
 }
 
 int sba_undistort_yuv(int device, const sba_yuv_planes* src, int64_t n_frames, int32_t height, int32_t width, const sba_lens* lens,
@@ -678,12 +662,8 @@ int sba_undistort_yuv(int device, const sba_yuv_planes* src, int64_t n_frames, i
   if (n_frames < 0 || height < 0 || width < 0) return detect_invalid(fn, "negative size");
   if (!src) return detect_invalid(fn, "null src");
   int rc = yuv_planes_invalid(fn, "src", *src, n_frames, height, width);
+  if (!rc) rc = lens_invalid(fn, lens, new_k);
   if (rc) return rc;
-  if (!lens || !new_k) return detect_invalid(fn, "null lens or new_k");
-  const double lv[9] = {lens->fx, lens->fy, lens->cx, lens->cy, lens->k1, lens->k2, lens->p1, lens->p2, lens->k3};
-  for (double v : lv) if (!std::isfinite(v)) return detect_invalid(fn, "a lens value is not finite");
-  for (int k = 0; k < 4; ++k) if (!std::isfinite(new_k[k])) return detect_invalid(fn, "a new_k value is not finite");
-  if (!(lens->fx > 0.0) || !(lens->fy > 0.0) || !(new_k[0] > 0.0) || !(new_k[1] > 0.0)) return detect_invalid(fn, "a focal length is not > 0");
   if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
   if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
   if (o.border_y < 0 || o.border_y > 255 || o.border_u < 0 || o.border_u > 255 || o.border_v < 0 || o.border_v > 255)

@@ -13,8 +13,8 @@
 // cv_store16): one 16-byte access, two of 8, four of 4, or single bytes.  Blocks cut by the right edge (width % 16 pixels, the
 // last of them alone on its chroma sample when the width is odd) and the last row of an odd height take the byte path, pixel
 // by pixel (cv_edge).  Padding is never read or written.
-// The host side stages host planes chunk by chunk through two device buffers and a host output through one more, in the order
-// frames_in_chunks (sba_frames.hpp) documents.
+// The host side stages host planes (YuvSource, sba_frames.hpp, which also holds the chroma modes CV_*) chunk by chunk through
+// two device buffers and a host output through one more, in the order frames_in_chunks (sba_frames.hpp) documents.
 #pragma once
 #include "sba_frames.hpp"
 
@@ -24,7 +24,6 @@ constexpr int CV_RUN = 16;                                   // pixels of a row 
 constexpr int CV_HALF = 32;                                  // lanes side by side on one row pair
 constexpr int CV_WAVE_COLS = CV_RUN * CV_HALF;               // pixels a wave spans
 constexpr int CV_TILE_ROWS = DOT_WAVES * 2 * 2;              // rows of a workgroup: two row pairs per wave
-enum { CV_PLANAR = 0, CV_UV = 1, CV_VU = 2, CV_STEP2 = 3 };  // how the chroma of a block is read
 
 struct CvParams {
   const uint8_t *y, *u, *v;                  // of the chunk's first frame; CV_UV / CV_VU: u is the lower of the two addresses
@@ -217,39 +216,25 @@ inline void cv_launch(const CvParams& P, int fmt, int64_t nf, hipStream_t st) {
 }
 
 // Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (frames_per_chunk
-// on the larger side when one of them is host memory, frames_in_chunks, FrameOutput).  What is staged is the luma plane, then
-// the chroma: ONE plane of 2 ceil(width / 2) bytes a row when u and v are the two halves of an interleaved plane (NV12, NV21),
-// else two planes of c_step (ceil(width / 2) - 1) + 1 bytes a row.  Which chunk or buffer a frame passes through does not
-// enter its arithmetic.
-inline int convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height, int32_t width,
-                        int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step,
-                        const sba_yuv_matrix& M, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& o, uint8_t* out) {
+// on the larger side when one of them is host memory, frames_in_chunks over the planes of a YuvSource, FrameOutput).  Which
+// chunk or buffer a frame passes through does not enter its arithmetic.
+inline int convert_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_yuv_matrix& M,
+                        int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& o, uint8_t* out) {
   if (n_frames == 0 || height == 0 || width == 0) return SBA_OK;
   HIPCHK(hipSetDevice(device));
-  const int C = cv_channels(o.out_format);
-  const int64_t cw = (width + 1) / 2, ch = (height + 1) / 2;
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
+  const YuvSource S(src, height, width);
   CvParams P{};
-  P.height = height; P.width = width; P.c_step = c_step;
+  P.height = height; P.width = width; P.c_step = src.c_step; P.c_mode = S.mode;
   P.y_offset = M.y_offset; P.cy = M.cy; P.cvr = M.cvr; P.cug = M.cug; P.cvg = M.cvg; P.cub = M.cub;
-  // two planes one byte apart are read as one only when its rows hold all their 2 cw bytes without overlapping the next row
-  P.c_mode = c_step == 1 ? CV_PLANAR : c_row_pitch < 2 * cw ? CV_STEP2 : v == u + 1 ? CV_UV : u == v + 1 ? CV_VU : CV_STEP2;
-  const bool paired = P.c_mode == CV_UV || P.c_mode == CV_VU;
-  const uint8_t* c_lo = P.c_mode == CV_VU ? v : u;                        // the plane the kernel's `u` stands for
 
-  const int64_t c_row = paired ? 2 * cw : (int64_t)c_step * (cw - 1) + 1, out_row = (int64_t)width * C;
-  const int n_planes = paired ? 2 : 3;                                    // luma, the kernel's u, and v when it is a plane of its own
-  const FramePlane planes[3] = {{y, y_row_pitch, y_frame_pitch, width, height},
-                                {c_lo, c_row_pitch, c_frame_pitch, c_row, ch},
-                                {v, c_row_pitch, c_frame_pitch, c_row, ch}};
-  const int64_t in_tight = (int64_t)width * height + (n_planes - 1) * c_row * ch;
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(in_tight, out_row * height));
+  const int64_t out_row = (int64_t)width * cv_channels(o.out_format);
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(S.tight, out_row * height));
   FrameOutput O(out, out_row_pitch, out_frame_pitch, out_row, height, out_dev, chunk);
   frames_in_chunks(
-      planes, n_planes, n_frames, in_dev, chunk,
+      S.planes, S.n_planes, n_frames, in_dev, chunk,
       [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {
-        P.y = c[0].base; P.u = c[1].base; P.v = c[n_planes - 1].base;      // paired: v is not read
-        P.y_row_pitch = c[0].row_pitch; P.y_frame_pitch = c[0].frame_pitch; P.c_row_pitch = c[1].row_pitch; P.c_frame_pitch = c[1].frame_pitch;
+        S.chunk(c, P.y, P.u, P.v, P.y_row_pitch, P.y_frame_pitch, P.c_row_pitch, P.c_frame_pitch);
         O.target(lo, P.out, P.out_row_pitch, P.out_frame_pitch);
         cv_launch(P, o.out_format, m, st);
       },

@@ -46,12 +46,9 @@ int sba_bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, in
                                       out_row_pitch, out_frame_pitch, opts, out);
 }
 
-int sba_convert_call(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height, int32_t width,
-                     int64_t y_row_pitch, int64_t y_frame_pitch, int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step,
-                     const sba_yuv_matrix& matrix, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& opts,
-                     uint8_t* out) {
-  return sba_detect::convert_call(device, y, u, v, n_frames, height, width, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step,
-                                  matrix, out_row_pitch, out_frame_pitch, opts, out);
+int sba_convert_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_yuv_matrix& matrix,
+                     int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& opts, uint8_t* out) {
+  return sba_detect::convert_call(device, src, n_frames, height, width, matrix, out_row_pitch, out_frame_pitch, opts, out);
 }
 
 int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -62,10 +59,8 @@ int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t
 }
 
 int sba_to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
-                    int64_t frame_pitch, uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_row_pitch, int64_t y_frame_pitch,
-                    int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts) {
-  return sba_detect::to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, y, u, v, y_row_pitch,
-                                 y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, matrix, opts);
+                    int64_t frame_pitch, const sba_yuv_planes& out, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts) {
+  return sba_detect::to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, out, matrix, opts);
 }
 
 int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,

@@ -4,10 +4,12 @@
 // pixels of a row inside both regions (frame_row_span), one wave's walk over them (scan_row), the rows of a workgroup
 // (frame_rows_per_band); what is done with a pixel once it is found is the consumer's sink (DotSink, BlobSink).  So are the
 // device helpers that more than one kernel uses (wave_lds_sync, channel_words / channel_byte) and ALL host-side plumbing of
-// every frame function (the "host side" below): chunk size, pitched copies, the loop over chunks with its staging, the output.
+// every frame function (the "host side" below): chunk size, pitched copies, the loop over chunks with its staging, the output,
+// and a set of YUV 4:2:0 planes as the source or the output of a call (chroma_mode, YuvSource, YuvOutput).
 // (The store of a finished LDS row at any alignment stays written out in k_undistort and k_resize: as a shared function it
 // compiled to other instructions in both.)
 #pragma once
+#include <optional>
 #include "sba_common.hpp"
 
 namespace sba_detect {
@@ -154,8 +156,9 @@ __device__ __forceinline__ bool scan_row(const uint8_t* __restrict__ rp, int xa,
 
 // ------------------------------------------------------------------------------------------------ host side
 // Everything between a caller's pointers and pitches and the kernels of a chunk: the size of a chunk (frames_per_chunk), the
-// one routine that moves pitched frames (copy_frames), the loop over chunks with its staging (frames_in_chunks) and the
-// output of a call that writes frames (FrameOutput).
+// one routine that moves pitched frames (copy_frames), the loop over chunks with its staging (frames_in_chunks), the output
+// of a call that writes frames (FrameOutput), and what the YUV 4:2:0 calls build from these: how two chroma planes are treated
+// (chroma_mode), their planes as a staged source (YuvSource) and as an output (YuvOutput).
 struct DotStream {
   hipStream_t s = nullptr;
   DotStream() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
@@ -296,6 +299,99 @@ struct FrameOutput {
     if (!on_device)
       copy_frames(out + lo * frame_pitch, row_pitch, frame_pitch, d_packed.p, row_bytes, row_bytes * rows, row_bytes, rows, m, hipMemcpyDeviceToHost, st);
   }
+};
+
+// ---- a set of 8-bit YUV 4:2:0 planes (sba_yuv_planes), read (YuvSource) or written (YuvOutput)
+enum { CV_PLANAR = 0, CV_UV = 1, CV_VU = 2, CV_STEP2 = 3 };  // how a kernel reads or writes the chroma of a block
+
+// The mode of two chroma planes of cw samples a row: two planes one byte apart are taken as ONE plane of pairs only when its
+// rows hold all their 2 cw bytes without overlapping the next row
+inline int chroma_mode(const uint8_t* u, const uint8_t* v, int64_t c_row_pitch, int32_t c_step, int64_t cw) {
+  return c_step == 1 ? CV_PLANAR : c_row_pitch < 2 * cw ? CV_STEP2 : v == u + 1 ? CV_UV : u == v + 1 ? CV_VU : CV_STEP2;
+}
+
+// Planes that frames_in_chunks reads: the luma plane, then the chroma -- ONE plane of 2 ceil(width / 2) bytes a row when u and
+// v are the halves of an interleaved plane (NV12, NV21), else two planes of c_step (ceil(width / 2) - 1) + 1 bytes a row.  A
+// source without pixels (height or width 0) has planes without bytes: nothing of it is staged or read.
+struct YuvSource {
+  int mode, n_planes;                        // n_planes: luma, the kernel's u, and v when it is a plane of its own
+  FramePlane planes[3];
+  int64_t tight;                             // packed bytes of a frame
+  YuvSource(const sba_yuv_planes& S, int32_t height, int32_t width) {
+    const bool empty = height == 0 || width == 0;
+    const int64_t cw = (width + 1) / 2, rows = empty ? 0 : height, c_rows = empty ? 0 : (height + 1) / 2;
+    mode = chroma_mode(S.u, S.v, S.c_row_pitch, S.c_step, cw);
+    const bool paired = mode == CV_UV || mode == CV_VU;
+    n_planes = paired ? 2 : 3;
+    const int64_t c_row = empty ? 0 : paired ? 2 * cw : (int64_t)S.c_step * (cw - 1) + 1;
+    planes[0] = {S.y, S.y_row_pitch, S.y_frame_pitch, empty ? 0 : width, rows};
+    planes[1] = {mode == CV_VU ? S.v : S.u, S.c_row_pitch, S.c_frame_pitch, c_row, c_rows};
+    planes[2] = {S.v, S.c_row_pitch, S.c_frame_pitch, c_row, c_rows};
+    tight = planes[0].row_bytes * rows + (n_planes - 1) * c_row * c_rows;
+  }
+  // what a kernel is given of the chunk `c` that frames_in_chunks hands to launch; paired: u is the lower address, v is not read
+  void chunk(const FramePlane* c, const uint8_t*& y, const uint8_t*& u, const uint8_t*& v, int64_t& y_row, int64_t& y_frame, int64_t& c_row,
+             int64_t& c_frame) const {
+    y = c[0].base; u = c[1].base; v = c[n_planes - 1].base;
+    y_row = c[0].row_pitch; y_frame = c[0].frame_pitch; c_row = c[1].row_pitch; c_frame = c[1].frame_pitch;
+  }
+};
+
+// Planes that a call writes, a FrameOutput each: the luma plane, then ONE plane of pairs or two planes, as above.  Host planes of
+// their own with c_step = 2 are the one layout a pitched copy cannot write without touching the bytes in between: the kernel
+// writes them packed (`mode` and `c_step` are what the KERNEL is given: CV_PLANAR and 1 then), they are fetched into a packed
+// host buffer of a chunk and spread from there by the host once the chunk is drained (done).
+struct YuvOutput {
+  int mode;
+  int32_t c_step;
+  int64_t tight;                             // packed bytes of a frame
+  YuvOutput(const sba_yuv_planes& D_, int32_t height, int32_t width, bool on_device_)
+      : D(D_), w(width), h(height), cw((width + 1) / 2), ch((height + 1) / 2), on_device(on_device_) {
+    const int m = chroma_mode(D.u, D.v, D.c_row_pitch, D.c_step, cw);
+    paired = m == CV_UV || m == CV_VU; spread = m == CV_STEP2 && !on_device;
+    mode = spread ? CV_PLANAR : m;
+    c_step = spread ? 1 : D.c_step;
+    c_row = paired ? 2 * cw : cw;            // bytes of a row as a pitched copy moves it
+    tight = w * h + (paired ? 1 : 2) * c_row * ch;
+  }
+  // once the frames of a chunk are known (frames_per_chunk)
+  void alloc(int64_t chunk) {
+    if (spread) { h_u.resize((size_t)(chunk * cw * ch)); h_v.resize((size_t)(chunk * cw * ch)); }
+    uint8_t* lower = mode == CV_VU ? D.v : D.u;
+    Oy.emplace(D.y, D.y_row_pitch, D.y_frame_pitch, w, h, on_device, chunk);
+    Ou.emplace(spread ? h_u.data() : lower, spread ? cw : D.c_row_pitch, spread ? cw * ch : D.c_frame_pitch, c_row, ch, on_device, chunk);
+    Ov.emplace(spread ? h_v.data() : D.v, spread ? cw : D.c_row_pitch, spread ? cw * ch : D.c_frame_pitch, c_row, paired ? 0 : ch, on_device, chunk);
+  }
+  // what the kernels of the chunk that starts at frame lo write; paired: u is the lower address and v = u, not used
+  void target(int64_t lo, uint8_t*& y, uint8_t*& u, uint8_t*& v, int64_t& y_row, int64_t& y_frame, int64_t& c_row_pitch, int64_t& c_frame) const {
+    int64_t row, frame;
+    Oy->target(lo, y, y_row, y_frame);
+    Ou->target(lo, u, c_row_pitch, c_frame);
+    v = u;
+    if (!paired) Ov->target(lo, v, row, frame);                           // the same pitches as u
+  }
+  // frames_in_chunks' fetch and done
+  void fetch(int64_t lo, int64_t m, hipStream_t st) const {
+    Oy->fetch(lo, m, st);
+    Ou->fetch(spread ? 0 : lo, m, st);                                    // spread: every chunk lands at the start of h_u, h_v
+    Ov->fetch(spread ? 0 : lo, m, st);
+  }
+  void done(int64_t lo, int64_t m) const {
+    if (!spread) return;
+    for (int64_t f = 0; f < m; ++f)
+      for (int64_t j = 0; j < ch; ++j) {
+        const uint8_t *su = h_u.data() + (f * ch + j) * cw, *sv = h_v.data() + (f * ch + j) * cw;
+        uint8_t *du = D.u + (lo + f) * D.c_frame_pitch + j * D.c_row_pitch, *dv = D.v + (lo + f) * D.c_frame_pitch + j * D.c_row_pitch;
+        for (int64_t i = 0; i < cw; ++i) { du[2 * i] = su[i]; dv[2 * i] = sv[i]; }
+      }
+  }
+
+ private:
+  sba_yuv_planes D;
+  int64_t w, h, cw, ch, c_row;
+  bool on_device, paired, spread;
+  std::vector<uint8_t> h_u, h_v;             // spread: the packed planes of a chunk on the host
+  std::optional<FrameOutput> Oy, Ou, Ov;
 };
 
 }  // namespace sba_detect

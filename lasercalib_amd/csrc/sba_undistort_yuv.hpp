@@ -27,10 +27,9 @@
 //     waves of a workgroup never wait for each other and a wave below the last row leaves at once.
 // The kernel is bound by its scattered 2- and 4-byte tap loads, as k_undistort is; per output pixel it issues 2 + 2 / 4 (NV12)
 // of them where k_undistort<3> issues 2 of three times the width, and it forms 1.5 one-channel samples instead of 3.
-// The host side is convert_call's on the way in (frames_in_chunks over two or three planes) and to_yuv_call's on the way out
-// (one FrameOutput per written plane, host planes with c_step = 2 spread by the host).
+// The host side is that of sba_frames.hpp: a YuvSource on the way in (frames_in_chunks over two or three planes, as in
+// convert_call) and a YuvOutput on the way out (as in to_yuv_call).
 #pragma once
-#include <vector>
 #include "sba_undistort.hpp"
 #include "sba_convert.hpp"
 
@@ -47,7 +46,7 @@ struct UyParams {
   int64_t sc_row_pitch, sc_frame_pitch;
   uint8_t *ou, *ov;                          // output chroma likewise
   int64_t oc_row_pitch, oc_frame_pitch;
-  int32_t sc_step, sc_mode, oc_mode;         // CV_PLANAR, CV_UV, CV_VU or CV_STEP2 (sba_convert.hpp) on either side
+  int32_t sc_step, sc_mode, oc_mode;         // CV_PLANAR, CV_UV, CV_VU or CV_STEP2 (sba_frames.hpp) on either side
   int32_t border_u, border_v;
 };
 
@@ -284,15 +283,8 @@ inline void uy_launch(const UyParams& P, int64_t nf, hipStream_t st) {
   HIPCHK(hipGetLastError());
 }
 
-// how two chroma planes are read or written: as one only when its rows hold all their 2 cw bytes without overlapping the next row
-inline int uy_chroma_mode(const uint8_t* u, const uint8_t* v, int64_t c_row_pitch, int32_t c_step, int64_t cw) {
-  return c_step == 1 ? CV_PLANAR : c_row_pitch < 2 * cw ? CV_STEP2 : v == u + 1 ? CV_UV : u == v + 1 ? CV_VU : CV_STEP2;
-}
-
-// Arguments are checked by the caller (sba_api.hip).  The source is staged as convert_call stages it (luma, then ONE plane of
-// 2 ceil(width / 2) bytes a row for interleaved chroma, else two planes), the planes are written as to_yuv_call writes them
-// (one FrameOutput each; host planes of their own with c_step = 2 are written packed, fetched packed and spread by the host
-// once the chunk is drained), in chunks of frames_per_chunk on the larger side when one of the two is host memory.  Which
+// Arguments are checked by the caller (sba_api.hip).  The source is staged as a YuvSource and the planes are written through a
+// YuvOutput (sba_frames.hpp), in chunks of frames_per_chunk on the larger side when one of the two is host memory.  Which
 // chunk, workgroup or buffer a frame passes through does not enter its arithmetic: any chunk_frames gives the same bytes.
 inline int undistort_yuv_call(int device, const sba_yuv_planes& S, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,
                               const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
@@ -308,58 +300,20 @@ inline int undistort_yuv_call(int device, const sba_yuv_planes& S, int64_t n_fra
   ud_geometry_out(P.L, 1, flags_out, map_out);
   if (n_frames == 0 || !out) return SBA_OK;
 
-  const sba_yuv_planes& D = *out;
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
-  const bool empty = height == 0 || width == 0;                           // a source without pixels: every sample is the border
-  const int64_t cw = (width + 1) / 2, ch = (height + 1) / 2, ocw = (out_width + 1) / 2, och = (out_height + 1) / 2;
-  P.sc_step = S.c_step;
-  P.sc_mode = uy_chroma_mode(S.u, S.v, S.c_row_pitch, S.c_step, cw);
-  const bool s_paired = P.sc_mode == CV_UV || P.sc_mode == CV_VU;
-  const int64_t sc_row = empty ? 0 : s_paired ? 2 * cw : (int64_t)S.c_step * (cw - 1) + 1;
-  const int n_planes = s_paired ? 2 : 3;                                  // luma, the kernel's su, and sv when it is a plane of its own
-  const FramePlane planes[3] = {{S.y, S.y_row_pitch, S.y_frame_pitch, empty ? 0 : width, empty ? 0 : height},
-                                {P.sc_mode == CV_VU ? S.v : S.u, S.c_row_pitch, S.c_frame_pitch, sc_row, empty ? 0 : ch},
-                                {S.v, S.c_row_pitch, S.c_frame_pitch, sc_row, empty ? 0 : ch}};
-  const int64_t in_tight = empty ? 0 : (int64_t)width * height + (n_planes - 1) * sc_row * ch;
-
-  const int mode = uy_chroma_mode(D.u, D.v, D.c_row_pitch, D.c_step, ocw);
-  const bool paired = mode == CV_UV || mode == CV_VU, spread = mode == CV_STEP2 && !out_dev;
-  P.oc_mode = spread ? CV_PLANAR : mode;
-  const int64_t oc_row = paired ? 2 * ocw : ocw;                          // bytes of a row as a pitched copy moves it
-  const int64_t out_tight = (int64_t)out_width * out_height + (paired ? 1 : 2) * oc_row * och;
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(in_tight, out_tight));
-  std::vector<uint8_t> h_u, h_v;                                          // spread: the packed planes of a chunk on the host
-  if (spread) { h_u.resize((size_t)(chunk * ocw * och)); h_v.resize((size_t)(chunk * ocw * och)); }
-  FrameOutput Oy(D.y, D.y_row_pitch, D.y_frame_pitch, out_width, out_height, out_dev, chunk);
-  FrameOutput Ou(spread ? h_u.data() : mode == CV_VU ? D.v : D.u, spread ? ocw : D.c_row_pitch, spread ? ocw * och : D.c_frame_pitch, oc_row, och, out_dev, chunk);
-  FrameOutput Ov(spread ? h_v.data() : D.v, spread ? ocw : D.c_row_pitch, spread ? ocw * och : D.c_frame_pitch, oc_row, paired ? 0 : och, out_dev, chunk);
+  const YuvSource Sp(S, height, width);                                   // a source without pixels: every sample is the border
+  YuvOutput O(*out, out_height, out_width, out_dev);
+  P.sc_step = S.c_step; P.sc_mode = Sp.mode; P.oc_mode = O.mode;
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(Sp.tight, O.tight));
+  O.alloc(chunk);
   frames_in_chunks(
-      planes, n_planes, n_frames, in_dev, chunk,
+      Sp.planes, Sp.n_planes, n_frames, in_dev, chunk,
       [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {
-        P.L.src.frames = c[0].base; P.L.src.row_pitch = c[0].row_pitch; P.L.src.frame_pitch = c[0].frame_pitch;
-        P.su = c[1].base; P.sv = c[n_planes - 1].base;                     // paired: sv = su, not read
-        P.sc_row_pitch = c[1].row_pitch; P.sc_frame_pitch = c[1].frame_pitch;
-        int64_t row, frame;
-        Oy.target(lo, P.L.out, P.L.out_row_pitch, P.L.out_frame_pitch);
-        Ou.target(lo, P.ou, P.oc_row_pitch, P.oc_frame_pitch);
-        P.ov = P.ou;
-        if (!paired) Ov.target(lo, P.ov, row, frame);                      // the same pitches as u
+        Sp.chunk(c, P.L.src.frames, P.su, P.sv, P.L.src.row_pitch, P.L.src.frame_pitch, P.sc_row_pitch, P.sc_frame_pitch);
+        O.target(lo, P.L.out, P.ou, P.ov, P.L.out_row_pitch, P.L.out_frame_pitch, P.oc_row_pitch, P.oc_frame_pitch);
         uy_launch(P, m, st);
       },
-      [&](int64_t lo, int64_t m, hipStream_t st) {
-        Oy.fetch(lo, m, st);
-        Ou.fetch(spread ? 0 : lo, m, st);                                  // spread: every chunk lands at the start of h_u, h_v
-        Ov.fetch(spread ? 0 : lo, m, st);
-      },
-      [&](int64_t lo, int64_t m) {
-        if (!spread) return;
-        for (int64_t f = 0; f < m; ++f)
-          for (int64_t j = 0; j < och; ++j) {
-            const uint8_t *su = h_u.data() + (f * och + j) * ocw, *sv = h_v.data() + (f * och + j) * ocw;
-            uint8_t *du = D.u + (lo + f) * D.c_frame_pitch + j * D.c_row_pitch, *dv = D.v + (lo + f) * D.c_frame_pitch + j * D.c_row_pitch;
-            for (int64_t i = 0; i < ocw; ++i) { du[2 * i] = su[i]; dv[2 * i] = sv[i]; }
-          }
-      });
+      [&](int64_t lo, int64_t m, hipStream_t st) { O.fetch(lo, m, st); }, [&](int64_t lo, int64_t m) { O.done(lo, m); });
   return SBA_OK;
 }
 

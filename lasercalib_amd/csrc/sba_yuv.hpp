@@ -11,10 +11,9 @@
 // luma and chroma are aligned independently, so every one of these accesses chooses its width from its ADDRESS (cv_load16,
 // cv_store16 of sba_convert.hpp, ty_store8 here).  Blocks cut by the right edge and the last row of an odd height take the
 // byte path (ty_edge).  Padding -- and with c_step = 2 the byte between two samples of a plane of its own -- is never written.
-// The host side stages host frames chunk by chunk through two device buffers and host planes through one packed buffer each,
-// in the order frames_in_chunks (sba_frames.hpp) documents.
+// The host side stages host frames chunk by chunk through two device buffers and host planes through one packed buffer each
+// (YuvOutput, sba_frames.hpp), in the order frames_in_chunks (sba_frames.hpp) documents.
 #pragma once
-#include <vector>
 #include "sba_convert.hpp"
 
 namespace sba_detect {
@@ -203,63 +202,32 @@ inline void ty_launch(const TyParams& P, int in, int chroma, int64_t nf, hipStre
 }
 
 // Arguments are checked by the caller (sba_api.hip).  Chunks and staging of the source are those of sba_frames.hpp
-// (frames_per_chunk on the larger side when one of them is host memory, frames_in_chunks); every written plane is a
-// FrameOutput: the luma plane, then ONE plane of 2 ceil(width / 2) bytes a row when u and v are the two halves of an
-// interleaved plane whose rows hold all of them (NV12, NV21), else two planes.  Host planes of their own with c_step = 2 are
-// the one layout a pitched copy cannot write without touching the bytes in between: the kernel writes them packed, they are
-// fetched into a packed host buffer of a chunk and spread from there by the host once the chunk is drained.  Which chunk or
-// buffer a frame passes through does not enter its arithmetic.
+// (frames_per_chunk on the larger side when one of them is host memory, frames_in_chunks); the planes are written through a
+// YuvOutput of that file.  Which chunk or buffer a frame passes through does not enter its arithmetic.
 inline int to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
-                       int64_t frame_pitch, uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_row_pitch, int64_t y_frame_pitch,
-                       int64_t c_row_pitch, int64_t c_frame_pitch, int32_t c_step, const sba_rgb_matrix& M, const sba_to_yuv_opts& o) {
+                       int64_t frame_pitch, const sba_yuv_planes& out, const sba_rgb_matrix& M, const sba_to_yuv_opts& o) {
   if (n_frames == 0 || height == 0 || width == 0) return SBA_OK;
   HIPCHK(hipSetDevice(device));
-  const int64_t cw = (width + 1) / 2, ch = (height + 1) / 2;
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
-  // two planes one byte apart are written as one only when its rows hold all their 2 cw bytes without overlapping the next row
-  const int mode = c_step == 1 ? CV_PLANAR : c_row_pitch < 2 * cw ? CV_STEP2 : v == u + 1 ? CV_UV : u == v + 1 ? CV_VU : CV_STEP2;
-  const bool paired = mode == CV_UV || mode == CV_VU, spread = mode == CV_STEP2 && !out_dev;
+  YuvOutput O(out, height, width, out_dev);
   TyParams P{};
-  P.height = height; P.width = width;
-  P.c_mode = spread ? CV_PLANAR : mode;
-  P.c_step = spread ? 1 : c_step;
+  P.height = height; P.width = width; P.c_mode = O.mode; P.c_step = O.c_step;
   P.yc = (1 << 19) + (M.y_offset << 20);
   P.cry = M.cry; P.cgy = M.cgy; P.cby = M.cby; P.cru = M.cru; P.cgu = M.cgu; P.cbu = M.cbu; P.crv = M.crv; P.cgv = M.cgv; P.cbv = M.cbv;
 
-  const int64_t in_row = (int64_t)width * channels, c_row = paired ? 2 * cw : cw;   // bytes of a row as a pitched copy moves it
-  const int64_t out_tight = (int64_t)width * height + (paired ? 1 : 2) * c_row * ch;
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(in_row * height, out_tight));
-  std::vector<uint8_t> h_u, h_v;                                          // spread: the packed planes of a chunk on the host
-  if (spread) { h_u.resize((size_t)(chunk * cw * ch)); h_v.resize((size_t)(chunk * cw * ch)); }
-  FrameOutput Oy(y, y_row_pitch, y_frame_pitch, width, height, out_dev, chunk);
-  FrameOutput Ou(spread ? h_u.data() : mode == CV_VU ? v : u, spread ? cw : c_row_pitch, spread ? cw * ch : c_frame_pitch, c_row, ch, out_dev, chunk);
-  FrameOutput Ov(spread ? h_v.data() : v, spread ? cw : c_row_pitch, spread ? cw * ch : c_frame_pitch, c_row, paired ? 0 : ch, out_dev, chunk);
+  const int64_t in_row = (int64_t)width * channels;
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(in_row * height, O.tight));
+  O.alloc(chunk);
   const FramePlane plane{frames, row_pitch, frame_pitch, in_row, height};
   const int in = channels == 1 ? TY_GRAY : o.in_format;
   frames_in_chunks(
       &plane, 1, n_frames, in_dev, chunk,
       [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {
         P.src = c->base; P.row_pitch = c->row_pitch; P.frame_pitch = c->frame_pitch;
-        int64_t row, frame;
-        Oy.target(lo, P.y, P.y_row_pitch, P.y_frame_pitch);
-        Ou.target(lo, P.u, P.c_row_pitch, P.c_frame_pitch);
-        if (!paired) Ov.target(lo, P.v, row, frame);                       // the same pitches as u
+        O.target(lo, P.y, P.u, P.v, P.y_row_pitch, P.y_frame_pitch, P.c_row_pitch, P.c_frame_pitch);
         ty_launch(P, in, o.chroma, m, st);
       },
-      [&](int64_t lo, int64_t m, hipStream_t st) {
-        Oy.fetch(lo, m, st);
-        Ou.fetch(spread ? 0 : lo, m, st);                                  // spread: every chunk lands at the start of h_u, h_v
-        Ov.fetch(spread ? 0 : lo, m, st);
-      },
-      [&](int64_t lo, int64_t m) {
-        if (!spread) return;
-        for (int64_t f = 0; f < m; ++f)
-          for (int64_t j = 0; j < ch; ++j) {
-            const uint8_t *su = h_u.data() + (f * ch + j) * cw, *sv = h_v.data() + (f * ch + j) * cw;
-            uint8_t *du = u + (lo + f) * c_frame_pitch + j * c_row_pitch, *dv = v + (lo + f) * c_frame_pitch + j * c_row_pitch;
-            for (int64_t i = 0; i < cw; ++i) { du[2 * i] = su[i]; dv[2 * i] = sv[i]; }
-          }
-      });
+      [&](int64_t lo, int64_t m, hipStream_t st) { O.fetch(lo, m, st); }, [&](int64_t lo, int64_t m) { O.done(lo, m); });
   return SBA_OK;
 }
 

@@ -183,7 +183,7 @@ def undistort_frames(frames, lens, new_camera_matrix=None, out_size=None, interp
         pix = str(out_pixel_format).lower()
         if pix not in _native.YUV_FORMATS:
             raise ValueError(f"out_pixel_format must be one of {_native.YUV_FORMATS}, not {out_pixel_format!r}")
-        m = _rgb_matrix(out_matrix)
+        m = _matrix(out_matrix, RgbMatrix)
         if out is None:
             out = _native.yuv_planes_alloc(pix, B, h, w, tensor, device)
         L = _native._yuv_layout(out, pix, device)
@@ -285,24 +285,69 @@ def optimal_new_camera_matrix(lens, image_size, alpha, new_size=None):
     return K_new, roi
 
 
-class YuvMatrix:
+class _IntMatrix:
+    """What :class:`YuvMatrix` and :class:`RgbMatrix` share: integer coefficients times 2^SHIFT named by ``__slots__``, checked
+    against the bound of the C entry point (``_in_bound``, worded by ``_BOUND``); ``_COUNT`` and ``_A`` word the other errors,
+    ``_OPENCV`` is the table of the preset "bt601"."""
+
+    __slots__ = ()
+    SHIFT = 20
+
+    def _set(self, *vals):
+        name = type(self).__name__
+        if any(int(v) != v for v in vals):
+            raise ValueError(f"{name}: the {self._COUNT} values must be integers, got {vals}")
+        for slot, v in zip(self.__slots__, vals):
+            setattr(self, slot, int(v))
+        if not type(self)._in_bound(self.as_tuple()):
+            raise ValueError(f"{name}{self.as_tuple()}: {self._BOUND}")
+
+    @classmethod
+    def preset(cls, name):
+        """"bt601": OpenCV's table for this direction (limited range, three-decimal constants); "bt709", "bt601-full",
+        "bt709-full": ``from_standard``."""
+        key = str(name).lower()
+        if key == "bt601":
+            return cls(*cls._OPENCV)
+        if key in ("bt709", "bt601-full", "bt709-full"):
+            kr, kb = (0.299, 0.114) if key.startswith("bt601") else (0.2126, 0.0722)
+            return cls.from_standard(kr, kb, full_range=key.endswith("-full"))
+        raise ValueError(f"unknown matrix {name!r}: one of 'bt601', 'bt709', 'bt601-full', 'bt709-full' or {cls._A} {cls.__name__}")
+
+    def as_tuple(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def __repr__(self):
+        return type(self).__name__ + "(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.__slots__) + ")"
+
+
+def _matrix(matrix, cls):
+    """The integers of a matrix of class ``cls``, of a preset's name or of a sequence of as many integers."""
+    if isinstance(matrix, cls):
+        return matrix.as_tuple()
+    return (cls.preset(matrix) if isinstance(matrix, str) else cls(*matrix)).as_tuple()
+
+
+class YuvMatrix(_IntMatrix):
     """The six integers of sba_convert_frames' rule (include/sba_hip.h), coefficients times 2^20:
     ``l = max(Y - y_offset, 0) cy``, ``R = l + cvr v``, ``G = l + cug u + cvg v``, ``B = l + cub u`` with u = U - 128,
     v = V - 128, each sum rounded by ``(s + 2^19) >> 20`` and clipped to 0..255.  The kernel knows nothing of standards:
-    ``from_standard`` and the presets compute the integers here, on the host."""
+    ``from_standard`` and the presets ("bt601" is the table of OpenCV's ``cvtColor(COLOR_YUV2BGR_NV12 / _I420)``) compute the
+    integers here, on the host."""
 
     __slots__ = ("y_offset", "cy", "cvr", "cug", "cvg", "cub")
-    SHIFT = 20
+    _COUNT, _A, _OPENCV, _in_bound = "six", "a", _native.YUV_BT601, staticmethod(_native.yuv_matrix_in_bound)
+    _BOUND = ("y_offset must be in 0..255 and 255 |cy| + 128 (|a| + |b|) + 2^19 below 2^31 "
+              "for the chroma coefficients a, b of every output row (the bound under which the sums fit 32 bits)")
 
     def __init__(self, y_offset, cy, cvr, cug, cvg, cub):
-        vals = (y_offset, cy, cvr, cug, cvg, cub)
-        if any(int(v) != v for v in vals):
-            raise ValueError(f"YuvMatrix: the six values must be integers, got {vals}")
-        for name, v in zip(self.__slots__, vals):
-            setattr(self, name, int(v))
-        if not _native.yuv_matrix_in_bound(self.as_tuple()):
-            raise ValueError(f"YuvMatrix{self.as_tuple()}: y_offset must be in 0..255 and 255 |cy| + 128 (|a| + |b|) + 2^19 below 2^31 "
-                             "for the chroma coefficients a, b of every output row (the bound under which the sums fit 32 bits)")
+        self._set(y_offset, cy, cvr, cug, cvg, cub)
 
     @classmethod
     def from_standard(cls, kr, kb, full_range=False):
@@ -318,39 +363,6 @@ class YuvMatrix:
         coeff = (sy, 2.0 * (1.0 - kr) * sc, -2.0 * kb * (1.0 - kb) / kg * sc, -2.0 * kr * (1.0 - kr) / kg * sc, 2.0 * (1.0 - kb) * sc)
         return cls(0 if full_range else 16, *(int(round(c * (1 << cls.SHIFT))) for c in coeff))
 
-    @classmethod
-    def preset(cls, name):
-        """"bt601": the table of OpenCV's ``cvtColor(COLOR_YUV2BGR_NV12 / _I420)`` (limited range, three-decimal constants);
-        "bt709", "bt601-full", "bt709-full": ``from_standard``."""
-        key = str(name).lower()
-        if key == "bt601":
-            return cls(*_native.YUV_BT601)
-        if key in ("bt709", "bt601-full", "bt709-full"):
-            kr, kb = (0.299, 0.114) if key.startswith("bt601") else (0.2126, 0.0722)
-            return cls.from_standard(kr, kb, full_range=key.endswith("-full"))
-        raise ValueError(f"unknown matrix {name!r}: one of 'bt601', 'bt709', 'bt601-full', 'bt709-full' or a YuvMatrix")
-
-    def as_tuple(self):
-        return tuple(getattr(self, n) for n in self.__slots__)
-
-    def __eq__(self, other):
-        return isinstance(other, YuvMatrix) and self.as_tuple() == other.as_tuple()
-
-    def __hash__(self):
-        return hash(self.as_tuple())
-
-    def __repr__(self):
-        return "YuvMatrix(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.__slots__) + ")"
-
-
-def _matrix(matrix):
-    """The six integers of a YuvMatrix, a preset's name or a sequence of six integers."""
-    if isinstance(matrix, YuvMatrix):
-        return matrix.as_tuple()
-    if isinstance(matrix, str):
-        return YuvMatrix.preset(matrix).as_tuple()
-    return YuvMatrix(*matrix).as_tuple()
-
 
 def convert_frames(frames, pixel_format, out_format="bgr", matrix="bt601", out=None, chunk_frames=0, device=0):
     """What a video decoder produces -- 8-bit YUV 4:2:0 -- into what the rest of the library reads, on the GPU
@@ -364,28 +376,24 @@ def convert_frames(frames, pixel_format, out_format="bgr", matrix="bt601", out=N
     detectors and the background model (``channel=0``).  ``matrix``: "bt601" (OpenCV's table, limited range), "bt709",
     "bt601-full", "bt709-full" or a :class:`YuvMatrix`.  Chroma is taken from the nearest sample, as OpenCV does.  The result is
     a numpy array for numpy frames and a device tensor for tensors, or ``out`` (either kind, any row and frame strides)."""
-    return _native.convert_frames(frames, pixel_format, out_format=out_format, matrix=_matrix(matrix), out=out,
+    return _native.convert_frames(frames, pixel_format, out_format=out_format, matrix=_matrix(matrix, YuvMatrix), out=out,
                                   chunk_frames=chunk_frames, device=device)
 
 
-class RgbMatrix:
+class RgbMatrix(_IntMatrix):
     """The ten integers of sba_frames_to_yuv's rule (include/sba_hip.h), coefficients times 2^20: ``Y = cry R + cgy G + cby B``
     plus ``y_offset``, ``U = cru R' + cgu G' + cbu B'`` plus 128, ``V = crv R' + cgv G' + cbv B'`` plus 128, each sum rounded by
     ``(s + 2^19) >> 20`` and clipped to 0..255.  The mirror of :class:`YuvMatrix`: the kernel knows nothing of standards,
-    ``from_standard`` and the presets compute the integers here, on the host."""
+    ``from_standard`` and the presets ("bt601" is the table of OpenCV's ``cvtColor(COLOR_BGR2YUV_I420)``) compute the integers
+    here, on the host."""
 
     __slots__ = ("y_offset", "cry", "cgy", "cby", "cru", "cgu", "cbu", "crv", "cgv", "cbv")
-    SHIFT = 20
+    _COUNT, _A, _OPENCV, _in_bound = "ten", "an", _native.RGB_BT601, staticmethod(_native.rgb_matrix_in_bound)
+    _BOUND = ("y_offset must be in 0..255 and 255 (|a| + |b| + |c|) below 2^28 for every "
+              "row (a, b, c) (the bound under which the sums fit 32 bits)")
 
     def __init__(self, y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv):
-        vals = (y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv)
-        if any(int(v) != v for v in vals):
-            raise ValueError(f"RgbMatrix: the ten values must be integers, got {vals}")
-        for name, v in zip(self.__slots__, vals):
-            setattr(self, name, int(v))
-        if not _native.rgb_matrix_in_bound(self.as_tuple()):
-            raise ValueError(f"RgbMatrix{self.as_tuple()}: y_offset must be in 0..255 and 255 (|a| + |b| + |c|) below 2^28 for every "
-                             "row (a, b, c) (the bound under which the sums fit 32 bits)")
+        self._set(y_offset, cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv)
 
     @classmethod
     def from_standard(cls, kr, kb, full_range=False):
@@ -403,39 +411,6 @@ class RgbMatrix:
         coeff = (kr * sy, kg * sy, kb * sy, -kr * su, -kg * su, (1.0 - kb) * su, (1.0 - kr) * sv, -kg * sv, -kb * sv)
         return cls(0 if full_range else 16, *(int(round(c * (1 << cls.SHIFT))) for c in coeff))
 
-    @classmethod
-    def preset(cls, name):
-        """"bt601": the table of OpenCV's ``cvtColor(COLOR_BGR2YUV_I420)`` (limited range, three-decimal constants); "bt709",
-        "bt601-full", "bt709-full": ``from_standard``."""
-        key = str(name).lower()
-        if key == "bt601":
-            return cls(*_native.RGB_BT601)
-        if key in ("bt709", "bt601-full", "bt709-full"):
-            kr, kb = (0.299, 0.114) if key.startswith("bt601") else (0.2126, 0.0722)
-            return cls.from_standard(kr, kb, full_range=key.endswith("-full"))
-        raise ValueError(f"unknown matrix {name!r}: one of 'bt601', 'bt709', 'bt601-full', 'bt709-full' or an RgbMatrix")
-
-    def as_tuple(self):
-        return tuple(getattr(self, n) for n in self.__slots__)
-
-    def __eq__(self, other):
-        return isinstance(other, RgbMatrix) and self.as_tuple() == other.as_tuple()
-
-    def __hash__(self):
-        return hash(self.as_tuple())
-
-    def __repr__(self):
-        return "RgbMatrix(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.__slots__) + ")"
-
-
-def _rgb_matrix(matrix):
-    """The ten integers of an RgbMatrix, a preset's name or a sequence of ten integers."""
-    if isinstance(matrix, RgbMatrix):
-        return matrix.as_tuple()
-    if isinstance(matrix, str):
-        return RgbMatrix.preset(matrix).as_tuple()
-    return RgbMatrix(*matrix).as_tuple()
-
 
 def frames_to_yuv(frames, pixel_format="nv12", in_format="bgr", matrix="bt601", chroma="nearest", out=None, chunk_frames=0, device=0):
     """What the rest of the library produces -- BGR / RGB frames or one plane -- into what a video encoder takes, 8-bit YUV
@@ -451,7 +426,7 @@ def frames_to_yuv(frames, pixel_format="nv12", in_format="bgr", matrix="bt601", 
     else the tuple of planes in the format's order -- ``(y, uv)`` with uv (B, ceil(H / 2), ceil(W / 2), 2), or ``(y, u, v)``
     (yv12: ``(y, v, u)``); or ``out``, a stacked array or such a tuple, numpy or tensors on ``device`` whatever side the frames
     are on, with any strides :func:`convert_frames` reads: what lies between the samples is left untouched."""
-    return _native.frames_to_yuv(frames, pixel_format, in_format=in_format, matrix=_rgb_matrix(matrix), chroma=chroma, out=out,
+    return _native.frames_to_yuv(frames, pixel_format, in_format=in_format, matrix=_matrix(matrix, RgbMatrix), chroma=chroma, out=out,
                                  chunk_frames=chunk_frames, device=device)
 
 
@@ -466,7 +441,7 @@ def planes_in_chunks(frames, pixel_format, matrix, channel, chunk_frames, device
     if channel not in (0, 1, 2):
         raise ValueError(f"with a pixel_format, channel names a plane of BGR: 0, 1 or 2, not {channel!r}")
     L = _native._yuv_layout(frames, pixel_format, device)
-    m = _matrix(matrix)
+    m = _matrix(matrix, YuvMatrix)
     step = int(chunk_frames) if chunk_frames > 0 else max(1, CONVERT_CHUNK_BYTES // max(1, L.height * L.width))
     for lo in range(0, max(L.n_frames, 1), step):
         hi = min(lo + step, L.n_frames)
@@ -527,7 +502,7 @@ def resize_frames(frames, factor, gray=False, channel_order="bgr", out=None, chu
     if pixel_format is None:
         return _native.resize_frames(frames, fx, fy, gray_w=w, out=out, chunk_frames=chunk_frames, device=device)
     L = _native._yuv_layout(frames, pixel_format, device)
-    m = _matrix(matrix)
+    m = _matrix(matrix, YuvMatrix)
     shape = (L.n_frames, L.height // fy, L.width // fx) + (() if w is not None else (3,))
     if out is None:
         if L.tensor:

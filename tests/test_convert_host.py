@@ -249,8 +249,8 @@ def test_python_arguments_are_checked_before_the_library_is_needed():
     with pytest.raises(ValueError, match="channel"):
         list(imaging.planes_in_chunks(np.zeros((1, 3, 2), np.uint8), "nv12", "bt601", 3, 0, 0))
     with pytest.raises(ValueError):
-        imaging._matrix((16, 8421504, 0, 0, 0, 0))
-    assert imaging._matrix("BT601") == BT601 and imaging._matrix(list(BT601)) == BT601
+        imaging._matrix((16, 8421504, 0, 0, 0, 0), imaging.YuvMatrix)
+    assert imaging._matrix("BT601", imaging.YuvMatrix) == BT601 and imaging._matrix(list(BT601), imaging.YuvMatrix) == BT601
 
 
 # ----------------------------------------------------------------------------- OpenCV, where it is installed

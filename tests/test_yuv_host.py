@@ -258,7 +258,7 @@ def test_python_arguments_are_checked_before_the_library_is_needed(monkeypatch):
         imaging.undistort_frames(bgr, lens, out_pixel_format="yuyv")
     with pytest.raises(ValueError, match="out holds"):
         imaging.undistort_frames(bgr, lens, out_pixel_format="nv12", out=np.zeros((2, 9, 6), np.uint8))
-    assert imaging._rgb_matrix("BT601") == BT601 and imaging._rgb_matrix(list(BT601)) == BT601
+    assert imaging._matrix("BT601", imaging.RgbMatrix) == BT601 and imaging._matrix(list(BT601), imaging.RgbMatrix) == BT601
 
 
 # ----------------------------------------------------------------------------- OpenCV, where it is installed
