@@ -1031,6 +1031,43 @@ int sba_undistort_yuv(int device, const sba_yuv_planes* src, int64_t n_frames, i
                       uint8_t* flags_out /*out_height*out_width, host, or NULL*/,
                       int32_t* map_out /*out_height*out_width*2, host, or NULL*/);
 
+/* ---------------------------------------------------------------- per-frame value histograms
+ * Every frame function above takes a fixed threshold (50 in sba_detect_dots, 70 in sba_detect_blobs); the reference finds it
+ * by hand (lasercalib/get_video_pixel.py: play the video, click a pixel, read its value).  Which threshold leaves one dot of
+ * a sane size in most frames, how many pixels are saturated, where the camera's dark level lies: all of that follows from
+ * the 256-bin histogram of the thresholded channel of every frame, which sba_frame_histograms returns in one pass over the
+ * bytes.  The number of pixels above t -- the n of sba_detect_dots at threshold t -- is its reversed cumulative sum, for all
+ * 256 values of t at once.  Stateless: no handle.  Frames are described as for sba_detect_dots (8-bit, channels 1, 3 or 4
+ * interleaved, any base, any pitches, host memory or with frames_on_device device memory read in place).
+ *
+ * Per frame f:
+ *   hist[f][v] = the number of pixels inside both regions whose byte `channel` equals v, v = 0..255.  The regions are those of
+ *                sba_dot_opts: the rectangle clipped to the frame, the circle tested in integers.  Width and height are at
+ *                most 16384, so a count is at most 2^28 and fits 32 bits.  A frame with an empty region has 256 zeros.
+ *   total[v]  += the sum over the call's frames of hist[f][v], in unsigned 64 bits.  total is ADDED TO: the caller preloads it,
+ *                with zeros for a fresh video, and a video can be streamed through any number of calls, in any order and
+ *                with any chunking, and ends with the same bits.  The histograms of a chunk are summed on the device into
+ *                256 64-bit counters, which are added to the host array once, at the end of the call.
+ * Both output pointers are host memory and either may be NULL.  With both NULL, or n_frames = 0, the call returns SBA_OK and
+ * writes nothing.  Host frames are staged through two device buffers of chunk_frames frames as for sba_detect_dots; device
+ * memory does not grow with n_frames.
+ * Errors (checked before any device work, text "sba_frame_histograms: ..." in sba_last_error(NULL)), no output byte written:
+ *   SBA_ERR_INVALID for null frames with n_frames > 0, channels not 1, 3 or 4, channel outside 0..channels-1, a negative size,
+ *   row_pitch < width channels, frame_pitch < height row_pitch; SBA_ERR_UNSUPPORTED for width or height above 16384.
+ * Determinism: integer additions only (integer atomics merge the workgroups' counts); two calls return the same bits. */
+typedef struct {
+  int32_t channel;          /* interleaved channel that is counted; default 1                      */
+  int32_t frames_on_device; /* 1: `frames` is a device pointer on `device`, read in place          */
+  int32_t roi_rect[4];      /* as sba_dot_opts                                                      */
+  int32_t roi_circle[3];    /* as sba_dot_opts                                                      */
+  int32_t chunk_frames;     /* host frames: frames per staged chunk; <= 0 = library default        */
+  int32_t reserved[4];
+} sba_hist_opts;
+int sba_frame_histograms(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width,
+                         int32_t channels /*1, 3 or 4*/, int64_t row_pitch, int64_t frame_pitch,
+                         const sba_hist_opts* opts /*NULL: {1, 0, ...0}*/,
+                         uint32_t* hist /*n_frames*256 or NULL*/, uint64_t* total /*256, ADDED TO, or NULL*/);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

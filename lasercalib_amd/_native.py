@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = (
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
     "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames", "sba_resize_frames",
-    "sba_frames_to_yuv", "sba_undistort_yuv",
+    "sba_frames_to_yuv", "sba_undistort_yuv", "sba_frame_histograms",
 )
 
 
@@ -115,6 +115,11 @@ class DotOpts(C.Structure):
 
 DOT_OK, DOT_NONE, DOT_TOO_SMALL, DOT_TOO_LARGE, DOT_SPREAD = 0, 1, 2, 3, 4       # sba_dot_status
 DOT_MAX_DIM = 16384
+
+
+class HistOpts(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("frames_on_device", C.c_int32), ("roi_rect", C.c_int32 * 4), ("roi_circle", C.c_int32 * 3),
+                ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class BlobOpts(C.Structure):
@@ -541,6 +546,8 @@ def load():
                                         C.POINTER(RgbMatrix), C.POINTER(ToYuvOpts)]),
         "sba_undistort_yuv": (C.c_int, [C.c_int, C.POINTER(YuvPlanes), C.c_int64, C.c_int32, C.c_int32, C.POINTER(LensStruct), dp, C.c_int32,
                                         C.c_int32, C.POINTER(YuvPlanes), C.POINTER(UndistortYuvOpts), C.c_void_p, C.c_void_p]),
+        "sba_frame_histograms": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                           C.POINTER(HistOpts), C.c_void_p, C.c_void_p]),
         "sba_resize_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_int64, C.c_int64, C.POINTER(ResizeOpts), C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
@@ -762,10 +769,13 @@ def _frames_out(out, shapes, on_device, device, like_frames=None):
 
 
 def _frame_args(frames, device, opts, channel, threshold, chunk_frames, roi_rect, roi_circle):
-    """What detect_dots and detect_blobs do alike with their frames: fills the fields both options structs have and returns
-    (B, H, W, leading arguments of the C call -- device, pointer, sizes, pitches, options --, the object that owns the pixels)."""
+    """What detect_dots, detect_blobs and frame_histograms do alike with their frames: fills the fields their options structs
+    share (``threshold`` None: the struct has none) and returns (B, H, W, leading arguments of the C call -- device, pointer,
+    sizes, pitches, options --, the object that owns the pixels)."""
     tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
-    opts.channel, opts.threshold, opts.frames_on_device, opts.chunk_frames = int(channel), int(threshold), 1 if tensor else 0, int(chunk_frames)
+    opts.channel, opts.frames_on_device, opts.chunk_frames = int(channel), 1 if tensor else 0, int(chunk_frames)
+    if threshold is not None:
+        opts.threshold = int(threshold)
     if roi_rect is not None:
         opts.roi_rect = (C.c_int32 * 4)(*(int(v) for v in roi_rect))
     if roi_circle is not None:
@@ -791,6 +801,26 @@ def detect_dots(frames, threshold=50, channel=1, min_area=0, max_area=0, max_ext
     centroid, status = np.full((B, 4), np.nan), np.full(B, DOT_NONE, np.int32)
     _check(lib.sba_detect_dots(*args, sums.ctypes.data, box.ctypes.data, centroid.ctypes.data, status.ctypes.data))
     return LaserDots(sums, box, centroid, status)
+
+
+def frame_histograms(frames, channel=1, roi_rect=None, roi_circle=None, total=None, want_hist=True, chunk_frames=0, device=0):
+    """256-bin histograms of byte ``channel`` of a batch of frames (sba_frame_histograms, include/sba_hip.h) -> (hist, total).
+
+    ``frames``, ``roi_rect``, ``roi_circle`` and ``chunk_frames`` as for ``detect_dots``.  ``hist`` is (B, 256) uint32, one row
+    per frame, or None with ``want_hist=False``; ``total`` is (256,) uint64: the sum of the rows added to the ``total`` handed
+    in (None: zeros), which is not written -- a video streams through any number of calls by passing each result on."""
+    lib = load()
+    opts = HistOpts()
+    B, _H, _W, args, _keep = _frame_args(frames, device, opts, channel, None, chunk_frames, roi_rect, roi_circle)
+    hist = np.zeros((B, 256), np.uint32) if want_hist else None
+    if total is None:
+        total = np.zeros(256, np.uint64)
+    else:
+        total = np.array(total, dtype=np.uint64)
+        if total.shape != (256,):
+            raise ValueError(f"total must hold 256 counts, got the shape {total.shape}")
+    _check(lib.sba_frame_histograms(*args, None if hist is None else hist.ctypes.data, total.ctypes.data))
+    return hist, total
 
 
 def detect_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=4, max_blobs=BLOB_DEFAULT_BLOBS, min_area=0,

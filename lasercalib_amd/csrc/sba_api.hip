@@ -40,6 +40,8 @@ int sba_to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t
 int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,
                            const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
                            const sba_undistort_yuv_opts& opts, uint8_t* flags_out, int32_t* map_out);
+int sba_hist_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
+                  int64_t frame_pitch, const sba_hist_opts& opts, uint32_t* hist, uint64_t* total);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -674,6 +676,22 @@ int sba_undistort_yuv(int device, const sba_yuv_planes* src, int64_t n_frames, i
   if (rc) return rc;
   return guarded(nullptr, [&] {
     return sba_undistort_yuv_call(device, *src, n_frames, height, width, *lens, new_k, out_height, out_width, out, o, flags_out, map_out);
+  });
+}
+
+int sba_frame_histograms(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                         int64_t row_pitch, int64_t frame_pitch, const sba_hist_opts* opts, uint32_t* hist, uint64_t* total) {
+  const char* fn = "sba_frame_histograms";
+  sba_hist_opts o{};
+  o.channel = 1;
+  if (opts) o = *opts;
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, 0);
+  // up to 16384 x 16384 a frame's count fits 32 bits: at most 2^28 pixels fall into one bin
+  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch,
+                                     " (the bound under which a count fits 32 bits)");
+  if (rc || n_frames == 0 || (!hist && !total)) return rc;
+  return guarded(nullptr, [&] {
+    return sba_hist_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, hist, total);
   });
 }
 

@@ -1,8 +1,9 @@
 // sba_detect.hip -- the kernels that work on video frames: the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
 // connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp), the
 // conversion of decoder frames (sba_convert.hpp), its way back to encoder frames (sba_yuv.hpp), the area-averaged previews
-// (sba_resize.hpp) and the undistortion of YUV 4:2:0 frames plane by plane (sba_undistort_yuv.hpp).  They do not depend on the
-// engine's camera model, so they are compiled once, in a translation unit of their own.
+// (sba_resize.hpp), the undistortion of YUV 4:2:0 frames plane by plane (sba_undistort_yuv.hpp) and the per-frame value
+// histograms (sba_hist.hpp).  They do not depend on the engine's camera model, so they are compiled once, in a translation
+// unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
 #include "sba_background.hpp"
@@ -10,6 +11,7 @@
 #include "sba_yuv.hpp"
 #include "sba_resize.hpp"
 #include "sba_undistort_yuv.hpp"
+#include "sba_hist.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -68,4 +70,9 @@ int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_fram
                            const sba_undistort_yuv_opts& opts, uint8_t* flags_out, int32_t* map_out) {
   return sba_detect::undistort_yuv_call(device, src, n_frames, height, width, lens, new_k, out_height, out_width, out, opts, flags_out,
                                         map_out);
+}
+
+int sba_hist_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
+                  int64_t frame_pitch, const sba_hist_opts& opts, uint32_t* hist, uint64_t* total) {
+  return sba_detect::hist_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, opts, hist, total);
 }

@@ -19,6 +19,10 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
   out, in one call and without a colour matrix (sba_undistort_yuv)
 * :func:`resize_frames`, :func:`mosaic` -- previews: ``cv2.resize(frame, size, interpolation=cv2.INTER_AREA)`` at an integer factor
   and ``cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)`` for a batch (sba_resize_frames), and the cameras of a rig side by side in one canvas
+* :func:`frame_histograms`, :class:`FrameHistograms` -- the 256-bin histogram of the detectors' channel of every frame
+  (sba_frame_histograms) and what follows from it: the pixels above every threshold at once, saturation, the dark level, Otsu's
+  threshold, and the threshold that leaves a dot of a sane size in most frames -- what the reference finds by clicking pixels
+  (``lasercalib/get_video_pixel.py``)
 
 Sizes are ``(width, height)``, as in OpenCV.  Pixels follow the rule written out in include/sba_hip.h: a float64 model, the
 source position on a 1/32-pixel grid, integer bilinear weights.  That is OpenCV's scheme, but OpenCV rounds its weight table to
@@ -34,7 +38,7 @@ from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE
 SBA_UNDIST_OUTSIDE, SBA_UNDIST_FOLDED, SBA_UNDIST_RANGE = UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE
 
 __all__ = ["Lens", "undistort_frames", "undistort_yuv", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
-           "YuvMatrix", "convert_frames", "RgbMatrix", "frames_to_yuv", "resize_frames", "mosaic", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
+           "YuvMatrix", "convert_frames", "RgbMatrix", "frames_to_yuv", "resize_frames", "mosaic", "frame_histograms", "FrameHistograms", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
 
 
 class Lens:
@@ -564,6 +568,115 @@ def mosaic(batches, factor, columns=None, gap=0, fill=0, gray=False, on_device=F
     for b, (h, wd), (x, y) in zip(batches, sizes, origins):
         _native.resize_frames(b, fx, fy, gray_w=w, out=canvas[:, y:y + h, x:x + wd], device=device)
     return canvas, origins
+
+
+class FrameHistograms:
+    """Result of :func:`frame_histograms`: ``hist`` (B, 256) uint32, one row per frame, or None when only the total was asked
+    for, and ``total`` (256,) uint64, the sum over every frame counted so far.  The methods are exact integer arithmetic on the
+    host and return one entry per frame; without ``hist`` they treat ``total`` as the one row there is."""
+
+    def __init__(self, hist, total):
+        self.hist, self.total = hist, total
+
+    def _rows(self):
+        """(B, 256) int64 counts; a total beyond 2^63 does not occur (2^28 pixels a frame)."""
+        return (self.total[None] if self.hist is None else self.hist).astype(np.int64)
+
+    def count_above(self):
+        """(B, 256) int64: entry [f, t] is the number of pixels with value > t -- the ``n`` of ``find_laser_dots(threshold=t)``."""
+        h = self._rows()
+        return h.sum(axis=1, keepdims=True) - np.cumsum(h, axis=1)
+
+    def n_saturated(self):
+        """(B,) the pixels with the value 255: the weighted centroid of a dot that holds some is biased."""
+        return self._rows()[:, 255]
+
+    def vmax(self):
+        """(B,) the largest value present, -1 for an empty region."""
+        h = self._rows()
+        return np.where(h.any(axis=1), 255 - np.argmax(h[:, ::-1] > 0, axis=1), -1)
+
+    def vmin(self):
+        """(B,) the smallest value present, -1 for an empty region."""
+        h = self._rows()
+        return np.where(h.any(axis=1), np.argmax(h > 0, axis=1), -1)
+
+    def percentile(self, q):
+        """(B,) the smallest v whose cumulative count -- the pixels with value <= v -- reaches ceil(q n / 100) of the frame's n
+        pixels, taken exactly (q as the fraction it is); -1 when n = 0.  q = 0 asks for a count of 0 and gives 0."""
+        from fractions import Fraction
+        if not 0 <= q <= 100:
+            raise ValueError(f"q must be within 0..100, got {q}")
+        cum = np.cumsum(self._rows(), axis=1)
+        out = np.full(cum.shape[0], -1, np.int64)
+        for f, c in enumerate(cum):
+            n = int(c[-1])
+            if n:
+                need = Fraction(q) * n / 100
+                out[f] = np.searchsorted(c, -((-need.numerator) // need.denominator), side="left")
+        return out
+
+    def otsu(self):
+        """(B,) Otsu's threshold: the t that maximises the between-class variance of the classes value <= t and value > t,
+        (s0 N - S n0)^2 / (n0 (N - n0)) with n0, s0 the count and the sum of the values up to t and N, S those of the frame,
+        compared as exact fractions of integers; the lowest t on ties (a frame of one value: 0); -1 for an empty region."""
+        h = self._rows().astype(object)
+        n0, s0 = np.cumsum(h, axis=1), np.cumsum(h * np.arange(256).astype(object), axis=1)
+        N, S = n0[:, -1:], s0[:, -1:]
+        num, den = (s0 * N - S * n0) ** 2, n0 * (N - n0)
+        den[den == 0] = 1                                     # a class is empty: the numerator is 0 there
+        best, bn, bd = np.zeros(h.shape[0], np.int64), num[:, 0], den[:, 0]
+        for t in range(1, 256):
+            better = num[:, t] * bd > bn * den[:, t]
+            best[better.astype(bool)] = t
+            bn, bd = np.where(better, num[:, t], bn), np.where(better, den[:, t], bd)
+        best[(N[:, 0] == 0).astype(bool)] = -1
+        return best
+
+    def threshold_table(self, min_area, max_area):
+        """(256,) int64: for every threshold t the number of frames with min_area <= count_above[f, t] <= max_area."""
+        above = self.count_above()
+        return ((above >= int(min_area)) & (above <= int(max_area))).sum(axis=0).astype(np.int64)
+
+    def suggest_threshold(self, min_area, max_area):
+        """The middle, rounded down, of the longest run of thresholds on which ``threshold_table`` attains its maximum -- the
+        lowest such run on ties --, or None when no threshold leaves a dot of that size in any frame."""
+        table = self.threshold_table(min_area, max_area)
+        if table.size == 0 or table.max() == 0:
+            return None
+        at_max = np.concatenate([[False], table == table.max(), [False]])
+        edges = np.flatnonzero(at_max[1:] != at_max[:-1])     # starts and ends (exclusive) of the runs, in turn
+        starts, ends = edges[::2], edges[1::2]
+        k = int(np.argmax(ends - starts))                     # the first of the longest
+        return int((starts[k] + ends[k] - 1) // 2)
+
+
+def frame_histograms(frames, channel=1, roi_rect=None, roi_circle=None, per_frame=True, total=None, chunk_frames=0, device=0,
+                     background=None, pixel_format=None, matrix="bt601") -> FrameHistograms:
+    """The 256-bin histogram of byte ``channel`` of every frame of a batch inside ``roi_rect`` and ``roi_circle``
+    (sba_frame_histograms) -> :class:`FrameHistograms`.  Everything is as for ``feature_detection.find_laser_dots`` -- the
+    frames (numpy or a tensor on the device), the regions, ``background=`` (the static light is gated out first) and
+    ``pixel_format=`` / ``matrix`` (decoder YUV 4:2:0, converted to the plane ``channel`` names) -- so the histogram is taken of
+    exactly the plane that detector would threshold.  ``per_frame=False`` returns only the running total, for whole videos;
+    ``total=`` (a (256,) array or a previous result) is continued, not written."""
+    from . import feature_detection as fd
+    total = total.total if isinstance(total, FrameHistograms) else total
+    if background is None and pixel_format is None:
+        return FrameHistograms(*_native.frame_histograms(frames, channel=channel, roi_rect=roi_rect, roi_circle=roi_circle, total=total,
+                                                         want_hist=per_frame, chunk_frames=chunk_frames, device=device))
+    running = [total]
+
+    def count(clean):
+        hist, running[0] = _native.frame_histograms(clean, channel=0, roi_rect=roi_rect, roi_circle=roi_circle, total=running[0],
+                                                    want_hist=per_frame, device=device)
+        return FrameHistograms(hist, None)
+
+    def make(hist):
+        return FrameHistograms(hist, running[0])
+
+    if pixel_format is not None:
+        return fd._from_decoder_frames(frames, pixel_format, matrix, background, channel, chunk_frames, device, count, ("hist",), make)
+    return fd._without_background(frames, background, channel, chunk_frames, device, count, ("hist",), make)
 
 
 class BackgroundModel:
