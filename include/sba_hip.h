@@ -716,7 +716,8 @@ int sba_detect_blobs(int device, const uint8_t* frames, int64_t n_frames, int32_
  * sba_detect_dots; SBA_ERR_INVALID for a NULL lens or new_k, a lens or new_k value that is not finite, a focal length that is
  * not > 0, an output size outside 0..16384, output pitches that are too small, an unknown interpolation, a border value outside
  * 0..255, and out == NULL with n_frames > 0 when neither diagnostic is asked for. */
-typedef enum { SBA_UNDIST_OUTSIDE = 1, SBA_UNDIST_FOLDED = 2, SBA_UNDIST_RANGE = 4 } sba_undistort_flag;
+typedef enum { SBA_UNDIST_OUTSIDE = 1, SBA_UNDIST_FOLDED = 2, SBA_UNDIST_RANGE = 4,
+               SBA_WARP_BEHIND = 8 /* sba_warp_frames only */ } sba_undistort_flag;
 typedef struct { double fx, fy, cx, cy, k1, k2, p1, p2, k3; } sba_lens;   /* OpenCV's 5-coefficient model; the library's
                                                                              11-/13-column rows are fx = fy = f, k3 = 0 */
 typedef struct {
@@ -733,6 +734,36 @@ int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, in
                          const sba_undistort_opts* opts /*NULL: all zero*/, uint8_t* out /*or NULL*/,
                          uint8_t* flags_out /*out_height*out_width, host, or NULL*/,
                          int32_t* map_out /*out_height*out_width*2, host, or NULL*/);
+
+/* ---------------------------------------------------------------- plane views and virtual cameras from video frames
+ * sba_undistort_frames resamples into a pinhole camera that shares the source's axes.  sba_warp_frames puts a projective front
+ * end in its place: destination pixel (x, y) goes through the 3 x 3 matrix m (row-major) into normalised camera coordinates and
+ * from there through the lens.  With m = [R u | R v | R o + t] for a camera X_cam = R X + t the destination is the metric view of
+ * the world plane o + x u + y v (the floor, a laser plane); with m = R_v^T K_new^-1 it is a virtual camera K_new rotated by R_v
+ * (rectification, levelling; K_new may have skew); with m = K_new^-1 it is sba_undistort_frames restated.  Stateless.  Frames,
+ * output, diagnostics, chunking and sba_undistort_opts are exactly those of sba_undistort_frames.
+ *
+ * The rule per destination pixel (x, y) -- this is the function's definition.  Every operation is ONE IEEE float64 operation, in
+ * this order, never contracted into a fused multiply-add; the divisions are the correctly rounded ones.
+ *   X = (m00*x + m01*y) + m02;  Y = (m10*x + m11*y) + m12;  Z = (m20*x + m21*y) + m22
+ *   front = Z > 0                                                            (false for NaN)
+ *   xn = front ? X / Z : 0;  yn = front ? Y / Z : 0
+ *   x2 = xn*xn; ... rad, xd, yd, sx, sy, dp, j00, j11, j01, det: the rule of sba_undistort_frames from "x2 = xn*xn" on, unchanged
+ *   in_range = front && sx > -32768 && sx < 32768 && sy > -32768 && sy < 32768
+ *   qx, qy, the taps, nearest, the border and the value: the rule of sba_undistort_frames, unchanged
+ *   flags: OUTSIDE, FOLDED and RANGE as there, plus 8 BEHIND (!front): SBA_WARP_BEHIND of sba_undistort_flag
+ * A pixel behind the camera therefore carries BEHIND | RANGE | OUTSIDE and never FOLDED (at xn = yn = 0 the determinant is 1),
+ * its map entry is (0, 0) and every channel of it is border_value.
+ * Mathematically m is defined up to a positive factor.  Bit for bit the result is invariant only under powers of two (which
+ * scale X, Y and Z exactly, short of overflow and underflow): another factor rounds the three sums differently.
+ * Errors, all checked before any device work (text "sba_warp_frames: ..." in sba_last_error(NULL)), out left untouched: those of
+ * sba_undistort_frames without the ones of new_k, and SBA_ERR_INVALID for a NULL m or a value of m that is not finite. */
+int sba_warp_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                    int64_t row_pitch, int64_t frame_pitch, const sba_lens* lens, const double* m /*9, row-major*/,
+                    int32_t out_height, int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch,
+                    const sba_undistort_opts* opts /*NULL: all zero*/, uint8_t* out /*or NULL*/,
+                    uint8_t* flags_out /*out_height*out_width, host, or NULL*/,
+                    int32_t* map_out /*out_height*out_width*2, host, or NULL*/);
 
 /* ---------------------------------------------------------------- static light in video frames: learn it, take it out
  * The detectors above inherit the reference's precondition that the laser dot is the only bright spot of a frame.  A status

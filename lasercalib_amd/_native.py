@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = (
     "sba_triangulate", "sba_align", "sba_apply_similarity", "sba_reproj_stats",
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
     "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames", "sba_resize_frames",
-    "sba_frames_to_yuv", "sba_undistort_yuv", "sba_frame_histograms",
+    "sba_frames_to_yuv", "sba_undistort_yuv", "sba_frame_histograms", "sba_warp_frames",
 )
 
 
@@ -146,6 +146,7 @@ class UndistortOpts(C.Structure):
 
 
 UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE = 1, 2, 4                       # sba_undistort_flag
+WARP_BEHIND = 8                                                            # sba_undistort_flag, set by sba_warp_frames only
 UNDIST_INTERPOLATION = {"linear": 0, "nearest": 1}                         # sba_undistort_opts.interpolation
 # the tile of destination pixels one workgroup owns (csrc/sba_undistort.hpp), for the tests that straddle it
 UNDIST_TILE_ROWS, UNDIST_TILE_COLS = 4, 256
@@ -533,6 +534,9 @@ def load():
         "sba_undistort_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                            C.POINTER(LensStruct), dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                            C.POINTER(UndistortOpts), C.c_void_p, C.c_void_p, C.c_void_p]),
+        "sba_warp_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                      C.POINTER(LensStruct), dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                      C.POINTER(UndistortOpts), C.c_void_p, C.c_void_p, C.c_void_p]),
         "sba_background_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                                 C.POINTER(BgAccumulateOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint64)]),
@@ -852,15 +856,10 @@ def detect_blobs(frames, threshold=70, channel=1, dilate_radius=1, close_radius=
     return LaserBlobs(ncomp, blobs, accepted, centroid, status, mask, labels)
 
 
-def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", border_value=0, out=None, want_flags=False,
-                     want_map=False, want_frames=True, chunk_frames=0, device=0, out_on_device=None):
-    """sba_undistort_frames (include/sba_hip.h): ``frames`` as for ``detect_dots`` (numpy, or a torch tensor on ``device`` read in
-    place) resampled through the lens ``lens9`` = (fx, fy, cx, cy, k1, k2, p1, p2, k3) into the pinhole image of ``new_k`` = (fxn,
-    fyn, cxn, cyn) of ``out_size`` = (height, width).  Returns (out, flags, map): ``out`` is a numpy array for numpy frames and a
-    device tensor for tensor frames -- allocated here, or the caller's ``out``, which may be a strided view with contiguous
-    pixels --, None with ``want_frames=False`` (then no frame is read); ``flags`` (height, width) uint8 and ``map`` (height, width, 2) int32 are numpy
-    or None.  ``out_on_device`` True / False puts the result on that side whatever side the frames are on (an ``out`` may then be of
-    either kind); None keeps it with the frames.  ``lasercalib_amd.imaging`` is the public face of this call."""
+def _through_lens(symbol, model, frames, lens9, out_size, interpolation, border_value, out, want_flags, want_map, want_frames,
+                  chunk_frames, device, out_on_device):
+    """What undistort_frames and warp_frames share -- everything but the front end of the model: ``symbol`` is the entry point,
+    ``model`` its float64 values (new_k or m)."""
     lib = load()
     if interpolation not in UNDIST_INTERPOLATION:
         raise ValueError(f"interpolation must be one of {sorted(UNDIST_INTERPOLATION)}, not {interpolation!r}")
@@ -871,7 +870,6 @@ def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", bor
     if not (0 <= Ho <= DOT_MAX_DIM and 0 <= Wo <= DOT_MAX_DIM):
         raise ValueError(f"out_size must be (height, width) within 0..{DOT_MAX_DIM}, got {(Ho, Wo)}")
     lens = LensStruct(*(float(v) for v in lens9))
-    nk = np.ascontiguousarray([float(v) for v in new_k], dtype=np.float64)
     opts = UndistortOpts()
     opts.frames_on_device = 1 if tensor else 0
     opts.interpolation, opts.border_value, opts.chunk_frames = UNDIST_INTERPOLATION[interpolation], int(border_value), int(chunk_frames)
@@ -889,10 +887,36 @@ def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", bor
         opts.out_on_device = 1 if out_tensor else 0
     flags = np.zeros((Ho, Wo), np.uint8) if want_flags else None
     qmap = np.zeros((Ho, Wo, 2), np.int32) if want_map else None
-    _check(lib.sba_undistort_frames(device, C.c_void_p(_synced(device, frames, also=bool(opts.out_on_device))), B, H, W, Cn, sr, sf, C.byref(lens), _dptr(nk), Ho, Wo, osr, osf,
+    _check(getattr(lib, symbol)(device, C.c_void_p(_synced(device, frames, also=bool(opts.out_on_device))), B, H, W, Cn, sr, sf, C.byref(lens), _dptr(model), Ho, Wo, osr, osf,
                                     C.byref(opts), C.c_void_p(optr), None if flags is None else flags.ctypes.data,
                                     None if qmap is None else qmap.ctypes.data))
     return out, flags, qmap
+
+
+def undistort_frames(frames, lens9, new_k, out_size, interpolation="linear", border_value=0, out=None, want_flags=False,
+                     want_map=False, want_frames=True, chunk_frames=0, device=0, out_on_device=None):
+    """sba_undistort_frames (include/sba_hip.h): ``frames`` as for ``detect_dots`` (numpy, or a torch tensor on ``device`` read in
+    place) resampled through the lens ``lens9`` = (fx, fy, cx, cy, k1, k2, p1, p2, k3) into the pinhole image of ``new_k`` = (fxn,
+    fyn, cxn, cyn) of ``out_size`` = (height, width).  Returns (out, flags, map): ``out`` is a numpy array for numpy frames and a
+    device tensor for tensor frames -- allocated here, or the caller's ``out``, which may be a strided view with contiguous
+    pixels --, None with ``want_frames=False`` (then no frame is read); ``flags`` (height, width) uint8 and ``map`` (height, width, 2) int32 are numpy
+    or None.  ``out_on_device`` True / False puts the result on that side whatever side the frames are on (an ``out`` may then be of
+    either kind); None keeps it with the frames.  ``lasercalib_amd.imaging`` is the public face of this call."""
+    nk = np.ascontiguousarray([float(v) for v in new_k], dtype=np.float64)
+    return _through_lens("sba_undistort_frames", nk, frames, lens9, out_size, interpolation, border_value, out, want_flags, want_map,
+                         want_frames, chunk_frames, device, out_on_device)
+
+
+def warp_frames(frames, lens9, m, out_size, interpolation="linear", border_value=0, out=None, want_flags=False, want_map=False,
+                want_frames=True, chunk_frames=0, device=0, out_on_device=None):
+    """sba_warp_frames (include/sba_hip.h): as ``undistort_frames`` with the 3 x 3 matrix ``m`` (nine values, row-major) in place of
+    ``new_k``: destination pixel (x, y) is the normalised camera position m (x, y, 1) taken through the lens ``lens9``.  ``flags``
+    may also hold WARP_BEHIND.  ``lasercalib_amd.imaging`` is the public face of this call."""
+    m = np.ascontiguousarray(m, dtype=np.float64).reshape(-1)
+    if m.shape != (9,):
+        raise ValueError(f"m must hold the nine values of a 3 x 3 matrix, got {m.shape[0]}")
+    return _through_lens("sba_warp_frames", m, frames, lens9, out_size, interpolation, border_value, out, want_flags, want_map,
+                         want_frames, chunk_frames, device, out_on_device)
 
 
 def _plane(name, a, itemsize, H, W, device, writeable):

@@ -42,6 +42,9 @@ int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_fram
                            const sba_undistort_yuv_opts& opts, uint8_t* flags_out, int32_t* map_out);
 int sba_hist_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
                   int64_t frame_pitch, const sba_hist_opts& opts, uint32_t* hist, uint64_t* total);
+int sba_warp_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
+                  int64_t frame_pitch, const sba_lens& lens, const double* m, int32_t out_height, int32_t out_width, int64_t out_row_pitch,
+                  int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out, uint8_t* flags_out, int32_t* map_out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -525,6 +528,33 @@ int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, in
   return guarded(nullptr, [&] {
     return sba_undistort_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, *lens, new_k, out_height, out_width,
                               out_row_pitch, out_frame_pitch, o, out, flags_out, map_out);
+  });
+}
+
+int sba_warp_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                    int64_t row_pitch, int64_t frame_pitch, const sba_lens* lens, const double* m, int32_t out_height, int32_t out_width,
+                    int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts* opts, uint8_t* out, uint8_t* flags_out,
+                    int32_t* map_out) {
+  const char* fn = "sba_warp_frames";
+  sba_undistort_opts o{};
+  if (opts) o = *opts;
+  static const double unit_k[4] = {1.0, 1.0, 0.0, 0.0};      // the call has no new_k: the matrix takes its place
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
+  if (!rc) rc = lens_invalid(fn, lens, unit_k);
+  if (rc) return rc;
+  if (!m) return detect_invalid(fn, "null m");
+  for (int k = 0; k < 9; ++k) if (!std::isfinite(m[k])) return detect_invalid(fn, "a value of m is not finite");
+  if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
+  if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
+  if (o.border_value < 0 || o.border_value > 255) return detect_invalid(fn, "border_value must be in 0..255");
+  if (!out && n_frames > 0 && !flags_out && !map_out) return detect_invalid(fn, "null out and no diagnostic asked for");
+  if (out) rc = out_pitch_invalid(fn, n_frames, out_height, (int64_t)out_width * channels, out_row_pitch, out_frame_pitch,
+                                  "out_row_pitch is smaller than out_width * channels", "out_height");
+  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc) return rc;
+  return guarded(nullptr, [&] {
+    return sba_warp_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, *lens, m, out_height, out_width,
+                         out_row_pitch, out_frame_pitch, o, out, flags_out, map_out);
   });
 }
 

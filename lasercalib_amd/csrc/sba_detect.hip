@@ -1,8 +1,8 @@
 // sba_detect.hip -- the kernels that work on video frames: the laser-dot detectors (sba_detect.hpp: moments; sba_blobs.hpp:
 // connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp), the
 // conversion of decoder frames (sba_convert.hpp), its way back to encoder frames (sba_yuv.hpp), the area-averaged previews
-// (sba_resize.hpp), the undistortion of YUV 4:2:0 frames plane by plane (sba_undistort_yuv.hpp) and the per-frame value
-// histograms (sba_hist.hpp).  They do not depend on the engine's camera model, so they are compiled once, in a translation
+// (sba_resize.hpp), the undistortion of YUV 4:2:0 frames plane by plane (sba_undistort_yuv.hpp), the per-frame value
+// histograms (sba_hist.hpp) and the plane views and virtual cameras (sba_warp.hpp).  They do not depend on the engine's camera model, so they are compiled once, in a translation
 // unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
@@ -12,6 +12,7 @@
 #include "sba_resize.hpp"
 #include "sba_undistort_yuv.hpp"
 #include "sba_hist.hpp"
+#include "sba_warp.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -75,4 +76,11 @@ int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_fram
 int sba_hist_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
                   int64_t frame_pitch, const sba_hist_opts& opts, uint32_t* hist, uint64_t* total) {
   return sba_detect::hist_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, opts, hist, total);
+}
+
+int sba_warp_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
+                  int64_t frame_pitch, const sba_lens& lens, const double* m, int32_t out_height, int32_t out_width, int64_t out_row_pitch,
+                  int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out, uint8_t* flags_out, int32_t* map_out) {
+  return sba_detect::warp_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, lens, m, out_height, out_width,
+                               out_row_pitch, out_frame_pitch, opts, out, flags_out, map_out);
 }

@@ -34,18 +34,18 @@ struct UdParams {
   int32_t frames_per_group;                  // frames one workgroup walks: grid.z groups share a chunk
 };
 
-// The rule of include/sba_hip.h for destination pixel (x, y): the source position on the 1/32-pixel grid ((0, 0) when it is not
-// in range) and the FOLDED and RANGE flags.
-__device__ __forceinline__ void ud_pixel(const UdParams& P, int x, int y, int& qx, int& qy, int& flags) {
+// The rule of include/sba_hip.h from "x2 = xn*xn" on, at the normalised position (xn, yn): the source position on the 1/32-pixel
+// grid ((0, 0) when it is not in range) and the FOLDED and RANGE flags.  `front` is false where a projective front end
+// (sba_warp.hpp) found the pixel behind the camera: it is then not in range whatever the lens says.
+__device__ __forceinline__ void ud_lens(const UdParams& P, double xn, double yn, bool front, int& qx, int& qy, int& flags) {
 #pragma clang fp contract(off)
-  const double xn = ((double)x - P.cxn) * P.ifx, yn = ((double)y - P.cyn) * P.ify;
   const double x2 = xn * xn, y2 = yn * yn, r2 = x2 + y2, xy = xn * yn;
   double t = r2 * P.k3; t = P.k2 + t; t = r2 * t; t = P.k1 + t; t = r2 * t;
   const double rad = 1.0 + t;
   const double xd = xn * rad + ((2.0 * P.p1) * xy + P.p2 * (r2 + 2.0 * x2));
   const double yd = yn * rad + (P.p1 * (r2 + 2.0 * y2) + (2.0 * P.p2) * xy);
   const double sx = P.fx * xd + P.cx, sy = P.fy * yd + P.cy;
-  const bool in_range = sx > -32768.0 && sx < 32768.0 && sy > -32768.0 && sy < 32768.0;
+  const bool in_range = front && sx > -32768.0 && sx < 32768.0 && sy > -32768.0 && sy < 32768.0;
   qx = in_range ? (int)floor(sx * 32.0 + 0.5) : 0;
   qy = in_range ? (int)floor(sy * 32.0 + 0.5) : 0;
   double dp = r2 * (3.0 * P.k3); dp = (2.0 * P.k2) + dp; dp = r2 * dp; dp = P.k1 + dp;
@@ -55,6 +55,20 @@ __device__ __forceinline__ void ud_pixel(const UdParams& P, int x, int y, int& q
   const double det = j00 * j11 - j01 * j01;
   flags = (det > 0.0 ? 0 : UD_FOLDED) | (in_range ? 0 : UD_RANGE);
 }
+
+// The rule of sba_undistort_frames for destination pixel (x, y): the pinhole front end, then the lens
+__device__ __forceinline__ void ud_pixel(const UdParams& P, int x, int y, int& qx, int& qy, int& flags) {
+#pragma clang fp contract(off)
+  const double xn = ((double)x - P.cxn) * P.ifx, yn = ((double)y - P.cyn) * P.ify;
+  ud_lens(P, xn, yn, true, qx, qy, flags);
+}
+
+// The two kernels below are templates over the parameter block of a call: what differs between the calls that resample through
+// a lens is the front end alone, the function model_pixel(Params, x, y, qx, qy, flags) found by the type of the block, and
+// ud_base(Params) is the UdParams inside it.  sba_undistort_frames: UdParams itself and ud_pixel.
+__host__ __device__ __forceinline__ const UdParams& ud_base(const UdParams& P) { return P; }
+__host__ __device__ __forceinline__ UdParams& ud_base(UdParams& P) { return P; }
+__device__ __forceinline__ void model_pixel(const UdParams& P, int x, int y, int& qx, int& qy, int& flags) { ud_pixel(P, x, y, qx, qy, flags); }
 
 // What the resampling keeps of a pixel: a byte offset `off` into a frame of C channels and
 //   tap = ax | ay << 5 | read << 10 | outside << 14 | left_second << 15 | right_first << 16 | row_step << 17
@@ -86,7 +100,9 @@ __device__ __forceinline__ void ud_taps(const UdParams& P, int C, int qx, int qy
 }
 
 // grid over the destination pixels, one thread each; flags and map are packed rows of out_width
-__global__ void __launch_bounds__(256) k_undistort_geometry(const UdParams P, int channels, uint8_t* __restrict__ flags, int2* __restrict__ map) {
+template <class Params>
+__global__ void __launch_bounds__(256) k_undistort_geometry(const Params M, int channels, uint8_t* __restrict__ flags, int2* __restrict__ map) {
+  const UdParams& P = ud_base(M);
   const int n = P.out_height * P.out_width;                               // <= 16384^2
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -94,7 +110,7 @@ __global__ void __launch_bounds__(256) k_undistort_geometry(const UdParams P, in
   int qx, qy, fl;
   int64_t off;
   uint32_t tap;
-  ud_pixel(P, x, y, qx, qy, fl);
+  model_pixel(M, x, y, qx, qy, fl);
   ud_taps(P, channels, qx, qy, !(fl & UD_RANGE), off, tap);
   if (flags) flags[i] = (uint8_t)(fl | (tap >> 14 & 1u ? UD_OUTSIDE : 0));
   if (map) map[i] = make_int2(qx, qy);
@@ -116,8 +132,9 @@ __device__ __forceinline__ void ud_load2(const uint8_t* p, uint32_t& a, uint32_t
 }
 
 // grid (tiles in x, tiles in y, frame groups), DOT_THREADS threads; P.src.frames and P.out point at the chunk's first frame
-template <int C>
-__global__ void __launch_bounds__(DOT_THREADS) k_undistort(const UdParams P, int n_frames) {
+template <int C, class Params>
+__global__ void __launch_bounds__(DOT_THREADS) k_undistort(const Params M, int n_frames) {
+  const UdParams& P = ud_base(M);
   __shared__ __attribute__((aligned(16))) uint8_t s_row[2][UD_TILE_ROWS][UD_ROW_LDS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int y = (int)blockIdx.y * UD_TILE_ROWS + wave, x0 = (int)blockIdx.x * UD_TILE_COLS;
@@ -131,7 +148,7 @@ __global__ void __launch_bounds__(DOT_THREADS) k_undistort(const UdParams P, int
     off[j] = 0; tap[j] = 0;                                               // a pixel beyond the image reads nothing
     if (row_on && x < P.out_width) {
       int qx, qy, fl;
-      ud_pixel(P, x, y, qx, qy, fl);
+      model_pixel(M, x, y, qx, qy, fl);
       ud_taps(P, C, qx, qy, !(fl & UD_RANGE), off[j], tap[j]);
     }
   }
@@ -197,16 +214,18 @@ __global__ void __launch_bounds__(DOT_THREADS) k_undistort(const UdParams P, int
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-inline void ud_launch(const UdParams& P, int channels, int64_t nf, hipStream_t st) {
+template <class Params>
+inline void ud_launch(const Params& M, int channels, int64_t nf, hipStream_t st) {
+  const UdParams& P = ud_base(M);
   const unsigned gx = (unsigned)((P.out_width + UD_TILE_COLS - 1) / UD_TILE_COLS), gy = (unsigned)((P.out_height + UD_TILE_ROWS - 1) / UD_TILE_ROWS);
   // about 2048 workgroups where the frames allow it; which workgroup takes a frame does not change its bytes
   const int64_t groups = std::max<int64_t>(1, std::min<int64_t>(nf, 2048 / ((int64_t)gx * gy)));
-  UdParams Q = P;
-  Q.frames_per_group = (int32_t)((nf + groups - 1) / groups);
-  const dim3 grid(gx, gy, (unsigned)((nf + Q.frames_per_group - 1) / Q.frames_per_group));
-  if (channels == 1) hipLaunchKernelGGL(k_undistort<1>, grid, dim3(DOT_THREADS), 0, st, Q, (int)nf);
-  else if (channels == 3) hipLaunchKernelGGL(k_undistort<3>, grid, dim3(DOT_THREADS), 0, st, Q, (int)nf);
-  else hipLaunchKernelGGL(k_undistort<4>, grid, dim3(DOT_THREADS), 0, st, Q, (int)nf);
+  Params Q = M;
+  const int32_t fpg = ud_base(Q).frames_per_group = (int32_t)((nf + groups - 1) / groups);
+  const dim3 grid(gx, gy, (unsigned)((nf + fpg - 1) / fpg));
+  if (channels == 1) hipLaunchKernelGGL((k_undistort<1, Params>), grid, dim3(DOT_THREADS), 0, st, Q, (int)nf);
+  else if (channels == 3) hipLaunchKernelGGL((k_undistort<3, Params>), grid, dim3(DOT_THREADS), 0, st, Q, (int)nf);
+  else hipLaunchKernelGGL((k_undistort<4, Params>), grid, dim3(DOT_THREADS), 0, st, Q, (int)nf);
   HIPCHK(hipGetLastError());
 }
 
@@ -217,15 +236,17 @@ inline void ud_set_lens(UdParams& P, const sba_lens& L, const double* new_k) {
 }
 
 // The diagnostics of a call, once: flags and map of every destination pixel of P into host memory (either may be NULL)
-inline void ud_geometry_out(const UdParams& P, int channels, uint8_t* flags_out, int32_t* map_out) {
+template <class Params>
+inline void ud_geometry_out(const Params& M, int channels, uint8_t* flags_out, int32_t* map_out) {
   if (!flags_out && !map_out) return;
+  const UdParams& P = ud_base(M);
   const int64_t out_px = (int64_t)P.out_height * P.out_width;
   DotStream s;
   DevBuf<uint8_t> d_flags;
   DevBuf<int2> d_map;
   if (flags_out) d_flags.alloc((size_t)out_px);
   if (map_out) d_map.alloc((size_t)out_px);
-  hipLaunchKernelGGL(k_undistort_geometry, dim3((unsigned)((out_px + 255) / 256)), dim3(256), 0, s.s, P, channels, d_flags.p, d_map.p);
+  hipLaunchKernelGGL(k_undistort_geometry<Params>, dim3((unsigned)((out_px + 255) / 256)), dim3(256), 0, s.s, M, channels, d_flags.p, d_map.p);
   HIPCHK(hipGetLastError());
   if (flags_out) HIPCHK(hipMemcpyAsync(flags_out, d_flags.p, (size_t)out_px, hipMemcpyDeviceToHost, s.s));
   if (map_out) HIPCHK(hipMemcpyAsync(map_out, d_map.p, sizeof(int2) * (size_t)out_px, hipMemcpyDeviceToHost, s.s));
@@ -235,19 +256,19 @@ inline void ud_geometry_out(const UdParams& P, int channels, uint8_t* flags_out,
 // Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (frames_per_chunk
 // on the larger of the two sides when one of them is host memory, frames_in_chunks, FrameOutput).  Which chunk, workgroup or
 // buffer a frame passes through does not enter its arithmetic: any chunk_frames gives the same bytes.
-inline int undistort_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                          int64_t row_pitch, int64_t frame_pitch, const sba_lens& L, const double* new_k, int32_t out_height,
-                          int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& o, uint8_t* out,
-                          uint8_t* flags_out, int32_t* map_out) {
+// `M` holds the model of the call (lens and front end); source, output and options are filled in here.
+template <class Params>
+inline int ud_call(Params& M, int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                   int64_t row_pitch, int64_t frame_pitch, int32_t out_height, int32_t out_width, int64_t out_row_pitch,
+                   int64_t out_frame_pitch, const sba_undistort_opts& o, uint8_t* out, uint8_t* flags_out, int32_t* map_out) {
   const int64_t out_px = (int64_t)out_height * out_width;
   if (out_px == 0) return SBA_OK;
   HIPCHK(hipSetDevice(device));
   static const int32_t whole[4] = {0, 0, 0, 0};
-  UdParams P{};
+  UdParams& P = ud_base(M);
   P.src = frame_view(frames, row_pitch, frame_pitch, height, width, 0, 0, whole, whole);
-  ud_set_lens(P, L, new_k);
   P.out_height = out_height; P.out_width = out_width; P.nearest = o.interpolation == 1; P.border = o.border_value;
-  ud_geometry_out(P, channels, flags_out, map_out);
+  ud_geometry_out(M, channels, flags_out, map_out);
   if (n_frames == 0 || !out) return SBA_OK;
 
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
@@ -260,10 +281,20 @@ inline int undistort_call(int device, const uint8_t* frames, int64_t n_frames, i
       [&](const FrameView& V, int64_t lo, int64_t m, hipStream_t st) {
         P.src = V;
         O.target(lo, P.out, P.out_row_pitch, P.out_frame_pitch);
-        ud_launch(P, channels, m, st);
+        ud_launch(M, channels, m, st);
       },
       [&](int64_t lo, int64_t m, hipStream_t st) { O.fetch(lo, m, st); });
   return SBA_OK;
+}
+
+inline int undistort_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                          int64_t row_pitch, int64_t frame_pitch, const sba_lens& L, const double* new_k, int32_t out_height,
+                          int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& o, uint8_t* out,
+                          uint8_t* flags_out, int32_t* map_out) {
+  UdParams P{};
+  ud_set_lens(P, L, new_k);
+  return ud_call(P, device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, out_height, out_width, out_row_pitch,
+                 out_frame_pitch, o, out, flags_out, map_out);
 }
 
 }  // namespace sba_detect

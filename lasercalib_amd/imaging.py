@@ -5,6 +5,9 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
 * :class:`Lens`                        -- OpenCV's 5-coefficient model (fx, fy, cx, cy, k1, k2, p1, p2, k3), from a camera row of
   the bundle adjustment or from a camera matrix and distortion coefficients
 * :func:`undistort_frames`             -- ``cv.undistort`` for a whole batch of frames of one camera, on the GPU
+* :func:`warp_frames`, :func:`plane_view`, :class:`PlaneGrid`, :func:`virtual_camera_matrix`, :func:`plane_mosaic` -- the
+  extrinsics put to use on the pictures (sba_warp_frames): the metric top-down view of the floor or of a laser plane through
+  every calibrated camera, rotated virtual cameras (rectification, levelling), and the views of a rig in one picture
 * :func:`optimal_new_camera_matrix`    -- ``cv.getOptimalNewCameraMatrix``: the camera matrix that keeps only valid pixels
   (alpha = 0), every source pixel (alpha = 1) or a blend; 81 points, on the host
 * :func:`invertible_region`            -- where the distortion model is locally invertible (the FOLDED flag), as a bool image
@@ -33,12 +36,14 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native
-from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE
+from ._native import UNDIST_FOLDED, UNDIST_OUTSIDE, UNDIST_RANGE, WARP_BEHIND
 
 SBA_UNDIST_OUTSIDE, SBA_UNDIST_FOLDED, SBA_UNDIST_RANGE = UNDIST_OUTSIDE, UNDIST_FOLDED, UNDIST_RANGE
+SBA_WARP_BEHIND = WARP_BEHIND
 
 __all__ = ["Lens", "undistort_frames", "undistort_yuv", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
-           "YuvMatrix", "convert_frames", "RgbMatrix", "frames_to_yuv", "resize_frames", "mosaic", "frame_histograms", "FrameHistograms", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE"]
+           "YuvMatrix", "convert_frames", "RgbMatrix", "frames_to_yuv", "resize_frames", "mosaic", "frame_histograms", "FrameHistograms", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE",
+           "warp_frames", "plane_view", "PlaneGrid", "virtual_camera_matrix", "plane_mosaic", "SBA_WARP_BEHIND"]
 
 
 class Lens:
@@ -233,6 +238,174 @@ def undistort_yuv(frames, pixel_format, lens, new_camera_matrix=None, out_size=N
                                              out_pixel_format=out_pixel_format, out=out, want_flags=want_flags, want_map=want_map,
                                              chunk_frames=chunk_frames, device=device)
     return (res, flags, qmap) if (want_flags or want_map) else res
+
+
+def _matrix3(matrix, name="matrix"):
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape != (3, 3) or not np.all(np.isfinite(m)):
+        raise ValueError(f"{name} must be a finite 3 x 3 matrix, got shape {m.shape}")
+    return m
+
+
+def warp_frames(frames, lens, matrix, out_size, interpolation="linear", border_value=0, out=None, want_flags=False, want_map=False,
+                chunk_frames=0, device=0):
+    """The frames of one camera seen through a projective front end (sba_warp_frames, include/sba_hip.h): pixel (x, y) of the
+    result is the normalised camera position ``matrix @ (x, y, 1)`` taken through ``lens``.  ``matrix`` (3 x 3) is defined up
+    to a positive factor; a pixel whose third coordinate is not positive lies behind the camera and holds ``border_value``.
+    :meth:`PlaneGrid.matrix` gives the matrix of a world plane, :func:`virtual_camera_matrix` that of a rotated pinhole camera.
+    Everything else -- ``frames``, ``out_size`` = (width, height), ``interpolation``, ``border_value``, ``out``, ``want_flags``,
+    ``want_map``, ``chunk_frames`` and what is returned -- is as for :func:`undistort_frames`; ``flags`` may also hold
+    SBA_WARP_BEHIND."""
+    lens = _lens(lens)
+    m = _matrix3(matrix)
+    w, h = _size(out_size, "out_size")
+    res, flags, qmap = _native.warp_frames(frames, lens.as_tuple(), m, (h, w), interpolation=interpolation, border_value=border_value,
+                                           out=out, want_flags=want_flags, want_map=want_map, chunk_frames=chunk_frames, device=device)
+    return (res, flags, qmap) if (want_flags or want_map) else res
+
+
+def rodrigues(rvec):
+    """The rotation matrix of a rotation vector, in float64: R = cos I + sin [a]x + (1 - cos) a a^T with a = rvec / |rvec|; the
+    identity for the zero vector.  The library's convention: X_cam = R X + t."""
+    r = np.asarray(rvec, dtype=np.float64).reshape(-1)
+    if r.shape != (3,) or not np.all(np.isfinite(r)):
+        raise ValueError(f"a rotation vector has three finite values, got {r}")
+    angle = np.linalg.norm(r)
+    if angle == 0.0:
+        return np.eye(3)
+    a = r / angle
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.cos(angle) * np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * np.outer(a, a)
+
+
+def _camera(camera):
+    """(lens, R, t) of a camera row of the bundle adjustment (11 or 13 columns) or of a (Lens, R, t) triple."""
+    if isinstance(camera, (tuple, list)) and len(camera) == 3 and isinstance(camera[0], Lens):
+        lens, R, t = camera
+        R, t = _matrix3(R, "R"), np.asarray(t, dtype=np.float64).reshape(-1)
+        if t.shape != (3,) or not np.all(np.isfinite(t)):
+            raise ValueError(f"t must hold three finite values, got {t}")
+        return lens, R, t
+    row = np.asarray(camera, dtype=np.float64).reshape(-1)
+    lens = Lens.from_camera_row(row)
+    return lens, rodrigues(row[:3]), row[3:6].copy()
+
+
+class PlaneGrid:
+    """A regular grid of points on a world plane, the pixels of a plane view: pixel (x, y) is the world point
+    ``origin + x * u_step + y * v_step`` (mm, as the calibration's world), ``size`` = (width, height)."""
+
+    def __init__(self, origin, u_step, v_step, size):
+        vec = [np.asarray(v, dtype=np.float64).reshape(-1) for v in (origin, u_step, v_step)]
+        if any(v.shape != (3,) or not np.all(np.isfinite(v)) for v in vec):
+            raise ValueError("origin, u_step and v_step must each hold three finite values")
+        self.origin, self.u_step, self.v_step = vec
+        if not np.any(np.cross(self.u_step, self.v_step)):
+            raise ValueError("u_step and v_step must span a plane")
+        self.size = _size(size, "size")
+
+    @classmethod
+    def z_plane(cls, z, x_range, y_range, mm_per_pixel):
+        """The plane z = ``z`` over x_range = (x0, x1) and y_range = (y0, y1), half open, at ``mm_per_pixel``: pixel (i, j) is
+        (x0 + i mm, y0 + j mm, z) and there are ceil((x1 - x0) / mm) x ceil((y1 - y0) / mm) of them."""
+        mm = float(mm_per_pixel)
+        (x0, x1), (y0, y1) = (float(v) for v in x_range), (float(v) for v in y_range)
+        if not (mm > 0 and x1 > x0 and y1 > y0 and np.isfinite([mm, x0, x1, y0, y1, float(z)]).all()):
+            raise ValueError("mm_per_pixel must be > 0 and the ranges finite and ascending")
+        w, h = int(np.ceil((x1 - x0) / mm)), int(np.ceil((y1 - y0) / mm))
+        return cls((x0, y0, float(z)), (mm, 0.0, 0.0), (0.0, mm, 0.0), (w, h))
+
+    def world_points(self):
+        """(height, width, 3): the world point of every pixel."""
+        w, h = self.size
+        x, y = np.arange(w, dtype=np.float64)[None, :, None], np.arange(h, dtype=np.float64)[:, None, None]
+        return self.origin + x * self.u_step + y * self.v_step
+
+    def pixel_of(self, world_xyz):
+        """(..., 2): the pixel (x, y), not rounded, of world points (..., 3); a point off the plane counts as its foot on it."""
+        d = np.asarray(world_xyz, dtype=np.float64) - self.origin
+        A = np.stack([self.u_step, self.v_step], axis=1)                     # 3 x 2
+        return d @ np.linalg.pinv(A).T
+
+    def matrix(self, camera):
+        """The matrix of :func:`warp_frames` for this grid seen by ``camera`` (a camera row of 11 or 13 columns, or a
+        ``(Lens, R, t)`` triple): ``[R u_step | R v_step | R origin + t]`` with X_cam = R X + t and Z > 0 in front."""
+        _lens_, R, t = _camera(camera)
+        return np.stack([R @ self.u_step, R @ self.v_step, R @ self.origin + t], axis=1)
+
+
+def plane_view(frames, camera, grid, **kw):
+    """The frames of a calibrated camera resampled onto the world plane of ``grid`` (a :class:`PlaneGrid`): a metric picture
+    of the floor or of a laser plane, in which what lies on the plane lands on the same pixel from every camera.  ``camera``:
+    a camera row of the bundle adjustment (11 or 13 columns) or a ``(Lens, R, t)`` triple with X_cam = R X + t, for cameras read
+    from OpenCV yaml files (``rc_ext``, ``tc_ext``).  Keywords and result as :func:`warp_frames`."""
+    if not isinstance(grid, PlaneGrid):
+        raise ValueError("grid must be a PlaneGrid")
+    lens, _R, _t = _camera(camera)
+    return warp_frames(frames, lens, grid.matrix(camera), grid.size, **kw)
+
+
+def virtual_camera_matrix(new_camera_matrix, rotation=None):
+    """The matrix of :func:`warp_frames` for a virtual pinhole camera K_new at the place of the source camera, turned by
+    ``rotation``: X_virtual = rotation @ X_source, the rectification matrix of ``cv.stereoRectify`` and
+    ``cv.initUndistortRectifyMap`` -> ``rotation.T @ inv(K_new)``.  K_new = [[fx, s, cx], [0, fy, cy], [0, 0, 1]] may have skew; without a rotation the result is
+    :func:`undistort_frames` restated (bit for bit when fx and fy are powers of two)."""
+    K = _matrix3(new_camera_matrix, "new_camera_matrix")
+    if K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1 or not (K[0, 0] > 0 and K[1, 1] > 0):
+        raise ValueError("new_camera_matrix must be [[fx, s, cx], [0, fy, cy], [0, 0, 1]] with fx, fy > 0")
+    a, b, s, cx, cy = 1.0 / K[0, 0], 1.0 / K[1, 1], K[0, 1], K[0, 2], K[1, 2]
+    inv = np.array([[a, -s * a * b, (s * cy * b - cx) * a], [0.0, b, -cy * b], [0.0, 0.0, 1.0]])
+    if rotation is None:
+        return inv
+    R = _matrix3(rotation, "rotation")
+    if np.max(np.abs(R @ R.T - np.eye(3))) > 1e-9 or np.linalg.det(R) < 0:
+        raise ValueError("rotation must be a rotation matrix")
+    return R.T @ inv
+
+
+def plane_mosaic(views, flags, maps, source_sizes, fill=0):
+    """The plane views of the cameras of a rig in one picture -> ``(mosaic, owner)``.
+
+    ``views``: one batch per camera, (B, height, width[, C]) of one shape, numpy arrays or device tensors; ``flags`` and
+    ``maps``: what the calls returned with ``want_flags`` and ``want_map``; ``source_sizes``: (width, height) of every camera's
+    frames.  The owner of a pixel is the camera with flags == 0 there whose source position lies farthest from the edge of its
+    own image -- the integer ``min(qx, 32 (W - 1) - qx, qy, 32 (H - 1) - qy)`` of its map entry --, the lowest index on ties;
+    a pixel nobody owns holds ``fill`` and owner -1.  ``owner`` is (height, width) int32, of the kind of the views.  Nothing is
+    blended: a pixel of the mosaic is a pixel of one view."""
+    n = len(views)
+    if n == 0 or not (len(flags) == len(maps) == len(source_sizes) == n):
+        raise ValueError("views, flags, maps and source_sizes must hold one entry per camera, at least one")
+    fill = int(fill)
+    if not 0 <= fill <= 255:
+        raise ValueError(f"fill must be in 0..255, got {fill}")
+    shape = tuple(views[0].shape)
+    tensor = _native._is_tensor(views[0])
+    if len(shape) not in (3, 4) or any(tuple(v.shape) != shape or _native._is_tensor(v) != tensor for v in views):
+        raise ValueError("every view must be (B, height, width[, C]) of one shape and kind")
+    hw = shape[1:3]
+    best = np.full(hw, np.iinfo(np.int64).min, np.int64)
+    owner = np.full(hw, -1, np.int32)
+    for k in range(n):
+        fl, qm = (a.cpu().numpy() if _native._is_tensor(a) else np.asarray(a) for a in (flags[k], maps[k]))
+        W, H = _size(source_sizes[k], "source_sizes")
+        if fl.shape != hw or qm.shape != hw + (2,):
+            raise ValueError(f"camera {k}: flags {fl.shape} and map {qm.shape} do not fit views of {hw}")
+        qx, qy = qm[..., 0].astype(np.int64), qm[..., 1].astype(np.int64)
+        score = np.minimum(np.minimum(qx, 32 * (W - 1) - qx), np.minimum(qy, 32 * (H - 1) - qy))
+        take = (fl == 0) & ((owner < 0) | (score > best))                   # strictly farther: ties stay with the lower index
+        best[take], owner[take] = score[take], k
+    if tensor:
+        import torch
+        own = torch.from_numpy(owner).to(views[0].device)
+        mask = own.reshape((1,) + hw + (1,) * (len(shape) - 3))
+        mosaic = torch.full(shape, fill, dtype=views[0].dtype, device=views[0].device)
+        for k in range(n):
+            mosaic = torch.where(mask == k, views[k], mosaic)
+        return mosaic, own
+    mosaic = np.full(shape, fill, views[0].dtype)
+    for k in range(n):
+        mosaic[:, owner == k] = np.asarray(views[k])[:, owner == k]
+    return mosaic, owner
 
 
 def invertible_region(lens, new_camera_matrix, size, device=0):
