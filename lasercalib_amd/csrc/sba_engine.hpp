@@ -1355,6 +1355,11 @@ struct Engine : EngineBase {
       hipLaunchKernelGGL((k_sq_trial<T, 2>), dim3(nblk_sq), dim3(PM_BLOCK), lds_cams(), stream, ps_lm(), tsets(), d_state.p, C,
                          uv_pm.p, has_w ? w_pm.p : nullptr, ci_pm.p, pi_pm.p, M, trial_part.p, nblk_sq);
   }
+  // the phase API's trial scalars (a caller that hands lm_decide a scalar array): the same fold of k_sq_trial's partials k_decide does
+  void launch_sq_scalars(double* scal) {
+    if (scal)
+      hipLaunchKernelGGL(k_trial_scalars, dim3(1), dim3(DECIDE_THREADS), 0, stream, trial_part.p, gmax_rd(), nblk_sq, nblk_sq, d_state.p, scal);
+  }
   // cost (0.5 sum rho^2) and max |gradient| from the 16x16 sums of the last squared-variant linearization
   void sq_read(double& cost, double& gmax) {
     const int ng = (opts.mode == SBA_MODE_CAMS_ONLY_SQ) ? C : 1;
@@ -1770,6 +1775,7 @@ struct Engine : EngineBase {
     if (opts.mode == SBA_MODE_TRANSFORM_SQ) {
       hipLaunchKernelGGL(k_sq_solve12, dim3(1), dim3(64), 0, stream, sq_16.p, d_state.p, tsets());
       launch_sq_trial();
+      launch_sq_scalars(scal);
       return SBA_OK;
     }
     if (h_state->free_cams) {
@@ -1903,7 +1909,7 @@ struct Engine : EngineBase {
         hipLaunchKernelGGL(k_point_factor<T>, dim3((N + 255) / 256), dim3(256), 0, stream, V.p, gp.p, D2p.p, d_state.p, N, pfac.p,
                          has_fixed ? pt_fixed_mask.p : (const unsigned char*)nullptr);
     }
-    if (sq_mode()) { launch_sq_trial(); return SBA_OK; }
+    if (sq_mode()) { launch_sq_trial(); launch_sq_scalars(scal); return SBA_OK; }
     prof_begin(KP_BACKSUB);
     launch_backsub_trial();
     prof_end(KP_BACKSUB);
@@ -2012,6 +2018,7 @@ struct Engine : EngineBase {
         rep->cost = cost; rep->initial_cost = initial_cost; rep->optimality = gmax; rep->step_norm = s.step_norm;
         rep->lambda = s.lam; rep->nfev = s.nfev; rep->njev = s.njev; rep->iterations = s.iter; rep->accepted = s.n_accepted;
         rep->status = s.status < 0 ? 0 : s.status;
+        rep->reserved = s.chol_f64_retries;
       }
       lm_active = false;
       return SBA_OK;

@@ -16,6 +16,10 @@ What it pins (tests/test_exact_model_host.py pins this file first; tests/test_gp
   point_step     (V_p + lam diag D_p) dp = -(g_p + W_p^T dc), fixed points exactly zero
   reduced_system S = blockdiag(U_c) - sum W_p V'_p^-1 W_p^T (not damped in the cameras) and rhs = -g_c + sum W_p V'_p^-1 g_p over the
                  free points, V'_p = V_p + lam diag D_p, with d = sqrt(diag U) and the magnitudes of their terms
+  tie_matrix     T of delta_c = T delta_s, the shared-intrinsics unknowns in the order of pySBA.py:313
+  tied_system    S_s = T^T S T, rhs_s = T^T rhs, diagU_s = T^T diagU, g_s = T^T g_c
+  sq_system      the squared-pixel-error variants: rho = w Delta^2, rows J~ = 2 w Delta dDelta/dtheta per camera (cameras only) or
+                 J~ = 2 w Delta (dDelta/dX) (x) [X, 1] (one 3 x 4 affine for all points), H = J~^T J~, g = J~^T rho, cost = 0.5 rho . rho
 About 1 ms per observation (the seven rotations a camera needs are built once per camera).
 """
 from __future__ import annotations
@@ -432,3 +436,103 @@ def reduced_system(Jc, Jp, r, ci, pi, n_cams, n_pts, lam, fixed=None, full_mp=Fa
         rhs[:] = [float(v) for row in acc for v in row]
     S = 0.5 * (S + S.T)
     return dict(S=S.astype(np.float64), S_ld=S, rhs=rhs, d=d, S_mag=S_mag, G=G, share=share)
+
+
+# ----------------------------------------------------------------------------- shared intrinsics (SBA_MODE_SHARED_INTR)
+def tie_matrix(n_cams, ncp):
+    """T (C ncp, n_tied) of zeros and ones, delta_c = T delta_s, written as the reference unpacks its parameter vector (pySBA.py:313,
+    fun_sharedcam): x = [f k1 k2 | 6 extrinsics per camera | the per-camera tail], tail = cx cy, or p1 p2 cx cy with 13 parameters;
+    a camera row is [extrinsics, shared, tail]."""
+    pc = ncp - 9
+    n_tied = 3 + (6 + pc) * n_cams
+    x = np.arange(n_tied)
+    shared, extr, tail = x[:3], x[3:3 + 6 * n_cams].reshape(n_cams, 6), x[3 + 6 * n_cams:].reshape(n_cams, pc)
+    col = np.concatenate((extr, np.tile(shared, (n_cams, 1)), tail), axis=1).ravel()
+    T = np.zeros((n_cams * ncp, n_tied))
+    T[np.arange(n_cams * ncp), col] = 1.0
+    return T
+
+
+def tied_system(T, S_ld, rhs, diagU, gc, full_mp=False):
+    """S_s = T^T S T (np.longdouble from the longdouble S, and rounded once), rhs_s, diagU_s, g_s = T^T of the float64 vectors, summed
+    in longdouble and rounded once.  A tied entry sums at most C^2 entries of S, each below d_i d_j, so the longdouble sum stays below
+    C^2 2^-64 of sum d_i d_j; full_mp sums the same entries in mpmath (tests/test_exact_model_host.py holds the two together)."""
+    L = np.longdouble
+    Tl = T.astype(L)
+    vec = lambda v: (Tl.T @ np.asarray(v, dtype=L).ravel())      # noqa: E731
+    if full_mp:
+        n, nt = T.shape
+        cols = [np.nonzero(T[:, a])[0] for a in range(nt)]
+        Ss = np.zeros((nt, nt), dtype=L)
+        with mp.workdps(SUM_DPS):
+            def mpl(v):
+                hi = float(v)
+                return mp.mpf(hi) + mp.mpf(float(v - L(hi)))
+            Sm = [[mpl(S_ld[i, j]) for j in range(n)] for i in range(n)]
+            for a in range(nt):
+                for b in range(a, nt):
+                    Ss[a, b] = Ss[b, a] = _ld(mp.fsum([Sm[i][j] for i in cols[a] for j in cols[b]]))
+    else:
+        Ss = Tl.T @ np.asarray(S_ld, dtype=L) @ Tl
+        Ss = 0.5 * (Ss + Ss.T)
+    rhs_s, dU_s, g_s = vec(rhs), vec(diagU), vec(gc)
+    return dict(S=Ss.astype(np.float64), S_ld=Ss, rhs=rhs_s.astype(np.float64), rhs_ld=rhs_s, diagU=dU_s.astype(np.float64),
+                g=g_s.astype(np.float64))
+
+
+# ----------------------------------------------------------------------------- the squared-pixel-error variants
+def sq_system(delta, Jc, Jp, w, ci, pi, pts, n_cams, kind, full_mp=False, row_factor=2):
+    """delta (M,2), Jc (M,2,NCP), Jp (M,2,3): the UNWEIGHTED exact pixel error and its derivatives (exact_blocks with w = 1).
+    kind 'cams' (SBA_MODE_CAMS_ONLY_SQ): one group per camera, P = NCP parameters, row J~ = 2 w Delta dDelta/dcam.
+    kind 'affine' (SBA_MODE_TRANSFORM_SQ): one group, P = 12, theta = reshape(3, 4) at the identity, J~[4 a + l] = 2 w Delta dDelta/dX_a [X, 1]_l.
+    rho = w Delta^2 per pixel component.  The rows [J~ | rho] are formed in mpmath; their products are summed in np.longdouble from the
+    longdouble roundings of the rows (each product within 3 x 2^-64 of itself, each sum of R rows within R 2^-64 of h_i h_j by
+    Cauchy-Schwarz); full_mp forms every sum in mpmath.  Returns H (G,P,P), g (G,P), cost, h = sqrt(diag H) (G,P), rho (M,2)."""
+    ci, pi = _indices(ci, pi)
+    M = ci.size
+    wv = _weights(w, M)
+    P = Jc.shape[2] if kind == "cams" else 12
+    G = n_cams if kind == "cams" else 1
+    L = np.longdouble
+    rows_mp = []
+    with mp.workdps(SUM_DPS):
+        for m in range(M):
+            Xh = [_mpf(v) for v in pts[pi[m]]] + [mp.mpf(1)]
+            for k in range(2):
+                d = _mpf(delta[m, k])
+                f = row_factor * _mpf(wv[m]) * d
+                if kind == "cams":
+                    row = [f * _mpf(v) for v in Jc[m, k]]
+                else:
+                    row = [f * _mpf(Jp[m, k, a]) * Xh[l] for a in range(3) for l in range(4)]
+                rows_mp.append(row + [_mpf(wv[m]) * d * d])
+        grp = np.repeat(ci if kind == "cams" else np.zeros(M, np.int64), 2)
+        Q = np.zeros((G, P + 1, P + 1), dtype=L)
+        if full_mp:
+            for g_ in range(G):
+                sel = np.nonzero(grp == g_)[0]
+                for i in range(P + 1):
+                    ri = [rows_mp[r][i] for r in sel]
+                    for j in range(i, P + 1):
+                        Q[g_, i, j] = Q[g_, j, i] = _ld(mp.fdot(ri, [rows_mp[r][j] for r in sel]))
+        else:
+            R = np.array([[_ld(v) for v in row] for row in rows_mp], dtype=L)
+            for g_ in range(G):
+                Rg = R[grp == g_]
+                Q[g_] = Rg.T @ Rg
+        rho = np.array([float(row[-1]) for row in rows_mp]).reshape(M, 2)
+    H = Q[:, :P, :P]
+    cost = 0.5 * np.sum(Q[:, P, P])
+    h = np.sqrt(np.einsum("gii->gi", H)).astype(np.float64)
+    return dict(H=H.astype(np.float64), H_ld=H, g=Q[:, :P, P].astype(np.float64), g_ld=Q[:, :P, P], cost=float(cost), cost_ld=cost,
+                h=np.where(h > 0, h, 1.0), rho=rho)
+
+
+def affine_points(theta, pts):
+    """theta (12,) = reshape(3, 4) applied to [X, 1], in mpmath at the CURRENT precision: a list of rows of mpf (exact_residual takes them)."""
+    th = [_mpf(v) for v in np.ravel(theta)]
+    out = []
+    for X in pts:
+        Xh = [_mpf(v) for v in X] + [mp.mpf(1)]
+        out.append([mp.fdot(th[4 * a:4 * a + 4], Xh) for a in range(3)])
+    return out

@@ -9,6 +9,9 @@ ratios on the cases of tests/test_gpu_exact_model.py are recomputed: they are wh
 (oracle/exact_cases.py: K = 16 x the largest ratio, not below 16), so the constants' origin is executable.  The reference of the reduced camera system (exact_model.reduced_system) is held to
 0.1 eps64 d_i d_j of a full-mpmath evaluation, and numpy's float64 and LAPACK's float32 Cholesky solves of the model's own
 systems are held to the a-priori backward-error bound the GPU file's part (e) uses, with what that bar can see worked out.
+  The last part does the same for the other four modes (tests/test_gpu_exact_variants.py): the tie matrix
+against the reference's unpacking, the tied and the squared-variant sums against full-mpmath evaluations, the model's ratios that set the new K,
+and a planted error for every new bar.
 
 Mutation check of this file (scratch copy): the coefficient 1/30 of a2_s in lm_schur_model.rodrigues_coeffs changed to 1/31
 fails test_numpy_model_per_column_kind[edge11] on the rotation kinds (the cameras below the series switch).
@@ -271,3 +274,152 @@ def test_numpy_cholesky_solves_stay_under_the_a_priori_bound(name):
         bad = q["dc"].ravel().copy()
         bad[k] *= 1.0 + rel
         assert xc.backward_error(q["S"], q["rhs"], damp, bad)[0] > bar
+
+
+# ============================================================================ the other four modes (tests/test_gpu_exact_variants.py)
+def test_tie_matrix_is_the_reference_unpack():
+    """T x is the reference's own unpacking of its shared-intrinsics parameter vector (oracle/sba_oracle.unpack_sharedcam, pySBA.py:313);
+    with 13 parameters the per-camera tail is [p1, p2, cx, cy]."""
+    from oracle import sba_oracle as orc11
+    for C in (1, 5, 16):
+        nt = 3 + 8 * C
+        x = np.arange(nt) + 1.0
+        T = ex.tie_matrix(C, 11)
+        cams, off = orc11.unpack_sharedcam(np.concatenate([x, np.zeros(3)]), C)
+        assert off == nt and T.shape == (11 * C, nt) and np.array_equal((T @ x).reshape(C, 11), cams)
+        assert np.all(T.sum(axis=1) == 1) and np.array_equal(T.sum(axis=0), np.r_[np.full(3, C), np.ones(nt - 3)])
+        nt = 3 + 10 * C
+        x = np.arange(nt) + 1.0
+        cams = (ex.tie_matrix(C, 13) @ x).reshape(C, 13)
+        assert np.array_equal(cams[:, 6:9], np.tile(x[:3], (C, 1))) and np.array_equal(cams[:, :6], x[3:3 + 6 * C].reshape(C, 6))
+        assert np.array_equal(cams[:, 9:], x[3 + 6 * C:].reshape(C, 4))
+
+
+def test_tied_system_against_full_mpmath():
+    """exact_model.tied_system sums T^T S T in np.longdouble; on t5x30 (65 -> 53 unknowns, the shared 3 x 3 block sums 25 entries) it
+    agrees with the same sums in mpmath to 0.1 eps64 of T^T (d d^T) T (observed: 2e-4), the vectors likewise."""
+    E, X = xc.exact("t5x30"), xc.reduced("t5x30")
+    T = ex.tie_matrix(5, 13)
+    A = ex.tied_system(T, X.S_ld, X.rhs, E.diagU, E.gc)
+    F = ex.tied_system(T, X.S_ld, X.rhs, E.diagU, E.gc, full_mp=True)
+    dd = T.T @ np.outer(X.d, X.d) @ T
+    assert A["S"].shape == (53, 53) and np.array_equal(A["S"], A["S"].T)
+    assert np.max(np.abs((A["S_ld"] - F["S_ld"]).astype(np.float64)) / dd) <= 0.1 * EPS64
+    with mp.workdps(ex.SUM_DPS):
+        for key, v, scale in (("rhs", X.rhs, T.T @ xc.rhs_scale("t5x30", EPS64)), ("g", E.gc, T.T @ E.gc_mag.ravel()), ("diagU", E.diagU, T.T @ E.diagU.ravel())):
+            want = np.array([float(mp.fsum([mp.mpf(float(x)) for x in np.ravel(v)[T[:, a] > 0]])) for a in range(53)])
+            assert np.max(np.abs(A[key] - want) / scale) <= EPS64, key          # rounded once: half an ulp of the sum itself
+    t = xc.tied("t5x30")
+    assert np.array_equal(t.S, A["S"]) and np.array_equal(t.g, A["g"])
+
+
+@pytest.mark.parametrize("name,kind", [("edge11", "cams"), ("t5x30", "affine")])
+def test_squared_variant_sums_against_full_mpmath(name, kind):
+    """exact_model.sq_system sums the products of its mpmath rows in np.longdouble; against every sum in mpmath: H to 0.1 eps64 h_i h_j,
+    g and the cost to 0.1 eps64 of their scales (observed: at most 4e-3)."""
+    c = xc.case(name)
+    X = xc.sq_exact(name, kind)
+    F = ex.sq_system(X.delta, X.Jc, X.Jp, c.w, c.ci, c.pi, c.pts, c.C, kind, full_mp=True)
+    g_s, cost_s = xc.sq_scales(name, kind, EPS64)
+    hh = X.h[:, :, None] * X.h[:, None, :]
+    assert X.H.shape == ((6, 11, 11) if kind == "cams" else (1, 12, 12))
+    assert np.max(np.abs((X.H_ld - F["H_ld"]).astype(np.float64)) / hh) <= 0.1 * EPS64
+    assert np.max(np.abs((X.g_ld - F["g_ld"]).astype(np.float64)) / g_s) <= 0.1 * EPS64
+    assert abs(float(X.cost_ld - F["cost_ld"])) / cost_s <= 0.1 * EPS64
+    assert np.max(np.abs(X.H) / hh) <= 1.0 + 4 * EPS64 and np.all(np.abs(X.g) <= g_s * (1 + 4 * EPS64))      # Cauchy-Schwarz; the scale bounds g
+    # rho = w Delta^2 of the UNWEIGHTED pixel error: with the weights of the case, w Delta is the residual of the weighted blocks
+    r = xc._blocks(name)[0]
+    assert np.max(np.abs(c.w[:, None] * X.delta - r) / np.abs(r).max()) <= 4 * EPS64
+    assert np.max(np.abs(X.rho - c.w[:, None] * X.delta ** 2) / X.rho.max()) <= 4 * EPS64
+
+
+_VARIANT_Q = ("dp", "s_cost", "s_pred", "s_dx2", "s_x2", "s_gmax")
+
+
+@pytest.mark.parametrize("name", xc.POINTS_ONLY_CASES)
+def test_numpy_model_of_a_points_only_trial(name):
+    """The model's ratios of a points-only trial (dc = 0) against the recorded MODEL_MAX_VARIANT, and those under the bars K in use."""
+    q = xc.model_quantities(name, mode="points")
+    assert q["rho"] > 0.25 and not np.any(q["dc"]) and np.array_equal(q["cams_new"], xc.case(name).cams)
+    R = xc.ratios(name, {k: q[k] for k in ("dc", "dp", "cams_new", "pts_new", "scal")}, EPS64)
+    assert R["cond"] <= 1e3 and R["fixed_zero"]
+    for k in _VARIANT_Q:
+        assert R[k] <= xc.MODEL_MAX_VARIANT["points"][k] <= xc.K[k], (k, R[k])
+
+
+@pytest.mark.parametrize("name", xc.SHARED_CASES)
+def test_numpy_model_of_a_shared_intrinsics_trial(name):
+    """The model's tied trial: ratios against MODEL_MAX_VARIANT and under K; its ds under the a-priori bound of every route the device
+    takes; and what bar (ii) sees: one term S[f of camera 1, f of camera 2] left out of the sum for S_s[f, f] (one `ib` term of
+    k_tie_system) before the solve misses the f64 bar by 4e7 and more, and the f32 bar by a factor 3.9 .. 5 on d16x24, t18x12 and m9x40;
+    on g24x10 and v34x6 that one term (two cameras with few common points) stays at 0.08 of the f32 bar: the f32 engine's bar sees a
+    wrong tied sum only from about 1e-5 of d_i d_j on."""
+    c = xc.case(name)
+    q = xc.model_quantities(name, mode="shared")
+    assert q["rho"] > 0.25 and np.all(q["dc"][:, 6:9] == q["dc"][0, 6:9])
+    R = xc.ratios(name, {k: q[k] for k in ("S", "rhs", "dc", "dp", "cams_new", "pts_new", "scal")}, EPS64)
+    for k in ("S", "rhs") + _VARIANT_Q:
+        assert R[k] <= xc.MODEL_MAX_VARIANT["shared"][k] <= xc.K[k], (k, R[k])
+    assert R["S"] <= xc.K["S_lin"] / 16.0
+    ds, bwd, own = xc.tied_backward_error(name, q["S"], q["rhs"], q["diagU"], q["dc"])
+    B64, what64, r64 = xc.tied_solve_bound("f64", name)
+    B32, what32, r32 = xc.tied_solve_bound("f32", name)
+    assert np.array_equal(ds, q["ds"]) and bwd <= B64 and own <= 0.01 * B64, (bwd / EPS64, B64 / EPS64)
+    n, nt = c.C * c.ncp, ds.size
+    assert (r64, r32) == {131: ("BLOCKED", "BLOCKED"), 195: ("LL", "LL_F32"), 275: ("BIG_DAG", "BIG_DAG_F32"), 183: ("LL", "LL_F32"),
+                          75: ("BLOCKED", "BLOCKED")}[nt]
+    assert xc.chol_route("f64", n) == {176: "BLOCKED", 264: "BIG_DAG", 374: "BIG_DAG", 234: "LL", 99: "BLOCKED"}[n]
+    T = ex.tie_matrix(c.C, c.ncp)
+    dU = T.T @ q["diagU"].ravel()
+    A = T.T @ q["S"] @ T + np.diag(xc.LAMBDA0 * np.where(dU > 0, dU, 1.0))
+    A[0, 0] -= q["S"][1 * c.ncp + 6, 2 * c.ncp + 6]
+    bad = np.linalg.solve(A, T.T @ q["rhs"])
+    seen = xc.tied_backward_error(name, q["S"], q["rhs"], q["diagU"], (T @ bad).reshape(c.C, c.ncp))[1]
+    print(f"\n[exact] tied model {name}: ds_bwd={bwd / EPS64:.3g} eps64, B64={B64 / EPS64:.4g} eps64, B32={B32 / xc.EPS['f32']:.4g} eps32, one term dropped: {seen / B32:.3g} x B32")
+    assert seen > 1e6 * B64 and (seen > 2 * B32 or name.startswith(("g24x10", "v34x6")))
+
+
+@pytest.mark.parametrize("name", xc.SHARED_GTOL_CASES)
+def test_tied_gradient_maximum_and_what_its_bar_sees(name):
+    """max |g| in the tied unknowns: the model under K / 16; the untied maximum misses the f32 bar by more than a factor 1e3."""
+    q = xc.model_quantities(name, mode="shared")
+    E, t = xc.exact(name), xc.tied(name)
+    assert xc.ratios(name, dict(gmax_tied=q["gmax_tied"]), EPS64)["gmax_tied"] <= xc.K["gmax_tied"] / 16.0
+    assert int(np.argmax(np.abs(t.g))) == 1 and np.max(np.abs(t.g)) > 1.3 * np.max(np.abs(E.gc)) > np.max(np.abs(E.gp))
+    assert xc.ratios(name, dict(gmax_tied=q["gmax"]), xc.EPS["f32"])["gmax_tied"] > 1e3 * xc.K["gmax_tied"]
+
+
+_SQ_Q = {"cams": ("H", "g", "cost", "lam", "res", "tcost"), "affine": ("cost", "lam", "res", "tcost")}
+
+
+@pytest.mark.parametrize("name,kind", [(n, "cams") for n in xc.SQ_CAMS_CASES] + [(n, "affine") for n in xc.SQ_AFFINE_CASES])
+def test_numpy_model_of_a_squared_variant_trial(name, kind):
+    """Where the K of the squared variants come from, and what each bar sees (all at eps32, the wider bar): the factor 2 of the rows
+    turned into 1 (H, g, the step's residual); the last observation left out of the sums (H and g, or the affine's residual); the
+    trial cost evaluated at the old parameters (a theta read from the wrong buffer); lambda from tau x the smallest diagonal entry."""
+    c = xc.case(name)
+    q = xc.sq_model(name, kind)
+    assert q["gain"] > 0.25                                   # the LM control accepts the trial
+    R = xc.sq_ratios(name, kind, q, EPS64)
+    assert abs(R["gain_exact"] - q["gain"]) <= 1e-6
+    for k in _SQ_Q[kind]:
+        assert R[k] <= xc.K[f"sq_{kind}_{k}"] / 16.0, (k, R[k])
+    if kind == "affine":                                      # the step read back from the stored theta: the allowance covers the rounding
+        th = xc.IDENT12 + q["x"].ravel()
+        assert xc.sq_ratios(name, kind, dict(theta=th, tcost=q["tcost"]), EPS64)["res"] <= xc.K["sq_affine_res"] / 16.0
+    e32 = xc.EPS["f32"]
+    X = xc.sq_exact(name, kind)
+    lam_x = xc.SQ_TAU * float(np.max(np.einsum("gii->gi", X.H)))
+    half = xc.sq_model(name, kind, row_factor=1.0)
+    solve = lambda H, g: np.stack([np.linalg.solve(H[k] + lam_x * np.eye(H.shape[1]), -g[k]) for k in range(H.shape[0])])      # noqa: E731
+    bad = xc.sq_ratios(name, kind, dict(H=half["H"], g=half["g"], x=solve(half["H"], half["g"]), tcost=q["cost"],
+                                        lam=xc.SQ_TAU * float(np.min(np.einsum("gii->gi", X.H)))), e32)
+    for k in ("H", "g", "res", "tcost", "lam"):
+        assert bad[k] > xc.K.get(f"sq_{kind}_{k}", xc.K["sq_cams_" + k]), (k, bad[k])
+    m = c.M - 1                                               # the last observation dropped from the sums
+    rows = xc.sq_model(name, kind)
+    d1 = ex.sq_system(X.delta[m:], X.Jc[m:], X.Jp[m:], c.w[m:], c.ci[m:], np.zeros(1, np.int64), c.pts[c.pi[m:]], c.C, kind)
+    Hl, gl = rows["H"] - d1["H"], rows["g"] - d1["g"]
+    lost = xc.sq_ratios(name, kind, dict(H=Hl, g=gl, x=solve(Hl, gl), tcost=q["tcost"]), e32)
+    for k in (("H", "g") if kind == "cams" else ("res",)):
+        assert lost[k] > xc.K[f"sq_{kind}_{k}"], (k, lost[k])
