@@ -1099,6 +1099,85 @@ int sba_frame_histograms(int device, const uint8_t* frames, int64_t n_frames, in
                          const sba_hist_opts* opts /*NULL: {1, 0, ...0}*/,
                          uint32_t* hist /*n_frames*256 or NULL*/, uint64_t* total /*256, ADDED TO, or NULL*/);
 
+/* ---------------------------------------------------------------- sub-pixel corner refinement
+ * The ChArUco half of the reference -- where every camera's starting intrinsics and extrinsics come from -- has one numerical
+ * step on pixels: cv.cornerSubPix, called per marker corner with winSize (3, 3), zeroZone (-1, -1), 200 iterations and eps
+ * 1e-5 (scripts/charuco_intrinsics.py:18,39-44).  sba_refine_corners does it for the corners of a batch of frames.  Finding and
+ * decoding markers stays with the caller, as decoding video does.  Stateless: no handle.  Frames are described as for
+ * sba_detect_dots (8-bit, channels 1, 3 or 4 interleaved, any base, any pitches, host memory or with frames_on_device device
+ * memory read in place).  The corners of frame f are the rows corner_start[f] .. corner_start[f + 1] - 1 of `corners`; a frame
+ * may have none.  Corners and all outputs are host memory.
+ *
+ * The window has the half sizes wx = win_x, wy = win_y and the weights m(i, j), i = -wy..wy, j = -wx..wx: `weights`, row-major,
+ * finite and >= 0, or with weights == NULL OpenCV's window, formed on the host in float64 as
+ *   m(i, j) = exp(-(i / wy)^2) * exp(-(j / wx)^2),   set to 0 for |i| <= zero_y and |j| <= zero_x
+ * when zero_x >= 0, zero_y >= 0, zero_x < wx and zero_y < wy (any other zero zone is ignored, as in OpenCV).  zero_x and zero_y
+ * are not applied to explicit weights: the caller zeroes what it wants left out.
+ *
+ * The rule per corner (x, y) -- this is the function's definition.  Every step is ONE IEEE float64 operation in the order
+ * written, never contracted into a fused multiply-add; the division is the correctly rounded one.
+ *   Start    (cx, cy) = (x, y).  A coordinate that is not finite or has |.| >= 32768 makes the corner INVALID: refined = the
+ *            input, iterations = 0, tensor = 0, no pixel is read.
+ *   Tap      T(u, v) = the value of pixel (clamp(u, 0, W - 1), clamp(v, 0, H - 1)): its byte `channel`, or with channel = -1 the
+ *            grey value g of sba_resize_frames' rule 1 with gray_w.  The border is replicated: a window may hang over the edge.
+ *   Sample   ix = floor(cx), ax = cx - ix, iy = floor(cy), ay = cy - iy, w = 1 - ax, h = 1 - ay.  For |j'| <= wx + 1 and
+ *            |i'| <= wy + 1:
+ *              top = w * T(ix + j', iy + i')     + ax * T(ix + j' + 1, iy + i')
+ *              bot = w * T(ix + j', iy + i' + 1) + ax * T(ix + j' + 1, iy + i' + 1)
+ *              S(i', j') = h * top + ay * bot
+ *   Window   per position (i, j) with weight m:
+ *              gx = S(i, j + 1) - S(i, j - 1)      gy = S(i + 1, j) - S(i - 1, j)
+ *              gxx = (gx * gx) * m      gxy = (gx * gy) * m      gyy = (gy * gy) * m
+ *              e1 = gxx * j + gxy * i              e2 = gxy * j + gyy * i
+ *   Sums     a = sum gxx, b = sum gxy, c = sum gyy, b1 = sum e1, b2 = sum e2: each formed per window ROW from j = -wx to wx
+ *            starting from 0.0, the row totals then added from i = -wy to wy starting from 0.0.  The two-level order is part
+ *            of the rule.
+ *   Step     det = a * c - b * b.  If !(fabs(det) > 2^-104) (DBL_EPSILON^2; false for NaN) the corner stops SINGULAR.  Else
+ *              s = 1 / det      nx = (cx + (c * s) * b1) - (b * s) * b2      ny = (cy - (b * s) * b1) + (a * s) * b2
+ *              err = (nx - cx) * (nx - cx) + (ny - cy) * (ny - cy)
+ *            (cx, cy) = (nx, ny) and the iteration count goes up by one.
+ *   Stop     after a step: if !(0 <= cx < W and 0 <= cy < H) LEFT_IMAGE; else if err <= eps * eps (formed once, on the host)
+ *            CONVERGED; else if the count equals max_iter MAX_ITER; else the next iteration samples at the new position.
+ *   Restore  at the end, unless INVALID: if |cx - x| > wx or |cy - y| > wy, refined = the input and RESTORED is or-ed in
+ *            (OpenCV's behaviour); else refined = (cx, cy).
+ * iterations = the steps applied; tensor = (a, b, c) of the last system formed: the window's structure tensor, which tells an
+ * edge (one small eigenvalue) from a corner and gives a corner a weight.  OpenCV throws it away.
+ * This is OpenCV's cornerSubPix with two differences: the patch S is float64 where OpenCV's is float32, and the order of the
+ * sums is fixed.  The library agrees BIT FOR BIT with this rule (tests/test_corners_host.py restates it in numpy), not with
+ * cv2: positions differ from cv2.cornerSubPix by what a float32 patch is worth.
+ * Host frames pass through two staging buffers of chunk_frames frames; a chunk's launch gets the corners of its frames.  Device
+ * memory does not grow with n_frames, and any chunk_frames gives the same bits.  n_frames = 0 or no corner at all returns SBA_OK
+ * and reads nothing.
+ * Errors, all checked before any device work (text "sba_refine_corners: ..." in sba_last_error(NULL)), no output written: the
+ * frame errors of sba_detect_dots; SBA_ERR_INVALID for a NULL corner_start with n_frames > 0, corner_start[0] != 0 or a
+ * decreasing entry, win_x or win_y outside 1..15, max_iter outside 1..10000, eps negative or NaN, channel outside
+ * -1..channels-1, channel = -1 with channels == 1, gray weights that are negative or do not sum to 2^15, a weight that is
+ * negative or not finite, NULL corners, refined or status when there are corners, and corners in frames without pixels. */
+typedef enum {
+  SBA_CORNER_CONVERGED = 1, SBA_CORNER_MAX_ITER = 2, SBA_CORNER_SINGULAR = 4, SBA_CORNER_LEFT_IMAGE = 8,
+  SBA_CORNER_RESTORED = 16, SBA_CORNER_INVALID = 32
+} sba_corner_status;
+typedef struct {
+  double eps;                /* stop when a step is no longer than this, in pixels; >= 0                        */
+  int32_t frames_on_device;  /* as sba_dot_opts                                                                 */
+  int32_t chunk_frames;      /* host frames: frames per staged chunk; <= 0 = library default                    */
+  int32_t channel;           /* 0..channels-1, or -1: the grey value of sba_resize_frames (3 or 4 channels)     */
+  int32_t gray_w[3];         /* as sba_resize_opts; all zero = {3735, 19235, 9798} (B, G, R)                    */
+  int32_t win_x, win_y;      /* half sizes of the window, 1..15                                                 */
+  int32_t zero_x, zero_y;    /* half sizes of the zero zone of the built-in window; -1, -1 = none               */
+  int32_t max_iter;          /* 1..10000                                                                        */
+  int32_t reserved[5];
+} sba_corner_opts;           /* 72 bytes */
+int sba_refine_corners(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width,
+                       int32_t channels /*1, 3 or 4*/, int64_t row_pitch, int64_t frame_pitch,
+                       const int64_t* corner_start /*n_frames+1, non-decreasing, [0]=0*/,
+                       const double* corners /*corner_start[n_frames]*2: (x, y) pixel coordinates*/,
+                       const sba_corner_opts* opts /*NULL: the reference's call: eps 1e-5, grey (channel 0 of one plane),
+                                                     window 3 x 3, no zero zone, 200 iterations*/,
+                       const double* weights /*(2 win_y+1)*(2 win_x+1), row-major, or NULL*/,
+                       double* refined /*as corners*/, int32_t* status /*sba_corner_status bits*/,
+                       int32_t* iterations /*or NULL*/, double* tensor /*n*3: a, b, c of the last system formed, or NULL*/);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
     "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames", "sba_resize_frames",
     "sba_frames_to_yuv", "sba_undistort_yuv", "sba_frame_histograms", "sba_warp_frames",
+    "sba_refine_corners",
 )
 
 
@@ -120,6 +121,17 @@ DOT_MAX_DIM = 16384
 class HistOpts(C.Structure):
     _fields_ = [("channel", C.c_int32), ("frames_on_device", C.c_int32), ("roi_rect", C.c_int32 * 4), ("roi_circle", C.c_int32 * 3),
                 ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class CornerOpts(C.Structure):                                            # sba_corner_opts
+    _fields_ = [("eps", C.c_double), ("frames_on_device", C.c_int32), ("chunk_frames", C.c_int32), ("channel", C.c_int32),
+                ("gray_w", C.c_int32 * 3), ("win_x", C.c_int32), ("win_y", C.c_int32), ("zero_x", C.c_int32), ("zero_y", C.c_int32),
+                ("max_iter", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+# sba_corner_status bits
+CORNER_CONVERGED, CORNER_MAX_ITER, CORNER_SINGULAR, CORNER_LEFT_IMAGE, CORNER_RESTORED, CORNER_INVALID = 1, 2, 4, 8, 16, 32
+CORNER_MAX_WIN, CORNER_MAX_ITERATIONS = 15, 10000
 
 
 class BlobOpts(C.Structure):
@@ -552,6 +564,8 @@ def load():
                                         C.c_int32, C.POINTER(YuvPlanes), C.POINTER(UndistortYuvOpts), C.c_void_p, C.c_void_p]),
         "sba_frame_histograms": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                            C.POINTER(HistOpts), C.c_void_p, C.c_void_p]),
+        "sba_refine_corners": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, ip, dp,
+                                         C.POINTER(CornerOpts), dp, dp, C.c_void_p, C.c_void_p, dp]),
         "sba_resize_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_int64, C.c_int64, C.POINTER(ResizeOpts), C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
@@ -1318,6 +1332,39 @@ def resize_frames(frames, fx, fy, gray_w=None, out=None, out_on_device=None, chu
     ptr = _synced(device, frames, also=out_tensor)
     _check(lib.sba_resize_frames(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, fx, fy, osr, osf, C.byref(opts), C.c_void_p(optr)))
     return out
+
+
+def refine_corners(frames, corner_start, corners, win=(3, 3), zero_zone=(-1, -1), max_iter=200, eps=1e-5, channel=0, gray_w=None,
+                   weights=None, chunk_frames=0, device=0):
+    """sba_refine_corners (include/sba_hip.h) -> (refined (n, 2) float64, status (n,) int32, iterations (n,) int32, tensor (n, 3)).
+
+    ``frames`` as for ``detect_dots``; ``corner_start`` (B + 1,) int64 and ``corners`` (n, 2) float64 as the header describes
+    them; ``win`` = (win_x, win_y) and ``zero_zone`` = (zero_x, zero_y) half sizes; ``channel`` -1 is the grey value with
+    ``gray_w`` (None: OpenCV's of B, G, R); ``weights`` None lets the library build OpenCV's window, else the
+    (2 win_y + 1, 2 win_x + 1) float64 weights.  ``lasercalib_amd.imaging.refine_corners`` is the public face of this call."""
+    lib = load()
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    start = np.ascontiguousarray(corner_start, dtype=np.int64)
+    if start.shape != (B + 1,):
+        raise ValueError(f"corner_start must hold {B + 1} offsets, got the shape {start.shape}")
+    n = int(start[-1])
+    xy = _f64(corners).reshape(-1, 2)
+    if xy.shape[0] != n:
+        raise ValueError(f"corners has {xy.shape[0]} rows, corner_start ends at {n}")
+    opts = CornerOpts()
+    opts.eps, opts.frames_on_device, opts.chunk_frames, opts.channel = float(eps), 1 if tensor else 0, int(chunk_frames), int(channel)
+    if gray_w is not None:
+        opts.gray_w = (C.c_int32 * 3)(*_int32s(gray_w, 3, "gray_w must be three 32-bit integers"))
+    (opts.win_x, opts.win_y), (opts.zero_x, opts.zero_y), opts.max_iter = (int(v) for v in win), (int(v) for v in zero_zone), int(max_iter)
+    if weights is not None:
+        weights = _f64(weights)
+        if weights.shape != (2 * opts.win_y + 1, 2 * opts.win_x + 1):
+            raise ValueError(f"weights must have the shape {(2 * opts.win_y + 1, 2 * opts.win_x + 1)}, got {weights.shape}")
+    refined, status = xy.copy(), np.full(n, CORNER_INVALID, np.int32)
+    iterations, tens = np.zeros(n, np.int32), np.zeros((n, 3))
+    _check(lib.sba_refine_corners(device, C.c_void_p(_synced(device, frames)), B, H, W, Cn, sr, sf, _iptr(start), _dptr(xy),
+                                  C.byref(opts), _dptr(weights), _dptr(refined), status.ctypes.data, iterations.ctypes.data, _dptr(tens)))
+    return refined, status, iterations, tens
 
 
 class Problem:

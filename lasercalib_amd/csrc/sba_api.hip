@@ -45,6 +45,10 @@ int sba_hist_call(int device, const uint8_t* frames, int64_t n_frames, int32_t h
 int sba_warp_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
                   int64_t frame_pitch, const sba_lens& lens, const double* m, int32_t out_height, int32_t out_width, int64_t out_row_pitch,
                   int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out, uint8_t* flags_out, int32_t* map_out);
+int sba_corners_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                     int64_t row_pitch, int64_t frame_pitch, const int64_t* corner_start, const double* corners,
+                     const sba_corner_opts& opts, const double* weights, double* refined, int32_t* status, int32_t* iterations,
+                     double* tensor);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -722,6 +726,46 @@ int sba_frame_histograms(int device, const uint8_t* frames, int64_t n_frames, in
   if (rc || n_frames == 0 || (!hist && !total)) return rc;
   return guarded(nullptr, [&] {
     return sba_hist_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, hist, total);
+  });
+}
+
+int sba_refine_corners(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                       int64_t row_pitch, int64_t frame_pitch, const int64_t* corner_start, const double* corners,
+                       const sba_corner_opts* opts, const double* weights, double* refined, int32_t* status, int32_t* iterations,
+                       double* tensor) {
+  const char* fn = "sba_refine_corners";
+  sba_corner_opts o{};
+  o.eps = 1e-5; o.channel = channels == 1 ? 0 : -1; o.win_x = o.win_y = 3; o.zero_x = o.zero_y = -1; o.max_iter = 200;   // the reference's call
+  if (opts) o = *opts;
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel == -1 ? 0 : o.channel, 0);
+  if (rc) return rc;
+  if (o.channel == -1) {
+    if (channels == 1) return detect_invalid(fn, "channel -1 (gray) needs 3 or 4 channels");
+    if (o.gray_w[0] == 0 && o.gray_w[1] == 0 && o.gray_w[2] == 0) { o.gray_w[0] = 3735; o.gray_w[1] = 19235; o.gray_w[2] = 9798; }   // OpenCV's B, G, R
+    if (o.gray_w[0] < 0 || o.gray_w[1] < 0 || o.gray_w[2] < 0) return detect_invalid(fn, "a gray weight is negative");
+    if ((int64_t)o.gray_w[0] + o.gray_w[1] + o.gray_w[2] != 1 << 15) return detect_invalid(fn, "the gray weights must sum to 2^15");
+  }
+  if (o.win_x < 1 || o.win_x > 15 || o.win_y < 1 || o.win_y > 15) return detect_invalid(fn, "win_x and win_y must be in 1..15");
+  if (o.max_iter < 1 || o.max_iter > 10000) return detect_invalid(fn, "max_iter must be in 1..10000");
+  if (!(o.eps >= 0.0)) return detect_invalid(fn, "eps must be >= 0");
+  if (n_frames > 0 && !corner_start) return detect_invalid(fn, "null corner_start");
+  int64_t n = 0;
+  if (n_frames > 0) {
+    if (corner_start[0] != 0) return detect_invalid(fn, "corner_start[0] must be 0");
+    for (int64_t f = 0; f < n_frames; ++f)
+      if (corner_start[f + 1] < corner_start[f]) return detect_invalid(fn, "corner_start must not decrease");
+    n = corner_start[n_frames];
+  }
+  if (weights)
+    for (int64_t i = 0; i < (int64_t)(2 * o.win_y + 1) * (2 * o.win_x + 1); ++i)
+      if (!std::isfinite(weights[i]) || weights[i] < 0.0) return detect_invalid(fn, "a weight is negative or not finite");
+  if (n > 0 && (!corners || !refined || !status)) return detect_invalid(fn, "null corners, refined or status");
+  if (n > 0 && (height == 0 || width == 0)) return detect_invalid(fn, "corners in frames without pixels");
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc || n == 0) return rc;
+  return guarded(nullptr, [&] {
+    return sba_corners_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, corner_start, corners, o, weights,
+                            refined, status, iterations, tensor);
   });
 }
 

@@ -2,7 +2,7 @@
 // connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp), the
 // conversion of decoder frames (sba_convert.hpp), its way back to encoder frames (sba_yuv.hpp), the area-averaged previews
 // (sba_resize.hpp), the undistortion of YUV 4:2:0 frames plane by plane (sba_undistort_yuv.hpp), the per-frame value
-// histograms (sba_hist.hpp) and the plane views and virtual cameras (sba_warp.hpp).  They do not depend on the engine's camera model, so they are compiled once, in a translation
+// histograms (sba_hist.hpp), the plane views and virtual cameras (sba_warp.hpp) and the sub-pixel corner refinement (sba_corners.hpp).  They do not depend on the engine's camera model, so they are compiled once, in a translation
 // unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
@@ -13,6 +13,7 @@
 #include "sba_undistort_yuv.hpp"
 #include "sba_hist.hpp"
 #include "sba_warp.hpp"
+#include "sba_corners.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -83,4 +84,12 @@ int sba_warp_call(int device, const uint8_t* frames, int64_t n_frames, int32_t h
                   int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out, uint8_t* flags_out, int32_t* map_out) {
   return sba_detect::warp_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, lens, m, out_height, out_width,
                                out_row_pitch, out_frame_pitch, opts, out, flags_out, map_out);
+}
+
+int sba_corners_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                     int64_t row_pitch, int64_t frame_pitch, const int64_t* corner_start, const double* corners,
+                     const sba_corner_opts& opts, const double* weights, double* refined, int32_t* status, int32_t* iterations,
+                     double* tensor) {
+  return sba_detect::corners_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, corner_start, corners, opts,
+                                  weights, refined, status, iterations, tensor);
 }

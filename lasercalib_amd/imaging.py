@@ -26,6 +26,9 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
   (sba_frame_histograms) and what follows from it: the pixels above every threshold at once, saturation, the dark level, Otsu's
   threshold, and the threshold that leaves a dot of a sane size in most frames -- what the reference finds by clicking pixels
   (``lasercalib/get_video_pixel.py``)
+* :func:`refine_corners`, :func:`corner_sub_pix`, :class:`CornerRefinement`, :func:`corner_weights` -- ``cv.cornerSubPix`` for the
+  marker corners of a batch of frames (sba_refine_corners; ``scripts/charuco_intrinsics.py:39-44``), with what OpenCV throws away:
+  the window's structure tensor, which tells an edge from a corner and gives every corner a weight
 
 Sizes are ``(width, height)``, as in OpenCV.  Pixels follow the rule written out in include/sba_hip.h: a float64 model, the
 source position on a 1/32-pixel grid, integer bilinear weights.  That is OpenCV's scheme, but OpenCV rounds its weight table to
@@ -43,7 +46,8 @@ SBA_WARP_BEHIND = WARP_BEHIND
 
 __all__ = ["Lens", "undistort_frames", "undistort_yuv", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
            "YuvMatrix", "convert_frames", "RgbMatrix", "frames_to_yuv", "resize_frames", "mosaic", "frame_histograms", "FrameHistograms", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE",
-           "warp_frames", "plane_view", "PlaneGrid", "virtual_camera_matrix", "plane_mosaic", "SBA_WARP_BEHIND"]
+           "warp_frames", "plane_view", "PlaneGrid", "virtual_camera_matrix", "plane_mosaic", "SBA_WARP_BEHIND",
+           "refine_corners", "corner_sub_pix", "corner_window", "corner_weights", "CornerRefinement"]
 
 
 class Lens:
@@ -850,6 +854,150 @@ def frame_histograms(frames, channel=1, roi_rect=None, roi_circle=None, per_fram
     if pixel_format is not None:
         return fd._from_decoder_frames(frames, pixel_format, matrix, background, channel, chunk_frames, device, count, ("hist",), make)
     return fd._without_background(frames, background, channel, chunk_frames, device, count, ("hist",), make)
+
+
+class CornerRefinement:
+    """What :func:`refine_corners` returns.  ``corners``: the refined positions in the shape of the input (a list of (k, 2)
+    arrays, or one array); over all corners in the order given ``xy`` (n, 2), ``status`` (n,) int32 of sba_corner_status bits,
+    ``iterations`` (n,) int32 and ``tensor`` (n, 3): a, b, c of the window's structure tensor [[a, b], [b, c]] at the last
+    position sampled."""
+
+    def __init__(self, corners, xy, status, iterations, tensor):
+        self.corners, self.xy, self.status, self.iterations, self.tensor = corners, xy, status, iterations, tensor
+
+    @property
+    def ok(self):
+        """(n,) bool: converged and not put back to its start."""
+        return (self.status & (_native.CORNER_CONVERGED | _native.CORNER_RESTORED)) == _native.CORNER_CONVERGED
+
+    def covariance_shape(self):
+        """(n, 2, 2): the inverse of the structure tensor, the shape of a corner's positional covariance up to the image
+        noise; NaN where the corner is SINGULAR or INVALID or the tensor has no inverse."""
+        a, b, c = self.tensor.T
+        det = a * c - b * b
+        bad = (self.status & (_native.CORNER_SINGULAR | _native.CORNER_INVALID)) != 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = np.stack([c, -b, -b, a], axis=1) / np.where(bad | (det == 0), np.nan, det)[:, None]
+        return inv.reshape(-1, 2, 2)
+
+
+def _pair(value, name):
+    try:
+        a, b = (int(v) for v in value)
+        if (a, b) != tuple(value):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be two integers, got {value!r}") from None
+    return a, b
+
+
+def corner_window(win, zero_zone=(-1, -1)):
+    """OpenCV's window of ``cv.cornerSubPix`` as (2 win_y + 1, 2 win_x + 1) float64 weights: entry (i, j) is
+    exp(-(i / win_y)^2) * exp(-(j / win_x)^2) with ``math.exp``, and 0 inside the zero zone when both of its half sizes are
+    >= 0 and it is smaller than the window (sba_refine_corners, include/sba_hip.h).  ``win`` and ``zero_zone`` are (x, y)."""
+    import math
+    (wx, wy), (zx, zy) = _pair(win, "win"), _pair(zero_zone, "zero_zone")
+    if not (1 <= wx <= _native.CORNER_MAX_WIN and 1 <= wy <= _native.CORNER_MAX_WIN):
+        raise ValueError(f"win must be in 1..{_native.CORNER_MAX_WIN}, got {(wx, wy)}")
+    m = np.empty((2 * wy + 1, 2 * wx + 1))
+    for i in range(2 * wy + 1):
+        yy = float(i - wy) / float(wy)
+        vy = math.exp(-(yy * yy))
+        for j in range(2 * wx + 1):
+            xx = float(j - wx) / float(wx)
+            m[i, j] = vy * math.exp(-(xx * xx))
+    if zx >= 0 and zy >= 0 and zx < wx and zy < wy:
+        m[wy - zy:wy + zy + 1, wx - zx:wx + zx + 1] = 0.0
+    return m
+
+
+def refine_corners(frames, corners, win=(3, 3), zero_zone=(-1, -1), max_iter=200, eps=1e-5, channel=None, weights=None,
+                   channel_order="bgr", chunk_frames=0, device=0) -> CornerRefinement:
+    """``cv.cornerSubPix`` for the corners of a batch of frames, on the GPU (sba_refine_corners, include/sba_hip.h) ->
+    :class:`CornerRefinement`.
+
+    ``frames`` as for ``feature_detection.find_laser_dots``: (B, H, W[, C]) uint8, numpy or a tensor on ``device`` read in
+    place.  ``corners``: a list of B arrays (k_f, 2) of (x, y) pixel coordinates, one per frame (a frame may have none), or one
+    (n, 2) array when there is a single frame.  ``win`` and ``zero_zone`` are OpenCV's winSize and zeroZone (half sizes, x
+    first), ``max_iter`` and ``eps`` its criteria.  ``channel``: the byte of a pixel that is read, or -1 for the grey value of
+    ``resize_frames`` (``channel_order`` as there); None is -1 for colour frames and 0 for one plane.  ``weights``: None is
+    OpenCV's window (:func:`corner_window`), else (2 win_y + 1, 2 win_x + 1) weights, finite and >= 0, to which ``zero_zone``
+    is not applied.  The weights are always built here and handed over explicitly, so the library's bits do not depend on the C
+    runtime's ``exp``."""
+    wx, wy = _pair(win, "win")
+    zero_zone = _pair(zero_zone, "zero_zone")
+    if not (1 <= wx <= _native.CORNER_MAX_WIN and 1 <= wy <= _native.CORNER_MAX_WIN):
+        raise ValueError(f"win must be in 1..{_native.CORNER_MAX_WIN}, got {(wx, wy)}")
+    if not 1 <= int(max_iter) <= _native.CORNER_MAX_ITERATIONS:
+        raise ValueError(f"max_iter must be in 1..{_native.CORNER_MAX_ITERATIONS}, got {max_iter!r}")
+    if not float(eps) >= 0.0:
+        raise ValueError(f"eps must be >= 0, got {eps!r}")
+    if weights is None:
+        weights = corner_window((wx, wy), zero_zone)
+    else:
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.shape != (2 * wy + 1, 2 * wx + 1):
+            raise ValueError(f"weights must have the shape {(2 * wy + 1, 2 * wx + 1)}, got {weights.shape}")
+        if not np.all(np.isfinite(weights)) or weights.min() < 0:
+            raise ValueError("weights must be finite and >= 0")
+    shape = tuple(frames.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError(f"frames must be (B, H, W, C) or (B, H, W), got {shape}")
+    B, Cn = int(shape[0]), int(shape[3]) if len(shape) == 4 else 1
+    channel = (0 if Cn == 1 else -1) if channel is None else int(channel)
+    if not (-1 <= channel < Cn) or (channel == -1 and Cn == 1):
+        raise ValueError(f"channel must be in 0..{Cn - 1}" + (" or -1 (gray)" if Cn > 1 else "") + f", got {channel}")
+    gray_w = _gray_weights(True, channel_order) if channel == -1 else None
+    single = isinstance(corners, np.ndarray) and corners.ndim == 2
+    per_frame = [corners] if single else list(corners)
+    if len(per_frame) != B:
+        raise ValueError(f"corners must be one (k, 2) array per frame ({B}), got {len(per_frame)}"
+                         + (": a single array needs a single frame" if single else ""))
+    per_frame = [np.asarray(c, dtype=np.float64).reshape(-1, 2) if np.size(c) == 0 else np.asarray(c, dtype=np.float64) for c in per_frame]
+    for f, c in enumerate(per_frame):
+        if c.ndim != 2 or c.shape[1] != 2:
+            raise ValueError(f"corners of frame {f} must be (k, 2), got {c.shape}")
+    start = np.zeros(B + 1, np.int64)
+    np.cumsum([len(c) for c in per_frame], out=start[1:])
+    xy = np.concatenate(per_frame) if per_frame else np.zeros((0, 2))
+    refined, status, iterations, tensor = _native.refine_corners(frames, start, xy, win=(wx, wy), zero_zone=zero_zone, max_iter=int(max_iter),
+                                                                 eps=float(eps), channel=channel, gray_w=gray_w, weights=weights,
+                                                                 chunk_frames=chunk_frames, device=device)
+    out = refined if single else [refined[start[f]:start[f + 1]] for f in range(B)]
+    return CornerRefinement(out, refined, status, iterations, tensor)
+
+
+def corner_sub_pix(gray, corners, winSize=(3, 3), zeroZone=(-1, -1), criteria=(3, 200, 1e-5), device=0):
+    """``cv.cornerSubPix(gray, corners, winSize, zeroZone, criteria)`` for one image -> the refined corners in the shape and dtype
+    of ``corners``, which may be (n, 1, 2) float32 as ``cv.aruco`` returns them.  ``criteria`` is OpenCV's (type, max_iter, eps):
+    bit 1 of the type (COUNT) makes max_iter count, bit 2 (EPS) eps; without them OpenCV's own 100 and 0 apply.  ``gray`` is
+    (H, W) uint8, or a colour image, of which the grey value is read."""
+    gray = gray if _native._is_tensor(gray) else np.ascontiguousarray(gray)
+    if len(gray.shape) not in (2, 3):
+        raise ValueError(f"gray must be one image (H, W) or (H, W, C), got the shape {tuple(gray.shape)}")
+    pts = np.asarray(corners)
+    if pts.size % 2 or (pts.ndim and pts.shape[-1] != 2):
+        raise ValueError(f"corners must hold (x, y) pairs, got the shape {pts.shape}")
+    kind, count, eps = criteria
+    count = min(max(int(count), 1), _native.CORNER_MAX_ITERATIONS) if int(kind) & 1 else 100
+    eps = max(float(eps), 0.0) if int(kind) & 2 else 0.0
+    res = refine_corners(gray[None], np.asarray(pts, dtype=np.float64).reshape(-1, 2), win=winSize, zero_zone=zeroZone, max_iter=count,
+                         eps=eps, device=device)
+    return res.xy.reshape(pts.shape).astype(pts.dtype if pts.dtype.kind == "f" else np.float64)
+
+
+def corner_weights(result, floor=0.0):
+    """One weight per corner of a :class:`CornerRefinement`, usable as ``PySBA`` ``pointWeights``: the smaller eigenvalue of the
+    structure tensor -- large at a crisp corner, near zero along an edge --, divided by its median over the corners that are
+    ``ok``, so that a typical corner weighs 1; 0 where not ``ok``.  ``floor``: the least weight an ``ok`` corner gets."""
+    a, b, c = result.tensor.T
+    lam = 0.5 * (a + c) - np.sqrt((0.5 * (a - c)) ** 2 + b * b)
+    ok = result.ok & np.isfinite(lam)
+    w = np.zeros(len(lam))
+    if ok.any():
+        med = np.median(lam[ok])
+        w[ok] = np.maximum(lam[ok] / med, float(floor)) if med > 0 else 1.0
+    return w
 
 
 class BackgroundModel:
