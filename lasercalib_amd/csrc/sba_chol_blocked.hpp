@@ -16,9 +16,11 @@
 //   diagonal entry is downdated with the lane's own l_ik): lanes 0..15 own the rows of the tile,
 //   lanes 16..31 run the rows of the identity through the same column operations and so end up with Linv^T, which is
 //   all that is stored (L11 itself is never needed again: B' and the back substitution both multiply by Linv).
+//   (S = float, round 6: the tile is factored in 4-pivot groups on the MFMA accumulator layout instead, chol16_tile / sba_chol16_block4.hpp.)
 // After the last column the blocked back substitution runs right-looking over all waves.
 #pragma once
 #include "sba_lm_kernels.hpp"
+#include "sba_chol16_block4.hpp"
 
 namespace SBA_NS {
 
@@ -258,6 +260,15 @@ __device__ __forceinline__ bool chol16_wave_t(S* __restrict__ blk, const S* __re
   return ok;
 }
 
+// The diagonal tile of cholb_core.  S = float (round 6): in 4-pivot groups on the accumulator layout (sba_chol16_block4.hpp: 40 scalar
+// broadcasts per tile instead of 136, the rest on three rounds of rank-4 MFMA updates) -- same contract, another rounding of the factor.
+// S = double: chol16_wave_t as before.
+template <typename S, bool NEWTON, typename L = CholLay<S>>
+__device__ __forceinline__ bool chol16_tile(S* __restrict__ blk, const S* __restrict__ a0, S tau) {
+  if constexpr (std::is_same<S, float>::value) return sba_block4::chol16_block4_f32<L::LD>(blk, a0, tau);
+  else return chol16_wave_t<S, NEWTON, L>(blk, a0, tau);
+}
+
 template <typename S, typename L = CholLay<S>>
 __device__ __forceinline__ void chol_panel_block_t(S* __restrict__ Ablk, const S* __restrict__ LinvT) {
   const int lane = threadIdx.x & 63;
@@ -494,7 +505,7 @@ __device__ __forceinline__ bool cholb_core(unsigned char* __restrict__ smem, Cho
     CHOL_STAMP();
   }
   if (wid == 0) {
-    if (!chol16_wave_t<S, NEWTON, L>(Lb + L::off(0, 0), F32 ? s_a0 : nullptr, tau)) { if (lane == 0) sh.fail = 1; }
+    if (!chol16_tile<S, NEWTON, L>(Lb + L::off(0, 0), F32 ? s_a0 : nullptr, tau)) { if (lane == 0) sh.fail = 1; }
   }
   __syncthreads();
   CHOL_STAMP();
@@ -525,7 +536,7 @@ __device__ __forceinline__ bool cholb_core(unsigned char* __restrict__ smem, Cho
     // ---- C: look-ahead factorisation of the next diagonal tile (wave 0) | rhs tail + trailing update (waves 1..7)
     if (wid == 0) {
       if (jb + 1 < nb) {
-        if (!chol16_wave_t<S, NEWTON, L>(Lb + L::off(jb + 1, jb + 1), F32 ? s_a0 + (jb + 1) * CB : nullptr, tau)) { if (lane == 0) sh.fail = 1; }
+        if (!chol16_tile<S, NEWTON, L>(Lb + L::off(jb + 1, jb + 1), F32 ? s_a0 + (jb + 1) * CB : nullptr, tau)) { if (lane == 0) sh.fail = 1; }
       }
     } else {
       // The wave that shares its SIMD with wave 0 (wave 4: waves go round the four SIMDs, tools/micro/hw_id.hip) takes the light
