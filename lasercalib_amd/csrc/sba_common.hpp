@@ -180,6 +180,19 @@ struct DevBuf {
   void zero(hipStream_t s) { if (n) HIPCHK(hipMemsetAsync(p, 0, n * sizeof(U), s)); }
 };
 
+// the dynamic LDS a kernel may ask for beyond the 64 KB default
+template <typename K> void set_lds(K* kernel, size_t bytes) {
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+}
+
+// cycle stamps a diagnostic run's kernel left in b (waits for the stream)
+inline std::vector<long long> read_stamps(const DevBuf<long long>& b, size_t count, hipStream_t stream) {
+  std::vector<long long> st(count);
+  HIPCHK(hipMemcpyAsync(st.data(), b.p, count * sizeof(long long), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return st;
+}
+
 // N timing events of one call: created together, the created ones destroyed with the scope (a HIPCHK that throws included)
 template <int N>
 struct DevEvents {

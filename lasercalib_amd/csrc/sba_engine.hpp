@@ -17,87 +17,17 @@
 #include "sba_align.hpp"
 #include "sba_reproj.hpp"
 #include "sba_layout.hpp"
+// (host side only; behind the kernels, whose order in the translation unit they leave alone)
+#include "sba_knobs.hpp"
+#include "sba_chol_solve.hpp"
 
 namespace SBA_NS {
 using namespace sba_host;
 
 constexpr int MAX_CAMS = 128;        // sba_upload refuses larger rigs
-
-// ============================================================================================== switches
-// The environment switches ("Environment switches"), read once per handle, at sba_create: a process may change
-// them between two handles.  read_knobs is the only place in the engine that looks at the environment.
-struct Knobs {
-  bool no_dense = false;             // SBA_NO_DENSE: no lane = (point, camera) kernels (fused Schur, dense back substitution)
-  bool no_fused64 = false;           // SBA_NO_FUSED64: fp64 keeps the pair kernels (no k_schur_fused_f64 / k_schur_fused_wide_f64)
-  bool no_wide = false;              // SBA_NO_WIDE: no wide kernels for 17+ cameras (pair kernels, point-aligned back substitution)
-  bool wide_pw2 = false;             // SBA_WIDE_PW2: two points per producer wave in the wide kernels, never three
-  // one-workgroup factorisations of up to 256 unknowns: the right-looking all-in-LDS kernel up to 176 (k_cholesky_blocked),
-  // the left-looking kernel with the factor on chip above that (k_cholesky_ll, sba_chol_ll.hpp: 17..23 cameras).
-  // SBA_CHOL=ll: the left-looking kernel for every size up to 256; SBA_CHOL=blocked: never (the streamed kernel above 176) -- A/B runs, tests
-  bool chol_ll = true, chol_ll_all = false;
-  // fp32 engine, up to 176 unknowns: factor on f32 lanes (v_mfma_f32_16x16x4, f32 pivot chain) and repeat in f64 only when that is
-  // refused -- a non-positive pivot, or one below chol_f32_tau times its diagonal entry (2^-23: the entry's own rounding noise).
-  // SBA_CHOL_F32=0 keeps the f64 factorisation of rounds 1-3; SBA_CHOL_F32_TAU overrides the threshold.
-  bool chol_f32 = true;
-  float chol_f32_tau = 1.1920929e-7f;
-  bool chol_big_dag = true;          // SBA_CHOL_BIG=launches keeps one launch per block column (rounds 1-3)
-  // systems larger than this take the multi-workgroup factorisation (sba_chol_big.hpp); up to CS_MAX_NB * CB = 512 unknowns the
-  // streamed one-workgroup kernel could run too, but it only wins below ~210 (measured at 50k points, fp32: 17 cameras 379 vs 388 us
-  // per iteration, 20: 417 vs 409, 24: 487 vs 454, 32: 647 vs 515).  SBA_CHOL_BIG_MIN_N moves it (diagnostics).
-  int chol_big_min_n = 209;
-  bool decide_kernel = false;        // SBA_DECIDE_KERNEL=1 keeps the separate k_decide launch (A/B measurements)
-  bool schur_scan = false;           // SBA_SCHUR_SCAN=1: several groups, producers scan the point's observations (no k_group_index)
-  bool no_bf3_pairs = false;         // SBA_NO_BF3_PAIRS=1: f32-input MFMA kernels for every group pair (A/B, equivalence test)
-  // The lane = (point, camera) kernels (fused linearise + Schur, wide, dense back substitution) cost the DENSE instruction count
-  // whatever the visibility; below this fraction of the N x C slots filled the observation-driven three-pass path would take over.
-  // Rounds 1-3 set it to 0.35 unmeasured.  Round 4 measured it (profiles/r4_visibility_sweep*.txt: 16 / 17 cameras, 10k and 50k points,
-  // fill 0.14 .. 0.45, both dtypes): the one-launch kernels win at EVERY fill a rig can have (two views of 16 cameras = 0.13: fp32
-  // 78 vs 102 us per iteration at 16 x 10k, 111 vs 163 at 17 x 10k, 118 vs 155 at 16 x 50k; fp64 212 vs 245) because the three-pass
-  // path is bound by its launches and pair kernels, not by the observation count.  So the threshold is 0; SBA_DENSE_MIN_VIS restores one.
-  double dense_min_vis = 0.0;
-  // instruments (stderr)
-  bool schur_debug = false;          // SBA_SCHUR_DEBUG=k: stamps of the k-th fused Schur launch (k >= 2: one with the decision in its prologue)
-  int schur_debug_skip = 0;
-  bool chol_debug = false;           // SBA_CHOL_DEBUG: stamps of the first factorisation
-  bool upload_debug = false;         // SBA_UPLOAD_DEBUG: phase times of sba_upload
-  bool solve_debug = false;          // SBA_SOLVE_DEBUG: host-side phase times of every sba_solve
-  // one-shot exchange (sba_ipc.hpp)
-  long long ipc_timeout_ticks = IPC_TIMEOUT_TICKS;   // SBA_IPC_TIMEOUT_S: how long a gate waits for a peer (100 MHz ticks)
-  bool ipc_allow_cached = false;     // SBA_IPC_ALLOW_CACHED=1: an exchange area in cached memory when uncached is not available
-};
-
-inline Knobs read_knobs() {
-  Knobs k;
-  auto set = [](const char* name) { return getenv(name) != nullptr; };
-  k.no_dense = set("SBA_NO_DENSE");
-  k.no_fused64 = set("SBA_NO_FUSED64");
-  k.no_wide = set("SBA_NO_WIDE");
-  k.wide_pw2 = set("SBA_WIDE_PW2");
-  k.decide_kernel = set("SBA_DECIDE_KERNEL");
-  k.schur_scan = set("SBA_SCHUR_SCAN");
-  k.no_bf3_pairs = set("SBA_NO_BF3_PAIRS");
-  k.chol_debug = set("SBA_CHOL_DEBUG");
-  k.upload_debug = set("SBA_UPLOAD_DEBUG");
-  k.solve_debug = set("SBA_SOLVE_DEBUG");
-  k.ipc_allow_cached = set("SBA_IPC_ALLOW_CACHED");
-  if (const char* e = getenv("SBA_CHOL")) { k.chol_ll = std::string(e) != "blocked"; k.chol_ll_all = std::string(e) == "ll"; }
-  if (const char* e = getenv("SBA_CHOL_F32")) k.chol_f32 = atoi(e) != 0;
-  if (const char* e = getenv("SBA_CHOL_F32_TAU")) { char* end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0 && v < 1) k.chol_f32_tau = (float)v; }
-  if (const char* e = getenv("SBA_CHOL_BIG")) k.chol_big_dag = std::string(e) != "launches";
-  if (const char* e = getenv("SBA_CHOL_BIG_MIN_N")) {
-    char* end = nullptr;
-    const long v = strtol(e, &end, 10);
-    if (end != e && *end == 0 && v >= 0) k.chol_big_min_n = (int)std::min<long>(v, CS_MAX_NB * CB);
-  }
-  if (const char* e = getenv("SBA_DENSE_MIN_VIS")) { char* end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0 && v <= 1) k.dense_min_vis = v; }
-  if (const char* e = getenv("SBA_SCHUR_DEBUG")) { k.schur_debug = true; k.schur_debug_skip = std::max(0, atoi(e) - 1); }
-  if (const char* e = getenv("SBA_IPC_TIMEOUT_S")) {
-    char* end = nullptr;
-    const double sec = strtod(e, &end);
-    if (end != e && sec > 0 && sec < 3600) k.ipc_timeout_ticks = (long long)(sec * 1e8);
-  }
-  return k;
-}
+// (the largest system, MAX_CAMS cameras of 13 parameters, fits the one-launch forms: k_chol_big_dag's block rows and the x of
+//  k_chol_big_back_all in LDS)
+static_assert(cholbig_npad(MAX_CAMS * 13) / BB <= CHOLDAG_MAX_NBR && (MAX_CAMS * 13 + BB - 1) / BB <= CHOLBIG_MAX_NBX, "large Cholesky sizes");
 
 // ============================================================================================== routes
 // What sba_upload knows about a problem when it picks the kernels
@@ -226,36 +156,6 @@ Route plan_route(const Layout& L, const Knobs& k) {
   return r;
 }
 
-// The factorisation of the reduced camera system (n_sys unknowns: C * NCP, or the tied ones of SBA_MODE_SHARED_INTR)
-enum class CholRoute {
-  LL,              // k_cholesky_ll: left-looking, factor on chip, up to 256 unknowns (sba_chol_ll.hpp)
-  LL_F32,          // ... behind k_cholesky_blocked on f32 lanes: k_cholesky_ll only runs when that one refused the system
-  BLOCKED,         // k_cholesky_blocked: right-looking, all in LDS, up to 176 unknowns (fp32 engine: on f32 lanes, f64 on a refusal)
-  STREAM,          // k_cholesky_stream: one workgroup, finished block columns streamed through L2, up to chol_big_min_n
-  BIG_DAG,         // k_chol_big_dag<double>: one launch, walker + tiles (sba_chol_big.hpp), then k_chol_big_back_all
-  BIG_DAG_F32,     // ... k_chol_big_dag<float>, the f64 instance behind it for the systems it refuses
-  BIG_LAUNCHES,    // k_chol_big_prepare + one k_chol_big_step per block column, then k_chol_big_back_all
-};
-// (the largest system, MAX_CAMS cameras of 13 parameters, fits the one-launch forms: k_chol_big_dag's block rows and the x of
-//  k_chol_big_back_all in LDS)
-static_assert(cholbig_npad(MAX_CAMS * 13) / BB <= CHOLDAG_MAX_NBR && (MAX_CAMS * 13 + BB - 1) / BB <= CHOLBIG_MAX_NBX, "large Cholesky sizes");
-
-template <typename T>
-CholRoute chol_route(int n_sys, int ncam /* C * NCP */, const Knobs& k, bool card_shared) {
-  if (k.chol_ll && (n_sys > CHOL_LDS_MAX_N || k.chol_ll_all) && n_sys <= CLL_MAX_NB * CB && ncam <= CLL_THREADS) {
-    // fp32 engine (round 4): the right-looking all-in-LDS kernel on f32 lanes in front of it
-    const bool f32 = sizeof(T) == 4 && k.chol_f32 && !k.chol_ll_all && n_sys > CHOL_LDS_MAX_N && ncam <= CHOLB_LDS_THREADS;
-    return f32 ? CholRoute::LL_F32 : CholRoute::LL;
-  }
-  // (up to 176 unknowns C * NCP <= CHOLB_LDS_THREADS holds: a tied system has 3 + 8 C or 3 + 10 C unknowns)
-  if (n_sys <= CHOL_LDS_MAX_N) return CholRoute::BLOCKED;
-  if (n_sys <= k.chol_big_min_n) return CholRoute::STREAM;             // (chol_big_min_n <= CS_MAX_NB * CB)
-  // ranks that share a card: k_chol_big_dag's progress argument (in-order dispatch of ONE launch) does not cover several such
-  // launches holding each other's CUs
-  if (!k.chol_big_dag || card_shared) return CholRoute::BIG_LAUNCHES;
-  return sizeof(T) == 4 && k.chol_f32 ? CholRoute::BIG_DAG_F32 : CholRoute::BIG_DAG;
-}
-
 // ============================================================================================== engine
 template <typename T>
 struct Engine : EngineBase {
@@ -313,23 +213,10 @@ struct Engine : EngineBase {
   LMState* h_state = nullptr;         // pinned
   sba_lm_opts opts{};
   bool lm_active = false;
-  DevBuf<double> chol_sol, chol_work, chol_W, chol_Minv, chol_Ld, chol_yv;
-  DevBuf<int> chol_info;
-  unsigned chol_epoch = 0;              // k_chol_big_back_all: launches so far (its parity picks the copy of x the launch works in)
-  int chol_yv_ext[2] = {0, 0};          // ... entries at the front of each copy of x that a launch may have left non-empty (launch_chol_big)
-  DevBuf<unsigned> chol_dag_flags;      // k_chol_big_dag: Mimg_j / W(r,c) published (value = the launch's epoch)
-  DevBuf<double> chol_Mimg;             // k_chol_big_dag: the factored diagonal blocks and their inverses, as they lie in LDS
-  // fp32 engine: f32 image of the reduced system in k_cholesky_blocked's LDS layout, written by k_build_exchange beside E_own in the
-  // library's own single-rank loop (row stride: chol_img_ld_of_route).  chol_img_ok: the image is the system in E_own -- form_reduced raises it when it
-  // passes the image and lowers it on every other call, which covers all other writers of E_own (the phase API, the multi-rank
-  // exchanges); a tied solve (k_tie_system) never uses it.
-  DevBuf<float> chol_img;
-  bool chol_img_ok = false;
-  unsigned chol_dag_epoch = 0;
+  CholSolver<T> chol;                   // the reduced camera solve: its buffers, f32 image and launch state (sba_chol_solve.hpp)
   bool card_shared = false;             // sba_ipc_attach found a peer rank's exchange area on THIS device (a rehearsal of N ranks on one card):
                                         // kernels whose workgroups wait for each other are then not used where a launch-per-step form exists
-  // SBA_CHOL_DEBUG / SBA_SCHUR_DEBUG: armed from the switches at sba_create, cleared once their stamps are printed
-  bool chol_debug = false;
+  // SBA_SCHUR_DEBUG: armed from the switch at sba_create, cleared once its stamps are printed
   bool schur_debug = false;
   int schur_debug_skip = 0;           // fused Schur launches still to pass before the one whose stamps are printed
   // multi-rank (one handle per GPU, points sharded, cameras replicated): RCCL communicator + exchange buffers
@@ -359,7 +246,6 @@ struct Engine : EngineBase {
   bool multi() const { return comm != nullptr || ipc_on; }
   long long N_global = 0;
   DevBuf<long long> schur_dbg;
-  DevBuf<long long> chol_dbg;
   double initial_cost = 0;
   std::vector<sba_lm_iter_log> log;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wait = nullptr;
@@ -426,7 +312,7 @@ struct Engine : EngineBase {
     d_state_buf.alloc(2);
     d_state.p = d_state_buf.p;
     kn = read_knobs();
-    chol_debug = kn.chol_debug;
+    chol.arm_debug(kn.chol_debug, stream);
     if (kn.schur_debug) { schur_debug = true; schur_debug_skip = kn.schur_debug_skip; schur_dbg.alloc(64); schur_dbg.zero(stream); }
     static bool attrs_set[16] = {};          // the function attributes are per process (and device), not per handle
     if (device < 16 && attrs_set[device]) return;
@@ -467,21 +353,7 @@ struct Engine : EngineBase {
       set_lds(&k_schur_offdiag_bf3, SchurBf3OffCfg::LDS_BYTES);
     }
     set_lds(&k_resjac<T>, 100 * 1024);
-    // (dynamic: the block triangle of 176 unknowns in doubles + two vectors = 146,432 B; the kernel's static LDS -- tables, damping,
-    //  right-hand side, trial cameras -- comes on top of it and both must fit the 160 KB of a CU)
-    set_lds(&k_cholesky_blocked<T>, (CHOLB_MAX_NB * (CHOLB_MAX_NB + 1) / 2 * CBS + 2 * CHOLB_MAX_NB * CB) * sizeof(double));
-    if constexpr (sizeof(T) == 4) {
-      set_lds(&k_cholesky_blocked<T, 16, 20>, (14 * 15 / 2 * CB * 20 + 2 * 14 * CB) * sizeof(float));
-      set_lds(&k_cholesky_blocked<T, 16, 17>, (16 * 17 / 2 * CB * 17 + 2 * 16 * CB) * sizeof(float));
-      set_lds(&k_cholesky_blocked<T, CHOLB_MAX_NB, 20, true>, (CHOLB_MAX_NB * (CHOLB_MAX_NB + 1) / 2 * CBS + 2 * CHOLB_MAX_NB * CB) * sizeof(double));
-      set_lds(&k_cholesky_blocked<T, 16, 20, true>, (14 * 15 / 2 * CB * 20 + 2 * 14 * CB) * sizeof(float));
-      set_lds(&k_cholesky_blocked<T, 16, 17, true>, (16 * 17 / 2 * CB * 17 + 2 * 16 * CB) * sizeof(float));
-    }
-    set_lds(&k_cholesky_stream, 150 * 1024);
-    set_lds(&k_cholesky_ll<T>, CLL_LDS_BYTES);
-    set_lds(&k_chol_big_step, CHOLBIG_LDS_BLOCKS * CBS * sizeof(double));
-    set_lds(&k_chol_big_dag<double>, CHOLBIG_LDS_BLOCKS * CBS * sizeof(double));
-    set_lds(&k_chol_big_dag<float>, CHOLBIG_LDS_BLOCKS * CholLay<float>::BS * sizeof(float));
+    CholSolver<T>::set_attrs();
     set_lds(&k_backsub_trial<T>, 100 * 1024);
     set_lds(&k_linearize_points<T>, 100 * 1024);
     set_lds(&k_residual<T>, 100 * 1024);
@@ -490,11 +362,6 @@ struct Engine : EngineBase {
     set_lds(&k_sq_trial<T, 1>, 100 * 1024);
     set_lds(&k_sq_trial<T, 2>, 100 * 1024);
     if (device < 16) attrs_set[device] = true;
-  }
-
-  // the dynamic LDS a kernel may ask for beyond the 64 KB default
-  template <typename K> static void set_lds(K* kernel, size_t bytes) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   }
 
   void sync() { HIPCHK(hipStreamSynchronize(stream)); }
@@ -806,13 +673,7 @@ struct Engine : EngineBase {
     bpart.alloc(std::max((size_t)ngroups * ksplit * GROUP_ROWS, rt.fused_wide ? (size_t)ksplit * WIDE_ROWS : (size_t)0));
     slabs.alloc(std::max((size_t)npairs * ksplit * GROUP_TILES * GROUP_TILES * 256, rt.fused_wide ? (size_t)ksplit * WIDE_SLOTS * 256 : (size_t)0));
     E_own.alloc((size_t)n * n + 3 * n + 1); scal_own.alloc(NSCAL); delta_c.alloc(n);
-    if constexpr (sizeof(T) == 4) {
-      // the largest triangle a one-workgroup f32 factorisation takes (16 block rows of 17-float rows; 14 of 20-float rows are fewer),
-      // whatever this upload's system: zero once -- n and the route, hence the layout, stay what they are until the next upload
-      chol_img.alloc((size_t)CLL_MAX_NB * (CLL_MAX_NB + 1) / 2 * CB * 17);
-      chol_img.zero(stream);
-    }
-    chol_img_ok = false;
+    chol.on_upload(stream);
     const int nres_blocks = (int)((M + PM_BLOCK - 1) / PM_BLOCK);
     const int nlinp = rt.nlinp;
     // (the one-group visibility masks are kept whenever they exist, also for routes that do not read them: sba_get_layout)
@@ -1076,18 +937,12 @@ struct Engine : EngineBase {
     pending_decide = false;
     gmax_cur = gm_out;
   }
-  std::vector<long long> read_stamps(const DevBuf<long long>& b, size_t count) {
-    std::vector<long long> st(count);
-    HIPCHK(hipMemcpyAsync(st.data(), b.p, count * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    sync();
-    return st;
-  }
   long long* fused_stamps() const { return (schur_debug && schur_debug_skip == 0) ? schur_dbg.p : nullptr; }
   // SBA_SCHUR_DEBUG=k: the stamps of the k-th fused Schur launch on stderr
   void print_fused_stamps(const char* kernel, const char* per, bool prologue) {
     if (!schur_debug) return;
     if (schur_debug_skip > 0) { --schur_debug_skip; return; }
-    const std::vector<long long> st = read_stamps(schur_dbg, 64);
+    const std::vector<long long> st = read_stamps(schur_dbg, 64, stream);
     fprintf(stderr, "[%s stamps, cycles since the first producer stamp; per %s: producer-done consumer-done]\n", kernel, per);
     for (int i = 0; i < 14; ++i) fprintf(stderr, "  it %2d: P %7lld  C %7lld\n", i, st[2 * i] - st[0], st[2 * i + 1] - st[0]);
     fprintf(stderr, "  phases (cycles): prologue %lld | main loop %lld | fold U %lld | slab stores %lld | tail %lld | whole kernel %lld\n",
@@ -1176,7 +1031,7 @@ struct Engine : EngineBase {
                          (const uint16_t*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr,
                          grp_indexed ? grp_mask.p : (const uint16_t*)nullptr, grp_indexed ? grp_start.p : (const int32_t*)nullptr);
       if (schur_debug) {
-        const std::vector<long long> st = read_stamps(schur_dbg, 64);
+        const std::vector<long long> st = read_stamps(schur_dbg, 64, stream);
         fprintf(stderr, "[schur_sym stamps, cycles; per chunk: produce-done after-barrier consume-done]\n");
         for (int i = 0; i < 8; ++i)
           fprintf(stderr, "  it %2d: P %7lld  B %7lld  C %7lld\n", i, st[3 * i] - st[0], st[3 * i + 1] - st[0], st[3 * i + 2] - st[0]);
@@ -1201,7 +1056,7 @@ struct Engine : EngineBase {
                            schur_debug ? schur_dbg.p : nullptr, grp_indexed ? grp_mask.p : (const uint16_t*)nullptr,
                            grp_indexed ? grp_start.p : (const int32_t*)nullptr);
       if (schur_debug) {
-        const std::vector<long long> st = read_stamps(schur_dbg, 64);
+        const std::vector<long long> st = read_stamps(schur_dbg, 64, stream);
         fprintf(stderr, "[schur stamps, cycles since first barrier; per chunk: producer-done consumer-done barrier-out]\n");
         for (int i = 0; i < 14; ++i)
           fprintf(stderr, "  it %2d: P %7lld  C %7lld  out %7lld\n", i, st[3 * i] - st[2], st[3 * i + 1] - st[2], st[3 * i + 2] - st[2]);
@@ -1495,7 +1350,7 @@ struct Engine : EngineBase {
       if (hipPointerGetAttributes(&at, ipc_area[r]) == hipSuccess) { if (at.device == device) card_shared = true; }
       else (void)hipGetLastError();
     }
-    if (chol_debug) fprintf(stderr, "[sba_ipc_attach] rank %d of %d: %s\n", rank, n_ranks, card_shared ? "a peer's exchange area lives on this device: ranks share the card (per-column launches for the large Cholesky)" : "no peer on this device");
+    if (chol.debug) fprintf(stderr, "[sba_ipc_attach] rank %d of %d: %s\n", rank, n_ranks, card_shared ? "a peer's exchange area lives on this device: ranks share the card (per-column launches for the large Cholesky)" : "no peer on this device");
     ipc_ptrs.upload(ipc_area, stream);
     if (ipc_fail.n == 0) ipc_fail.alloc(1);
     ipc_fail.zero(stream);
@@ -1656,18 +1511,10 @@ struct Engine : EngineBase {
   }
 
   int lm_form_reduced(double* E) override { return form_reduced(E, nullptr); }
-  // row stride of the f32 image the untied system's factorisation would copy, 0 = that route takes none
-  int chol_img_ld_of_route() const {
-    if (sizeof(T) != 4 || !kn.chol_f32 || chol_img.n == 0) return 0;
-    const CholRoute route = chol_route<T>(n, n, kn, card_shared);
-    if (route == CholRoute::BLOCKED) return 20;
-    if (route == CholRoute::LL_F32) return (n + CB - 1) / CB <= 14 ? 20 : 17;
-    return 0;
-  }
   int form_reduced(double* E, double* Pk, bool own_loop = false /* run_loop's single-rank iteration: E is E_own */) {
     if (!lm_active) { err = "sba_lm_begin has not been called"; return SBA_ERR_STATE; }
     poll_clean = false;
-    chol_img_ok = false;
+    chol.image_written(false);
     if (!bf3_path()) flush_decide();
     if (sq_mode()) {
       if (opts.mode == SBA_MODE_CAMS_ONLY_SQ)
@@ -1692,80 +1539,16 @@ struct Engine : EngineBase {
       // slab tiles: 3 = the wide kernels' compact rows, 1 = parameter-major (the bf16 kernels), 0 = camera-major
       const int emajor_mode = wide ? 3 : ((fused() && sizeof(T) == 4) || pairs_bf3()) ? 1 : 0;
       // the f32 image for the factorisation: the library's own single-rank loop only, and not for a tied solve
-      const int img_ld = (own_loop && !multi() && !Pk && E == E_own.p && fc && opts.mode != SBA_MODE_SHARED_INTR) ? chol_img_ld_of_route() : 0;
+      const CholPlan cp = plan_chol<T>(n, n, kn, card_shared);
+      float* img = chol.image_for(cp, own_loop && !multi() && !Pk && E == E_own.p && fc && opts.mode != SBA_MODE_SHARED_INTR);
       hipLaunchKernelGGL(k_build_exchange<T>, dim3(nblocks), dim3(1024), 0, stream, slabs.p, bpart.p, rt.ksplit, pair_ga.p,
                          pair_gb.p, np_arg, U.p, gc.p, cost_part.p, n_lin_parts(), C, fc, E, d_state.p,
                          (fused() || rt.pairs_fold_u) ? gdpart.p : (const double*)nullptr, Pk, emajor_mode, nt_launch,
-                         img_ld ? chol_img.p : (float*)nullptr, img_ld);
-      chol_img_ok = img_ld != 0;
+                         img, img ? cp.img_ld : 0);
+      chol.image_written(img != nullptr);
     }
     prof_end(KP_REDUCE);
     return SBA_OK;
-  }
-
-  // A = S + lam D (n_sys x n_sys, in E) -> chol_sol = A^-1 rhs, chol_info != 0 when A is not positive definite
-  // factorisation, both substitutions and the LM epilogue (k_chol_epilogue's work) of a large reduced system
-  void launch_chol_big(double* Esys, int n_sys, bool tied, CholRoute route) {
-    const int npad = cholbig_npad(n_sys), nbr = npad / BB, nbx = (n_sys + BB - 1) / BB;
-    if (chol_W.n < (size_t)npad * npad) {
-      chol_W.alloc((size_t)npad * npad); chol_Minv.alloc((size_t)nbr * BB * BB); chol_Ld.alloc((size_t)nbr * BB * BB);
-      // k_chol_big_back_all: x, one copy per parity of its epoch, "empty" until stored.  The copies lie chol_yv.n / 2 apart, the npad
-      // of the largest system the handle has solved, whatever the system of a launch (a smaller one uses the front of each copy)
-      chol_yv.alloc(2 * (size_t)npad);
-      std::vector<long long> empty(2 * (size_t)npad, CHOLBIG_X_EMPTY);
-      HIPCHK(hipMemcpyAsync(chol_yv.p, empty.data(), empty.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
-      sync();
-      chol_yv_ext[0] = chol_yv_ext[1] = 0;
-    }
-    if (chol_sol.n < (size_t)n_sys) { chol_sol.alloc(n_sys); chol_info.alloc(1); }
-    const size_t lds = (size_t)CHOLBIG_LDS_BLOCKS * CBS * sizeof(double);
-    const bool dag = route != CholRoute::BIG_LAUNCHES, dag32 = route == CholRoute::BIG_DAG_F32;
-    if (dag) {
-      // factorisation (and k_chol_big_prepare's work) in one launch: a walker workgroup on the diagonal, workgroup = tile behind it,
-      // columns handed over through flags (sba_chol_big.hpp).  fp32 engine: on f32 lanes first, the f64 instance behind it only
-      // runs when that one refused the system (LMState::chol_retry)
-      if (chol_dag_flags.n == 0) { chol_dag_flags.alloc(choldag_nflags(CHOLDAG_MAX_NBR)); chol_dag_flags.zero(stream); }
-      if (chol_Mimg.n == 0) chol_Mimg.alloc((size_t)CHOLDAG_MAX_NBR * choldag_img<double>());
-      if (chol_debug) { chol_dbg.alloc(8 * (CHOLDAG_MAX_NBR + 1)); chol_dbg.zero(stream); }
-      const dim3 grid(1 + nbr * (nbr + 1) / 2);
-      if (dag32)
-        hipLaunchKernelGGL(k_chol_big_dag<float>, grid, dim3(CHOLBIG_THREADS), (size_t)CHOLBIG_LDS_BLOCKS * CholLay<float>::BS * sizeof(float), stream,
-                           Esys, n_sys, d_state.p, D2c.p, reinterpret_cast<float*>(chol_W.p), npad, reinterpret_cast<float*>(chol_Mimg.p),
-                           chol_dag_flags.p, ++chol_dag_epoch, chol_info.p, 0, kn.chol_f32_tau, chol_debug ? chol_dbg.p : nullptr);
-      hipLaunchKernelGGL(k_chol_big_dag<double>, grid, dim3(CHOLBIG_THREADS), lds, stream, Esys, n_sys, d_state.p, D2c.p, chol_W.p, npad,
-                         chol_Mimg.p, chol_dag_flags.p, ++chol_dag_epoch, chol_info.p, dag32 ? 1 : 0, 0.0,
-                         (chol_debug && !dag32) ? chol_dbg.p : nullptr);
-      if (chol_debug) {
-        const std::vector<long long> sv = read_stamps(chol_dbg, 8 * (CHOLDAG_MAX_NBR + 1));
-        fprintf(stderr, "[chol_dag%s, the walker, x10 ns: wait for W(c,c-1), W(c,c) | load | panel | downdate | factor+inverse | image stored | flag]\n", dag32 ? " on f32 lanes" : "");
-        for (int cc = 0; cc < nbr; ++cc) {
-          const long long* v = sv.data() + 8 * cc;
-          fprintf(stderr, "  c=%2d at %6lld:", cc, v[4] - sv[0]);
-          if (cc > 0) fprintf(stderr, " wait %4lld | load %4lld | panel %4lld | downdate %4lld |", v[1] - sv[8 * (cc - 1) + 7], v[2] - v[1], v[3] - v[2], v[4] - v[3]);
-          fprintf(stderr, " factor %4lld | image %4lld | flag %4lld | column %5lld\n", v[5] - v[4], v[6] - v[5], v[7] - v[6], cc > 0 ? v[7] - sv[8 * (cc - 1) + 7] : v[7] - v[0]);
-        }
-        chol_debug = false;
-      }
-    } else {
-      hipLaunchKernelGGL(k_chol_big_prepare, dim3(nbr * (nbr + 1) / 2), dim3(256), 0, stream, Esys, n_sys, d_state.p, D2c.p,
-                         chol_W.p, npad, chol_info.p);
-      for (int j = 0; j < nbr; ++j) {
-        const int q = nbr - 1 - j;
-        hipLaunchKernelGGL(k_chol_big_step, dim3(std::max(1, q * (q + 1) / 2)), dim3(CHOLBIG_THREADS), lds, stream, chol_W.p, npad, j,
-                           chol_Minv.p, chol_Ld.p, chol_info.p, d_state.p);
-      }
-    }
-    // the whole back substitution in one launch: block row = workgroup, x_b handed over as its own flag; block row 0 runs the epilogue.
-    // The launch stores its x into the first nbx * BB entries of the copy of its parity and empties the other copy as far as any
-    // launch before it -- of this solve or of an earlier one with another system size -- may have stored into it: after every launch
-    // the other copy is empty as a whole, so the next launch finds nothing but its own x there, whatever its size.
-    const int par = (int)(++chol_epoch & 1), xstride = (int)(chol_yv.n / 2);
-    const int nclear = std::max(chol_yv_ext[1 - par], nbx * BB);
-    hipLaunchKernelGGL(k_chol_big_back_all<T>, dim3(nbx), dim3(256), 0, stream, (const void*)chol_W.p, npad, n_sys, chol_Ld.p, chol_Minv.p,
-                       chol_yv.p, xstride, nclear, chol_epoch, chol_sol.p, chol_info.p, d_state.p, dag ? (const void*)chol_Mimg.p : (const void*)nullptr,
-                       dag32 ? 1 : 0, Esys, C, D2c.p, ps_lm(), delta_c.p, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr);
-    chol_yv_ext[1 - par] = 0;
-    chol_yv_ext[par] = nbx * BB;
   }
 
   // scal == nullptr: single rank, the partials are folded inside k_decide and no scalar exchange is needed
@@ -1788,120 +1571,9 @@ struct Engine : EngineBase {
                            E_tied.p, d_state.p);
         Esys = E_tied.p;
       }
-      const int32_t* tie = tied ? tie_map.p : nullptr;
-      const int32_t* first = tied ? tie_first.p : nullptr;
-      const int nb = (n_sys + CB - 1) / CB;
-      const CholRoute route = chol_route<T>(n_sys, n, kn, card_shared);
-      // the f32 image k_build_exchange left beside E_own (chol_img_ok: nothing has written E_own since)
-      const float* img = (chol_img_ok && !tied && E == E_own.p && chol_img_ld_of_route() != 0) ? chol_img.p : nullptr;
-      (void)img;
-      switch (route) {
-        case CholRoute::LL:
-        case CholRoute::LL_F32: {
-          // up to 256 unknowns (23 cameras): left-looking, factor on chip (sba_chol_ll.hpp)
-          if (chol_work.n < (size_t)nb * (nb + 1) / 2 * CB * CB) chol_work.alloc((size_t)CLL_MAX_NB * (CLL_MAX_NB + 1) / 2 * CB * CB);
-          if (chol_debug && chol_dbg.n < 128) { chol_dbg.alloc(128); chol_dbg.zero(stream); }
-          // fp32 engine (round 4): the right-looking all-in-LDS kernel on f32 lanes in front of it (the f32 triangle of up to 16 block
-          // rows fits the LDS: 20-float rows up to 14 block rows, 17-float rows at 15 and 16); the f64 kernel then only runs when that
-          // factorisation refused the system (LMState::chol_retry)
-          if constexpr (sizeof(T) == 4) {
-            if (route == CholRoute::LL_F32) {
-              if (nb <= 14) {
-                const size_t lds32 = ((size_t)(nb * (nb + 1) / 2) * CB * 20 + 2 * (size_t)nb * CB) * sizeof(float);
-                if (img)
-                  hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 20, true>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
-                                     ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau, img);
-                else
-                  hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 20>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
-                                     ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau, (const float*)nullptr);
-              } else {
-                const size_t lds32 = ((size_t)(nb * (nb + 1) / 2) * CB * 17 + 2 * (size_t)nb * CB) * sizeof(float);
-                if (img)
-                  hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 17, true>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
-                                     ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau, img);
-                else
-                  hipLaunchKernelGGL((k_cholesky_blocked<T, 16, 17>), dim3(1), dim3(CHOLB_LDS_THREADS), lds32, stream, Esys, C, d_state.p, D2c.p,
-                                     ps_lm(), delta_c.p, n_sys, tie, first, (long long*)nullptr, 1, kn.chol_f32_tau, (const float*)nullptr);
-              }
-            }
-          }
-          hipLaunchKernelGGL(k_cholesky_ll<T>, dim3(1), dim3(CLL_THREADS), CLL_LDS_BYTES, stream, Esys, C, d_state.p, D2c.p,
-                             ps_lm(), delta_c.p, n_sys, tie, first, chol_work.p, chol_debug ? chol_dbg.p : nullptr,
-                             route == CholRoute::LL_F32 ? 1 : 0);
-          if (chol_debug) {
-            const std::vector<long long> st = read_stamps(chol_dbg, 128);
-            if (nb > 6) {
-              const long long x0 = st[2 + 2 * 3], y0 = st[3 + 2 * 3];      // start of X_3 / Y_3 (thread 0)
-              fprintf(stderr, "[chol_ll step 3, cycles after the step's barrier, per wave] X done:");
-              for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[64 + w] - x0);
-              fprintf(stderr, " | Y done:");
-              for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[72 + w] - y0);
-              fprintf(stderr, "\n[chol_ll back substitution, block row 5] x done (per wave, from wave 0's):");
-              for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[80 + w] - st[80]);
-              fprintf(stderr, " | barrier passed %lld | update done:", st[96] - st[80]);
-              for (int w = 0; w < 8; ++w) fprintf(stderr, " %lld", st[88 + w] - st[96]);
-              fprintf(stderr, " | barrier passed %lld\n", st[97] - st[96]);
-            }
-            fprintf(stderr, "[chol_ll stamps, cycles] setup %lld  chol0 %lld |", st[1] - st[0], st[2] - st[1]);
-            for (int j = 0; j < nb; ++j) fprintf(stderr, " X%d %lld Y%d %lld |", j, st[3 + 2 * j] - st[2 + 2 * j], j, st[4 + 2 * j] - st[3 + 2 * j]);
-            fprintf(stderr, " backsub %lld  epilogue %lld  total %lld\n", st[3 + 2 * nb] - st[2 + 2 * nb], st[4 + 2 * nb] - st[3 + 2 * nb], st[4 + 2 * nb] - st[0]);
-            chol_debug = false;
-          }
-          break;
-        }
-        case CholRoute::BLOCKED: {
-          const size_t lds = ((size_t)(nb * (nb + 1) / 2) * CBS + 2 * (size_t)nb * CB) * sizeof(double);
-          if (chol_debug && chol_dbg.n == 0) { chol_dbg.alloc(64); }
-          bool with_img = false;
-          if constexpr (sizeof(T) == 4) {
-            if (img) {
-              with_img = true;
-              hipLaunchKernelGGL((k_cholesky_blocked<T, CHOLB_MAX_NB, 20, true>), dim3(1), dim3(CHOLB_LDS_THREADS), lds, stream, Esys, C, d_state.p,
-                                 D2c.p, ps_lm(), delta_c.p, n_sys, tie, first, chol_debug ? chol_dbg.p : nullptr, 1, kn.chol_f32_tau, img);
-            }
-          }
-          if (!with_img)
-            hipLaunchKernelGGL(k_cholesky_blocked<T>, dim3(1), dim3(CHOLB_LDS_THREADS), lds, stream, Esys, C, d_state.p, D2c.p,
-                               ps_lm(), delta_c.p, n_sys, tie, first, chol_debug ? chol_dbg.p : nullptr, (sizeof(T) == 4 && kn.chol_f32) ? 1 : 0,
-                               kn.chol_f32_tau, (const float*)nullptr);
-          if (chol_debug) {
-            const std::vector<long long> st = read_stamps(chol_dbg, 64);
-            fprintf(stderr, "[chol stamps, cycles] load %lld  chol0 %lld |", st[1] - st[0], st[2] - st[1]);
-            for (int j = 0; j < nb; ++j) fprintf(stderr, " B%d %lld C%d %lld |", j, st[3 + 2 * j] - st[2 + 2 * j], j, st[4 + 2 * j] - st[3 + 2 * j]);
-            fprintf(stderr, " backsub %lld  epilogue %lld  total %lld\n", st[3 + 2 * nb] - st[2 + 2 * nb], st[4 + 2 * nb] - st[3 + 2 * nb], st[4 + 2 * nb] - st[0]);
-            fprintf(stderr, "[chol C0, cycles after B0's barrier, per wave]");
-            for (int w = 0; w < CHOLB_LDS_THREADS / 64; ++w) fprintf(stderr, " %lld", st[40 + w] - st[3]);
-            fprintf(stderr, "\n");
-            chol_debug = false;
-          }
-          break;
-        }
-        case CholRoute::STREAM: {
-          // 17 .. 46 cameras: one workgroup, left-looking, finished block columns streamed through L2
-          if (chol_sol.n < (size_t)n_sys) { chol_sol.alloc(n_sys); chol_info.alloc(1); }
-          if (chol_work.n < (size_t)nb * (nb + 1) / 2 * CB * CB) chol_work.alloc((size_t)nb * (nb + 1) / 2 * CB * CB);
-          // panel (nb blocks) + rhs + as much staging as the 150 KB budget leaves (fewer, larger streaming rounds)
-          const size_t fixed = ((size_t)nb * CBS + (size_t)nb * CB) * sizeof(double);
-          const int scap = std::min(64, std::max(nb, (int)((150 * 1024 - fixed) / (CBS * sizeof(double)))));
-          const size_t lds = fixed + (size_t)scap * CBS * sizeof(double);
-          if (chol_debug && chol_dbg.n == 0) chol_dbg.alloc(64);
-          hipLaunchKernelGGL(k_chol_prepare, dim3((n_sys + 255) / 256), dim3(256), 0, stream, Esys, n_sys, d_state.p, D2c.p, chol_sol.p);
-          hipLaunchKernelGGL(k_cholesky_stream, dim3(1), dim3(CHOLB_THREADS), lds, stream, Esys, n_sys, chol_work.p, chol_sol.p,
-                             chol_info.p, d_state.p, scap, chol_debug ? chol_dbg.p : nullptr);
-          if (chol_debug) {
-            const std::vector<long long> st = read_stamps(chol_dbg, 8);
-            fprintf(stderr, "[chol_stream cycles] update %lld  factor %lld  solve %lld  write-back %lld  back-substitution %lld\n", st[0], st[1], st[2], st[3], st[4]);
-            chol_debug = false;
-          }
-          hipLaunchKernelGGL(k_chol_epilogue<T>, dim3(1), dim3(1024), 0, stream, Esys, C, n_sys, d_state.p, D2c.p, ps_lm(), delta_c.p,
-                             chol_sol.p, chol_info.p, tie, first);
-          break;
-        }
-        default:
-          // 24 .. 128 cameras: multi-workgroup factorisation (sba_chol_big.hpp)
-          launch_chol_big(Esys, n_sys, tied, route);
-          break;
-      }
+      chol.solve(plan_chol<T>(n_sys, n, kn, card_shared),
+                 {stream, Esys, n_sys, C, d_state.p, D2c.p, ps_lm(), delta_c.p, tied ? tie_map.p : nullptr, tied ? tie_first.p : nullptr},
+                 !tied && E == E_own.p);
       prof_end(KP_CHOL);
     } else {
       hipLaunchKernelGGL(k_nocam_step, dim3(1), dim3(64), 0, stream, d_state.p, E, n);

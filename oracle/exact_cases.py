@@ -236,7 +236,7 @@ RSQ_F32 = EPS["f32"]         # v_rsq_f32: one ulp (sba_chol_blocked.hpp:178)
 
 
 def chol_route(dtype, n, env=None, ncam=None):
-    """chol_route<T>(n_sys, ncam, knobs) of sba_engine.hpp:244-257 by name: the factorisation that n unknowns take when the rig has
+    """chol_route<T>(n_sys, ncam, knobs) of sba_chol_solve.hpp by name: the factorisation that n unknowns take when the rig has
     ncam = C * NCP camera parameters (a tied system of SBA_MODE_SHARED_INTR has n < ncam; default: ncam = n)."""
     env = env or {}
     ncam = n if ncam is None else ncam
@@ -255,7 +255,7 @@ def chol_route(dtype, n, env=None, ncam=None):
 
 def device_solve_bound(dtype, n, env=None, ncam=None):
     """(B, what ran) of the factorisation the engine's route runs on n unknowns when no f64 repeat was taken (report.reserved == 0),
-    after chol_route and read_knobs (sba_engine.hpp:244-257, :83-86); env holds the SBA_CHOL / SBA_CHOL_BIG / SBA_CHOL_F32 switches;
+    after chol_route (sba_chol_solve.hpp) and read_knobs (sba_knobs.hpp); env holds the SBA_CHOL / SBA_CHOL_BIG / SBA_CHOL_F32 switches;
     ncam: the rig's C * NCP where the system is a tied one (`chol_route` above names the same route).
     A pivot 1/sqrt(a_kk) off by delta scales row and column k of the factored matrix by (1 + delta)^2: 2 delta of d_i d_j.
       f64 engine, every kernel: f64, refined pivots.

@@ -59,13 +59,13 @@ def test_no_gpu_means_loud_failure(lib):
 
 
 def test_environment_switches_are_read_in_one_place_and_documented():
-    """The engine reads the environment in read_knobs (csrc/sba_engine.hpp) and nowhere else, and the SBA_* names it knows
+    """The engine reads the environment in read_knobs (csrc/sba_knobs.hpp) and nowhere else, and the SBA_* names it knows
     are exactly the ones INTEGRATION.md's table of environment switches lists."""
     csrc = os.path.join(ROOT, "lasercalib_amd", "csrc")
     sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip", ".h"))}
-    engine = sources["sba_engine.hpp"]
-    parser = re.search(r"\ninline Knobs read_knobs\(\) \{\n.*?\n\}\n", engine, flags=re.S)
-    assert parser, "read_knobs not found in sba_engine.hpp"
+    knobs = sources["sba_knobs.hpp"]
+    parser = re.search(r"\ninline Knobs read_knobs\(\) \{\n.*?\n\}\n", knobs, flags=re.S)
+    assert parser, "read_knobs not found in sba_knobs.hpp"
     total = sum(text.count("getenv(") for text in sources.values())
     assert total > 0 and parser.group(0).count("getenv(") == total, "getenv( outside read_knobs"
     literals = set()

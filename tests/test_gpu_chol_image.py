@@ -36,6 +36,8 @@ RIGS = [
     pytest.param(16, 5000, {}, id="16x5000-n176-more-chunks-than-workgroups"),
     pytest.param(5, 400, {}, id="5x400-n55-padded-tail-in-last-block"),
     pytest.param(17, 300, {}, id="17x300-n187-16-block-rows-20-float-rows"),
+    pytest.param(20, 300, {}, id="20x300-n220-14-block-rows-last-size-on-20-float-rows"),
+    pytest.param(21, 300, {}, id="21x300-n231-15-block-rows-first-size-on-17-float-rows"),
     pytest.param(23, 300, {}, id="23x300-n253-16-block-rows-17-float-rows"),
     pytest.param(16, 300, {"tangential": True}, id="16x300-tangential-n208"),
     pytest.param(16, 2000, {"visibility": 0.5, "min_cams_per_point": 4}, id="16x2000-masked-one-launch-route"),

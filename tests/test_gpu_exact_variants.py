@@ -12,7 +12,7 @@ SBA_MODE_POINTS_ONLY (k_nocam_step, the back substitution with dc = 0, the trial
   parts are exactly 0); fixed points bit-identical.
 SBA_MODE_SHARED_INTR (build_tie_tables, k_tie_system, the tie / first arguments of every factorisation and of chol_epilogue_body,
 chol_route(n_tied, n), the tied gradient of lm_finish), lambda0 = 1e-2, f, k1, k2 of every camera at their mean ("+shared"):
-  case            n    n_tied  f64 route  f32 route     (oracle/exact_cases.chol_route, the mirror of sba_engine.hpp:244-257)
+  case            n    n_tied  f64 route  f32 route     (oracle/exact_cases.chol_route, the mirror of chol_route in sba_chol_solve.hpp)
   d16x24+shared   176  131     BLOCKED    BLOCKED       k_cholesky_blocked, f32 lanes in the f32 engine
   g24x10+shared   264  195     LL         LL_F32        left-looking (its untied system takes BIG_DAG)
   v34x6+shared    374  275     BIG_DAG    BIG_DAG_F32   above 256 unknowns

@@ -174,7 +174,7 @@ def _run_sequence(C, dtype, env=None):
 def test_mode_sequence_on_one_handle_equals_fresh_handles(C, dtype):
     """FULL -> SHARED_INTR -> FULL -> POINTS_ONLY -> SHARED_INTR on one handle, from x0 each time, every step against a fresh
     handle.  The reduced system has n = P C unknowns in MODE_FULL and 3 + (P - 3) C tied ones in MODE_SHARED_INTR; the camera
-    counts put the two on different factorisations (chol_route) or different paddings (cholbig_npad = the next multiple of 64
+    counts put the two on different factorisations (chol_route, sba_chol_solve.hpp) or different paddings (cholbig_npad = the next multiple of 64
     above 16 ceil(n / 16)); MODE_POINTS_ONLY has no camera system and leaves the buffers of the other two as they are.
 
         cameras  n FULL / tied   MODE_FULL                                         MODE_SHARED_INTR
