@@ -1178,6 +1178,65 @@ int sba_refine_corners(int device, const uint8_t* frames, int64_t n_frames, int3
                        double* refined /*as corners*/, int32_t* status /*sba_corner_status bits*/,
                        int32_t* iterations /*or NULL*/, double* tensor /*n*3: a, b, c of the last system formed, or NULL*/);
 
+/* ---------------------------------------------------------------- local-mean masks: the first stage of the marker search
+ * The reference finds its ChArUco markers with cv2.aruco.ArucoDetector.detectMarkers on the grey plane of a frame
+ * (scripts/run_viewers.py:72-77, scripts/charuco_intrinsics.py:29-33, scripts/charuco_extrinsics.py:106).  Its first stage is
+ * cv.adaptiveThreshold(grey, 255, ADAPTIVE_THRESH_MEAN_C, THRESH_BINARY_INV, w, 7), once per window size w -- 3, 13 and 23 by
+ * default --, the only part of the search that touches every pixel, and several times; what follows works on contours.  A
+ * local mean is also what no global threshold replaces under uneven light.  sba_adaptive_threshold does it for a batch of
+ * frames and up to four windows in one call.  Fitting quads and decoding bits stays with the caller.  Stateless: no handle.
+ * Frames are described as for sba_detect_dots (8-bit, channels 1, 3 or 4 interleaved, any base, any pitches, host memory or
+ * with frames_on_device device memory read in place).
+ *
+ * Both outputs have ONE byte per pixel: row r of frame f of window k at base + k out_window_pitch + f out_frame_pitch +
+ * r out_row_pitch, base = out (the masks) or mean_out (the local means); either may be NULL, not both when n_frames > 0.  They
+ * share the three pitches and lie in host memory or, with out_on_device, in device memory of `device`, written in place.
+ * Padding -- between rows, frames and windows -- is never written.  The outputs must not overlap the frames.  A mask in
+ * device memory is a one-channel frame that sba_detect_blobs labels at threshold 127.
+ *
+ * The rule -- this is the function's definition; b = block[k], all integers:
+ * 1. v(x, y) is byte `channel` of the pixel, or with channel = -1 the grey value of its first three bytes c0, c1, c2,
+ *      v = (c0*w0 + c1*w1 + c2*w2 + 2^14) >> 15
+ *    formed per source pixel: rule 1 of sba_resize_frames, with the same gray_w and the same errors.
+ * 2. The border is replicated (OpenCV's BORDER_REPLICATE | BORDER_ISOLATED): outside the frame v is taken at
+ *    (clamp(x, 0, width - 1), clamp(y, 0, height - 1)).
+ * 3. S_k(x, y) is the sum of v over the b x b window centred on (x, y); S_k <= 255 * 127^2 = 4 112 895.
+ * 4. mean_k = floor((2 S_k + b^2) / (2 b^2)): the integer nearest to S_k / b^2, which is unique because b^2 is odd (no ties).
+ *    OpenCV's saturate_cast<uchar>(sum * scale) equals it for every b <= 127, in its float32 form
+ *    rint(fl32(S) * fl32(1.0f / b^2)) and in its float64 form alike (tests/test_adaptive_host.py checks every S of every b;
+ *    the float32 form first differs at b = 165: that is where the limit of 127 comes from).
+ * 5. d = v - mean_k.  invert = 0 (THRESH_BINARY):      out = d >  -delta[k] ? max_value : 0
+ *                     invert = 1 (THRESH_BINARY_INV):  out = d <= -delta[k] ? max_value : 0
+ *    This is adaptiveThreshold's table with idelta = delta.  OpenCV forms idelta from its floating C as ceil(C) for BINARY and
+ *    floor(C) for BINARY_INV; that conversion is the caller's (lasercalib_amd.imaging does it).
+ * 6. mean_out, where given, holds mean_k: cv.blur / cv.boxFilter(normalize=True) of the plane under the same border.
+ * Frames pass through the device in chunks (host frames through two staging buffers, host outputs through one packed buffer
+ * per window and output); device memory does not grow with n_frames, and any chunk_frames gives the same bytes.  n_frames = 0
+ * returns SBA_OK and writes nothing.  The bytes are the same from run to run.
+ * Errors, all checked before any device work (text "sba_adaptive_threshold: ..." in sba_last_error(NULL)), both outputs left
+ * untouched: the frame errors of sba_detect_dots; SBA_ERR_INVALID for n_windows outside 1..4, a block that is even or outside
+ * 3..127, a delta outside -256..256, invert not 0 or 1, max_value outside 0..255, a channel outside -1..channels-1, channel =
+ * -1 with channels == 1, gray weights that are negative or do not sum to 2^15, out_row_pitch < width, out_frame_pitch <
+ * height out_row_pitch, n_windows > 1 with out_window_pitch < n_frames out_frame_pitch, and both outputs NULL with
+ * n_frames > 0. */
+typedef struct {
+  int32_t n_windows;         /* 1..4 */
+  int32_t block[4];          /* odd, 3..127: side of the window of window k */
+  int32_t delta[4];          /* -256..256: OpenCV's C, already an integer (rule 5) */
+  int32_t invert;            /* 0: THRESH_BINARY, 1: THRESH_BINARY_INV (what ArUco uses) */
+  int32_t max_value;         /* 0..255; 0 means 255 */
+  int32_t channel;           /* 0..channels-1, or -1: the grey value with gray_w, as sba_corner_opts */
+  int32_t gray_w[3];         /* as sba_resize_opts: all zero = {3735, 19235, 9798} */
+  int32_t frames_on_device, out_on_device, chunk_frames;   /* as sba_resize_opts */
+  int32_t reserved[4];
+} sba_adaptive_opts;         /* 88 bytes */
+int sba_adaptive_threshold(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width,
+                           int32_t channels /*1, 3 or 4*/, int64_t row_pitch, int64_t frame_pitch,
+                           const sba_adaptive_opts* opts /*NULL: detectMarkers' call: windows 3, 13, 23, delta 7, inverted, 255,
+                                                           grey (channel 0 of one plane)*/,
+                           int64_t out_row_pitch, int64_t out_frame_pitch, int64_t out_window_pitch,
+                           uint8_t* out /*or NULL*/, uint8_t* mean_out /*or NULL*/);
+
 /* ---------------------------------------------------------------- multi-GPU inside the library (RCCL over xGMI)
  * One process per GPU, one handle per process holding a contiguous slice of the points and all their observations
  * (cameras replicated).  After sba_comm_init the handle's sba_solve_lm runs the sharded loop itself: per LM trial ONE

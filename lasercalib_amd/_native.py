@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = (
     "sba_unproject_rows", "sba_unproject", "sba_detect_dots", "sba_detect_blobs",
     "sba_undistort_frames", "sba_background_accumulate", "sba_background_suppress", "sba_convert_frames", "sba_resize_frames",
     "sba_frames_to_yuv", "sba_undistort_yuv", "sba_frame_histograms", "sba_warp_frames",
-    "sba_refine_corners",
+    "sba_refine_corners", "sba_adaptive_threshold",
 )
 
 
@@ -127,6 +127,28 @@ class CornerOpts(C.Structure):                                            # sba_
     _fields_ = [("eps", C.c_double), ("frames_on_device", C.c_int32), ("chunk_frames", C.c_int32), ("channel", C.c_int32),
                 ("gray_w", C.c_int32 * 3), ("win_x", C.c_int32), ("win_y", C.c_int32), ("zero_x", C.c_int32), ("zero_y", C.c_int32),
                 ("max_iter", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class AdaptiveOpts(C.Structure):                                          # sba_adaptive_opts
+    _fields_ = [("n_windows", C.c_int32), ("block", C.c_int32 * 4), ("delta", C.c_int32 * 4), ("invert", C.c_int32),
+                ("max_value", C.c_int32), ("channel", C.c_int32), ("gray_w", C.c_int32 * 3), ("frames_on_device", C.c_int32),
+                ("out_on_device", C.c_int32), ("chunk_frames", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+ADAPTIVE_MAX_WINDOWS, ADAPTIVE_MAX_BLOCK, ADAPTIVE_MAX_DELTA = 4, 127, 256
+# the columns a wave reads in one step and the tile of a workgroup (csrc/sba_adaptive.hpp: AT_STEP, at_tile), for the tests that
+# straddle them
+ADAPTIVE_STEP = 256
+
+
+def adaptive_tile(max_block):
+    """(columns, rows, row segments) of the tile a workgroup takes when ``max_block`` is the largest window of the call."""
+    R = int(max_block) // 2
+    L = (R + 1 + 3) // 4 * 4
+    if R <= 48:
+        return (ADAPTIVE_STEP - L - R) // 4 * 4, 64 if R <= 32 else 32, 1
+    tw = 128 if (32 + 2 * R) * ((128 + L + R + 3) // 4 * 4) <= 32768 else 64
+    return tw, 32, 256 // tw
 
 
 # sba_corner_status bits
@@ -566,6 +588,8 @@ def load():
                                            C.POINTER(HistOpts), C.c_void_p, C.c_void_p]),
         "sba_refine_corners": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, ip, dp,
                                          C.POINTER(CornerOpts), dp, dp, C.c_void_p, C.c_void_p, dp]),
+        "sba_adaptive_threshold": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                             C.POINTER(AdaptiveOpts), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
         "sba_resize_frames": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_int64, C.c_int64, C.POINTER(ResizeOpts), C.c_void_p]),
         "sba_align": (C.c_int, [H, C.POINTER(AlignOpts), dp, dp, dp, dp, C.POINTER(AlignReport)]),
@@ -1365,6 +1389,78 @@ def refine_corners(frames, corner_start, corners, win=(3, 3), zero_zone=(-1, -1)
     _check(lib.sba_refine_corners(device, C.c_void_p(_synced(device, frames)), B, H, W, Cn, sr, sf, _iptr(start), _dptr(xy),
                                   C.byref(opts), _dptr(weights), _dptr(refined), status.ctypes.data, iterations.ctypes.data, _dptr(tens)))
     return refined, status, iterations, tens
+
+
+def _windows_out(name, a, K, B, H, W, device):
+    """A caller's (K, B, H, W) uint8 output of adaptive_threshold -> (is a tensor, address, window, frame and row stride)."""
+    tensor = _is_tensor(a)
+    if not tensor and not (isinstance(a, np.ndarray) and a.flags.writeable):
+        raise ValueError(f"{name} must be a writeable numpy array or a tensor on the device")
+    if tuple(a.shape) != (K, B, H, W):
+        raise ValueError(f"{name} has the shape {tuple(a.shape)}, expected {(K, B, H, W)}")
+    _t, _a, _n, _H, _W, _C, sr, sf = _frame_layout(a[0], device)           # checks dtype, device and the strides inside a window
+    sw = int(a.stride(0) if tensor else a.strides[0])
+    if K == 1 or B * H * W == 0:
+        sw = max(sw, B * sf)
+    if sw < B * sf:
+        raise ValueError(f"{name}: the windows must lie in ascending order, a window's frames in front of the next window's")
+    return tensor, _addr(a), sw, sf, sr
+
+
+def adaptive_threshold(frames, blocks, deltas, invert=True, max_value=255, channel=-1, gray_w=None, out=None, mean_out=None,
+                       out_on_device=None, chunk_frames=0, device=0):
+    """sba_adaptive_threshold (include/sba_hip.h): the local-mean masks of ``frames`` (as for ``detect_dots``: numpy, or a torch
+    tensor on ``device`` read in place) for the K <= 4 odd window sizes ``blocks`` and integer ``deltas`` -> (masks, means), each
+    (K, B, H, W) uint8 or None.  ``channel`` -1 is the grey value with ``gray_w`` (None: OpenCV's of B, G, R).  ``out``: None
+    allocates the masks, False leaves them out, else the caller's array; ``mean_out``: None leaves the means out, True allocates
+    them, else the caller's array.  What is allocated lies on the side the frames are on (``out_on_device`` True / False
+    overrides that).  A caller's array is a writeable numpy array or a tensor on ``device`` of the shape (K, B, H, W), which may
+    be a view into a larger array: its strides are the pitches, pixels contiguous, and what lies between is left untouched; when
+    both are the caller's they must lie on the same side with the same strides.  ``lasercalib_amd.imaging.adaptive_threshold``
+    is the public face of this call."""
+    lib = load()
+    tensor, frames, B, H, W, Cn, sr, sf = _frame_layout(frames, device)
+    blocks = list(blocks)
+    K = len(blocks)
+    blocks = _int32s(blocks, K, "blocks must be 32-bit integers")
+    if not 1 <= K <= ADAPTIVE_MAX_WINDOWS:
+        raise ValueError(f"blocks must hold 1..{ADAPTIVE_MAX_WINDOWS} window sizes, got {K}")
+    deltas = _int32s(deltas, K, f"deltas must be {K} 32-bit integers, one per window")
+    opts = AdaptiveOpts()
+    opts.n_windows, opts.invert, opts.max_value, opts.channel = K, 1 if invert else 0, int(max_value), int(channel)
+    opts.block[:K], opts.delta[:K] = blocks, deltas
+    if gray_w is not None:
+        opts.gray_w = (C.c_int32 * 3)(*_int32s(gray_w, 3, "gray_w must be three 32-bit integers"))
+    if out is False and mean_out is None:
+        raise ValueError("neither the masks nor the means are asked for")
+    given = [(n, a) for n, a in (("out", out), ("mean_out", mean_out)) if a is not None and a is not False and a is not True]
+    if out is True:
+        out = None
+    layouts = [_windows_out(n, a, K, B, H, W, device) for n, a in given]
+    if len(layouts) == 2 and (layouts[0][0] != layouts[1][0] or layouts[0][2:] != layouts[1][2:]):
+        raise ValueError("out and mean_out must lie on the same side and have the same strides: the call has one set of pitches")
+    if layouts:
+        out_tensor, _p, sw, osf, osr = layouts[0]
+    else:
+        out_tensor, sw, osf, osr = tensor if out_on_device is None else bool(out_on_device), B * H * W, H * W, W
+
+    def fresh():
+        if out_tensor:
+            import torch
+            return torch.empty((K, B, H, W), dtype=torch.uint8, device=f"cuda:{device}")
+        return np.empty((K, B, H, W), np.uint8)
+
+    if layouts and (out is None or mean_out is True):                      # allocated beside a caller's array: in its strides
+        if (sw, osf, osr) != (B * H * W, H * W, W):
+            raise ValueError("out and mean_out share the pitches: pass both, or neither, when one is a view with strides")
+    out = None if out is False else fresh() if out is None else out
+    mean_out = fresh() if mean_out is True else mean_out
+    opts.frames_on_device, opts.out_on_device, opts.chunk_frames = 1 if tensor else 0, 1 if out_tensor else 0, int(chunk_frames)
+    ptr = _synced(device, frames, also=out_tensor)
+    _check(lib.sba_adaptive_threshold(device, C.c_void_p(ptr), B, H, W, Cn, sr, sf, C.byref(opts), osr, osf, sw,
+                                      C.c_void_p(None if out is None else _addr(out)),
+                                      C.c_void_p(None if mean_out is None else _addr(mean_out))))
+    return out, mean_out
 
 
 class Problem:

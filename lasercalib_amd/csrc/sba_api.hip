@@ -49,6 +49,9 @@ int sba_corners_call(int device, const uint8_t* frames, int64_t n_frames, int32_
                      int64_t row_pitch, int64_t frame_pitch, const int64_t* corner_start, const double* corners,
                      const sba_corner_opts& opts, const double* weights, double* refined, int32_t* status, int32_t* iterations,
                      double* tensor);
+int sba_adaptive_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                      int64_t row_pitch, int64_t frame_pitch, const sba_adaptive_opts& opts, int64_t out_row_pitch, int64_t out_frame_pitch,
+                      int64_t out_window_pitch, uint8_t* out, uint8_t* mean_out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -766,6 +769,43 @@ int sba_refine_corners(int device, const uint8_t* frames, int64_t n_frames, int3
   return guarded(nullptr, [&] {
     return sba_corners_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, corner_start, corners, o, weights,
                             refined, status, iterations, tensor);
+  });
+}
+
+int sba_adaptive_threshold(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                           int64_t row_pitch, int64_t frame_pitch, const sba_adaptive_opts* opts, int64_t out_row_pitch,
+                           int64_t out_frame_pitch, int64_t out_window_pitch, uint8_t* out, uint8_t* mean_out) {
+  const char* fn = "sba_adaptive_threshold";
+  sba_adaptive_opts o{};
+  o.n_windows = 3; o.block[0] = 3; o.block[1] = 13; o.block[2] = 23; o.delta[0] = o.delta[1] = o.delta[2] = 7;   // detectMarkers' call
+  o.invert = 1; o.channel = channels == 1 ? 0 : -1;
+  if (opts) o = *opts;
+  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel == -1 ? 0 : o.channel, 0);
+  if (rc) return rc;
+  if (o.n_windows < 1 || o.n_windows > 4) return detect_invalid(fn, "n_windows must be in 1..4");
+  for (int k = 0; k < o.n_windows; ++k) {
+    if (o.block[k] < 3 || o.block[k] > 127 || o.block[k] % 2 == 0) return detect_invalid(fn, "a block must be odd and in 3..127");
+    if (o.delta[k] < -256 || o.delta[k] > 256) return detect_invalid(fn, "a delta must be in -256..256");
+  }
+  if (o.invert != 0 && o.invert != 1) return detect_invalid(fn, "invert must be 0 (binary) or 1 (binary, inverted)");
+  if (o.max_value < 0 || o.max_value > 255) return detect_invalid(fn, "max_value must be in 0..255");
+  if (o.channel == -1) {
+    if (channels == 1) return detect_invalid(fn, "channel -1 (gray) needs 3 or 4 channels");
+    if (o.gray_w[0] == 0 && o.gray_w[1] == 0 && o.gray_w[2] == 0) { o.gray_w[0] = 3735; o.gray_w[1] = 19235; o.gray_w[2] = 9798; }   // OpenCV's B, G, R
+    if (o.gray_w[0] < 0 || o.gray_w[1] < 0 || o.gray_w[2] < 0) return detect_invalid(fn, "a gray weight is negative");
+    if ((int64_t)o.gray_w[0] + o.gray_w[1] + o.gray_w[2] != 1 << 15) return detect_invalid(fn, "the gray weights must sum to 2^15");
+  }
+  rc = out_pitch_invalid(fn, n_frames, height, width, out_row_pitch, out_frame_pitch, "out_row_pitch is smaller than width", "height");
+  if (rc) return rc;
+  if (o.n_windows > 1 && (__int128)n_frames * out_frame_pitch > out_window_pitch)
+    return detect_invalid(fn, "out_window_pitch is smaller than n_frames * out_frame_pitch");
+  if ((__int128)o.n_windows * out_window_pitch > INT64_MAX) return detect_invalid(fn, "n_windows * out_window_pitch overflows");
+  if (!out && !mean_out && n_frames > 0) return detect_invalid(fn, "null out and null mean_out");
+  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (rc || n_frames == 0) return rc;
+  return guarded(nullptr, [&] {
+    return sba_adaptive_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, out_row_pitch, out_frame_pitch,
+                             out_window_pitch, out, mean_out);
   });
 }
 

@@ -2,7 +2,8 @@
 // connected components), the undistortion (sba_undistort.hpp), the background statistics (sba_background.hpp), the
 // conversion of decoder frames (sba_convert.hpp), its way back to encoder frames (sba_yuv.hpp), the area-averaged previews
 // (sba_resize.hpp), the undistortion of YUV 4:2:0 frames plane by plane (sba_undistort_yuv.hpp), the per-frame value
-// histograms (sba_hist.hpp), the plane views and virtual cameras (sba_warp.hpp) and the sub-pixel corner refinement (sba_corners.hpp).  They do not depend on the engine's camera model, so they are compiled once, in a translation
+// histograms (sba_hist.hpp), the plane views and virtual cameras (sba_warp.hpp) the sub-pixel corner refinement (sba_corners.hpp) and the local-mean masks
+// (sba_adaptive.hpp).  They do not depend on the engine's camera model, so they are compiled once, in a translation
 // unit of their own.
 #include "sba_blobs.hpp"
 #include "sba_undistort.hpp"
@@ -14,6 +15,7 @@
 #include "sba_hist.hpp"
 #include "sba_warp.hpp"
 #include "sba_corners.hpp"
+#include "sba_adaptive.hpp"
 
 int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
@@ -92,4 +94,11 @@ int sba_corners_call(int device, const uint8_t* frames, int64_t n_frames, int32_
                      double* tensor) {
   return sba_detect::corners_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, corner_start, corners, opts,
                                   weights, refined, status, iterations, tensor);
+}
+
+int sba_adaptive_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
+                      int64_t row_pitch, int64_t frame_pitch, const sba_adaptive_opts& opts, int64_t out_row_pitch, int64_t out_frame_pitch,
+                      int64_t out_window_pitch, uint8_t* out, uint8_t* mean_out) {
+  return sba_detect::adaptive_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, opts, out_row_pitch,
+                                   out_frame_pitch, out_window_pitch, out, mean_out);
 }

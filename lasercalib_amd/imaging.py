@@ -29,6 +29,9 @@ the reference: ``cv.getOptimalNewCameraMatrix``, ``cv.undistort``, ``probe_monot
 * :func:`refine_corners`, :func:`corner_sub_pix`, :class:`CornerRefinement`, :func:`corner_weights` -- ``cv.cornerSubPix`` for the
   marker corners of a batch of frames (sba_refine_corners; ``scripts/charuco_intrinsics.py:39-44``), with what OpenCV throws away:
   the window's structure tensor, which tells an edge from a corner and gives every corner a weight
+* :func:`adaptive_threshold`, :func:`adaptive_threshold_cv`, :func:`marker_threshold_windows` -- ``cv.adaptiveThreshold`` with
+  ``ADAPTIVE_THRESH_MEAN_C`` for a batch of frames and up to four window sizes at once (sba_adaptive_threshold): the first stage
+  of ``cv2.aruco``'s ``detectMarkers`` (``scripts/run_viewers.py:72-77``), whose masks ``find_laser_blobs`` can label in place
 
 Sizes are ``(width, height)``, as in OpenCV.  Pixels follow the rule written out in include/sba_hip.h: a float64 model, the
 source position on a 1/32-pixel grid, integer bilinear weights.  That is OpenCV's scheme, but OpenCV rounds its weight table to
@@ -47,7 +50,9 @@ SBA_WARP_BEHIND = WARP_BEHIND
 __all__ = ["Lens", "undistort_frames", "undistort_yuv", "optimal_new_camera_matrix", "invertible_region", "BackgroundModel",
            "YuvMatrix", "convert_frames", "RgbMatrix", "frames_to_yuv", "resize_frames", "mosaic", "frame_histograms", "FrameHistograms", "SBA_UNDIST_OUTSIDE", "SBA_UNDIST_FOLDED", "SBA_UNDIST_RANGE",
            "warp_frames", "plane_view", "PlaneGrid", "virtual_camera_matrix", "plane_mosaic", "SBA_WARP_BEHIND",
-           "refine_corners", "corner_sub_pix", "corner_window", "corner_weights", "CornerRefinement"]
+           "refine_corners", "corner_sub_pix", "corner_window", "corner_weights", "CornerRefinement",
+           "adaptive_threshold", "adaptive_threshold_cv", "marker_threshold_windows", "ADAPTIVE_THRESH_MEAN_C", "THRESH_BINARY",
+           "THRESH_BINARY_INV"]
 
 
 class Lens:
@@ -998,6 +1003,94 @@ def corner_weights(result, floor=0.0):
         med = np.median(lam[ok])
         w[ok] = np.maximum(lam[ok] / med, float(floor)) if med > 0 else 1.0
     return w
+
+
+ADAPTIVE_THRESH_MEAN_C, THRESH_BINARY, THRESH_BINARY_INV = 0, 0, 1      # OpenCV's constants
+
+
+def marker_threshold_windows(win_min=3, win_max=23, win_step=10):
+    """The window sizes ``cv2.aruco``'s ``detectMarkers`` thresholds with (its adaptiveThreshWinSizeMin, -Max and -Step):
+    ``range(win_min, win_max + 1, win_step)``, an even size made odd by adding 1.  The default gives (3, 13, 23)."""
+    win_min, win_max, win_step = int(win_min), int(win_max), int(win_step)
+    if win_min < 3 or win_max < win_min or win_step < 1:
+        raise ValueError(f"need 3 <= win_min <= win_max and win_step >= 1, got {(win_min, win_max, win_step)}")
+    return tuple(w + 1 if w % 2 == 0 else w for w in range(win_min, win_max + 1, win_step))
+
+
+def adaptive_threshold(frames, block_size, C=7, threshold_type="binary_inv", max_value=255, channel=None, return_mean=False,
+                       out=None, channel_order="bgr", chunk_frames=0, device=0):
+    """``cv.adaptiveThreshold(grey, max_value, ADAPTIVE_THRESH_MEAN_C, type, block_size, C)`` for a batch of frames, on the GPU
+    (sba_adaptive_threshold, include/sba_hip.h): a pixel is set where it is darker (``"binary_inv"``, what ArUco uses) or
+    brighter (``"binary"``) than the mean of the ``block_size`` x ``block_size`` window around it, less ``C``.
+
+    ``frames`` as for ``feature_detection.find_laser_dots``: (B, H, W[, C]) uint8, numpy or a tensor on ``device`` read in
+    place.  ``block_size``: an odd int in 3..127 -> (B, H, W), or a sequence of up to four -> (K, B, H, W): all windows in one
+    call, the frames read once (:func:`marker_threshold_windows` gives ArUco's).  ``C``: a number or one per window, turned
+    into the integer OpenCV compares with (``ceil`` for binary, ``floor`` for binary_inv).  ``channel``: the byte of a pixel
+    that is read, or -1 for the grey value of ``resize_frames`` (``channel_order`` as there); None is -1 for colour frames and
+    0 for one plane.  ``return_mean``: also return the local means (``cv.blur`` with a replicated border) -> (masks, means).
+    The result lies where the frames lie, or is the caller's ``out`` of the result's shape (a view with strides is written in
+    place); a mask left on the device is a one-channel frame that ``find_laser_blobs`` labels at ``threshold=127``."""
+    kind = {"binary": 0, "binary_inv": 1, THRESH_BINARY: 0, THRESH_BINARY_INV: 1}.get(
+        threshold_type.lower() if isinstance(threshold_type, str) else threshold_type)
+    if kind is None:
+        raise ValueError(f"threshold_type must be 'binary' or 'binary_inv', not {threshold_type!r}")
+    single = np.ndim(block_size) == 0
+    blocks = [block_size] if single else list(block_size)
+    if not 1 <= len(blocks) <= _native.ADAPTIVE_MAX_WINDOWS:
+        raise ValueError(f"block_size must be one window size or up to {_native.ADAPTIVE_MAX_WINDOWS}, got {len(blocks)}")
+    for b in blocks:
+        if int(b) != b or int(b) % 2 == 0 or not 3 <= int(b) <= _native.ADAPTIVE_MAX_BLOCK:
+            raise ValueError(f"a block size must be an odd integer in 3..{_native.ADAPTIVE_MAX_BLOCK}, got {b!r}")
+    cs = [C] * len(blocks) if np.ndim(C) == 0 else list(C)
+    if len(cs) != len(blocks):
+        raise ValueError(f"C must be one number or one per window ({len(blocks)}), got {len(cs)}")
+    if not all(np.isfinite(float(c)) for c in cs):
+        raise ValueError(f"C must be finite, got {C!r}")
+    deltas = [int(np.floor(float(c))) if kind else int(np.ceil(float(c))) for c in cs]
+    if any(abs(d) > _native.ADAPTIVE_MAX_DELTA for d in deltas):
+        raise ValueError(f"C must lie in -{_native.ADAPTIVE_MAX_DELTA}..{_native.ADAPTIVE_MAX_DELTA}, got {C!r}")
+    if not 0 < int(max_value) <= 255:
+        raise ValueError(f"max_value must be in 1..255, got {max_value!r}")
+    shape = tuple(frames.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError(f"frames must be (B, H, W, C) or (B, H, W), got {shape}")
+    Cn = int(shape[3]) if len(shape) == 4 else 1
+    channel = (0 if Cn == 1 else -1) if channel is None else int(channel)
+    if not (-1 <= channel < Cn) or (channel == -1 and Cn == 1):
+        raise ValueError(f"channel must be in 0..{Cn - 1}" + (" or -1 (gray)" if Cn > 1 else "") + f", got {channel}")
+    gray_w = _gray_weights(True, channel_order) if channel == -1 else None
+    if out is not None and single:
+        if len(out.shape) != 3:
+            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {shape[:3]}")
+        out = out[None]
+    masks, means = _native.adaptive_threshold(frames, [int(b) for b in blocks], deltas, invert=bool(kind), max_value=int(max_value),
+                                              channel=channel, gray_w=gray_w, out=out, mean_out=True if return_mean else None,
+                                              chunk_frames=chunk_frames, device=device)
+    if single:
+        masks, means = masks[0], None if means is None else means[0]
+    return (masks, means) if return_mean else masks
+
+
+def adaptive_threshold_cv(src, maxValue, adaptiveMethod, thresholdType, blockSize, C, device=0):
+    """``cv.adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C)`` for one 2-D grey image -> (H, W)
+    uint8.  ``adaptiveMethod`` must be ``ADAPTIVE_THRESH_MEAN_C`` (0), ``thresholdType`` ``THRESH_BINARY`` (0) or
+    ``THRESH_BINARY_INV`` (1); ``maxValue`` is saturated to 0..255 as OpenCV does, and 0 gives an empty mask."""
+    if adaptiveMethod != ADAPTIVE_THRESH_MEAN_C:
+        raise ValueError(f"only ADAPTIVE_THRESH_MEAN_C (0) is implemented, got adaptiveMethod = {adaptiveMethod!r}")
+    if thresholdType not in (THRESH_BINARY, THRESH_BINARY_INV):
+        raise ValueError(f"thresholdType must be THRESH_BINARY (0) or THRESH_BINARY_INV (1), got {thresholdType!r}")
+    src = src if _native._is_tensor(src) else np.ascontiguousarray(src)
+    if len(src.shape) != 2:
+        raise ValueError(f"src must be one grey image (H, W), got the shape {tuple(src.shape)}")
+    top = int(min(max(np.rint(float(maxValue)), 0), 255))
+    if top == 0:
+        if _native._is_tensor(src):
+            return src.new_zeros(tuple(src.shape))
+        if src.dtype != np.uint8:
+            raise ValueError(f"frames must be uint8, not {src.dtype}")
+        return np.zeros(src.shape, np.uint8)
+    return adaptive_threshold(src[None], int(blockSize), C=C, threshold_type=thresholdType, max_value=top, device=device)[0]
 
 
 class BackgroundModel:
