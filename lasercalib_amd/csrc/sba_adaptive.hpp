@@ -205,11 +205,11 @@ inline void at_launch(const AtParams& P, int channels, int64_t nf, hipStream_t s
 
 // Arguments are checked by the caller (sba_api.hip): n_frames > 0, the windows, the weights set, one output at least.  Chunks,
 // staging and outputs are those of sba_frames.hpp: a FrameOutput per window and kind of output, which share the pitches.
-inline int adaptive_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                         int64_t row_pitch, int64_t frame_pitch, const sba_adaptive_opts& o, int64_t out_row_pitch,
-                         int64_t out_frame_pitch, int64_t out_window_pitch, uint8_t* out, uint8_t* mean_out) {
+int adaptive_call(const FrameBatch& B, const sba_adaptive_opts& o, const FrameOut& out, int64_t out_window_pitch, uint8_t* mean_out) {
+  const int64_t n_frames = B.n_frames;
+  const int32_t height = B.height, width = B.width, channels = B.channels;
   if (height == 0 || width == 0) return SBA_OK;
-  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(B.device));
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
   const int K = o.n_windows;
   AtParams P{};
@@ -222,14 +222,16 @@ inline int adaptive_call(int device, const uint8_t* frames, int64_t n_frames, in
     P.R = std::max(P.R, P.r[k]);
   }
   at_tile(P);
-  const int64_t plane = (int64_t)width * height, in_bytes = plane * channels, out_bytes = plane * K * ((out ? 1 : 0) + (mean_out ? 1 : 0));
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, std::max(in_dev ? 0 : in_bytes, out_dev ? 0 : out_bytes));
+  const int64_t out_bytes = (int64_t)width * height * K * ((out.out ? 1 : 0) + (mean_out ? 1 : 0));
+  // neither policy of chunk_of: a side counts only when it is host memory itself, so masks that stay on the device, up to eight
+  // planes a frame, do not shrink the staging copies of host frames
+  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, std::max(in_dev ? 0 : frame_bytes(B), out_dev ? 0 : out_bytes));
   std::optional<FrameOutput> O[2][AT_MAX_WINDOWS];                        // masks, means
   for (int k = 0; k < K; ++k) {
-    if (out) O[0][k].emplace(out + k * out_window_pitch, out_row_pitch, out_frame_pitch, width, height, out_dev, chunk);
-    if (mean_out) O[1][k].emplace(mean_out + k * out_window_pitch, out_row_pitch, out_frame_pitch, width, height, out_dev, chunk);
+    if (out.out) O[0][k].emplace(FrameOut{out.out + k * out_window_pitch, out.row_pitch, out.frame_pitch}, width, height, out_dev, chunk);
+    if (mean_out) O[1][k].emplace(FrameOut{mean_out + k * out_window_pitch, out.row_pitch, out.frame_pitch}, width, height, out_dev, chunk);
   }
-  const FramePlane src{frames, row_pitch, frame_pitch, (int64_t)width * channels, height};
+  const FramePlane src = frame_plane(B);
   frames_in_chunks(
       &src, 1, n_frames, in_dev, chunk,
       [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {

@@ -1,8 +1,15 @@
 // sba_api.hip -- C ABI (include/sba_hip.h) over the per-camera-model engines.  gfx950 only; no CPU fallback:
 // every entry point fails with SBA_ERR_NO_DEVICE / SBA_ERR_HIP when the GPU is not usable.
+//
+// The frame entry points (sba_detect_dots ... sba_adaptive_threshold, the second half of this file) all take one path: the ABI
+// scalars become a FrameBatch (and a FrameOut where frames are written), the shared checks and the entry point's own run in the
+// order tests/test_frame_arg_errors.py pins, and the call ends in the sba_detect::*_call that sba_frame_calls.hpp declares.
 #include "sba_common.hpp"
+#include "sba_frame_calls.hpp"
 
 using namespace sba_host;
+using sba_detect::FrameBatch;
+using sba_detect::FrameOut;
 
 // factories of the two engine translation units (sba_engine_ncp11.hip: the reference's 11-parameter radial camera,
 // sba_engine_ncp13.hip: 13 parameters, radial + tangential)
@@ -14,44 +21,6 @@ int sba_unproject_rows_ncp11(int device, int64_t n, const double* uv, const doub
                              double* xn_out, double* origin_out, double* dir_out, double* points_out, double* depth_out, int32_t* status_out);
 int sba_unproject_rows_ncp13(int device, int64_t n, const double* uv, const double* cam_rows, const double* planes, int64_t n_planes,
                              double* xn_out, double* origin_out, double* dir_out, double* points_out, double* depth_out, int32_t* status_out);
-int sba_detect_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                    int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& opts, uint64_t* sums, int32_t* box, double* centroid,
-                    int32_t* status);
-int sba_blobs_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                   int64_t row_pitch, int64_t frame_pitch, const sba_blob_opts& opts, int32_t* n_components, uint64_t* blobs,
-                   int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out);
-int sba_undistort_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                       int64_t row_pitch, int64_t frame_pitch, const sba_lens& lens, const double* new_k, int32_t out_height,
-                       int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out,
-                       uint8_t* flags_out, int32_t* map_out);
-int sba_bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                           int64_t row_pitch, int64_t frame_pitch, const sba_background_accumulate_opts& opts, const uint8_t* use,
-                           uint32_t* sum, uint64_t* sumsq, uint32_t* hot, uint8_t* vmax, uint64_t* n_used);
-int sba_bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                         int64_t row_pitch, int64_t frame_pitch, const uint8_t* level, const uint8_t* mask, int64_t out_row_pitch,
-                         int64_t out_frame_pitch, const sba_background_suppress_opts& opts, uint8_t* out);
-int sba_convert_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_yuv_matrix& matrix,
-                     int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& opts, uint8_t* out);
-int sba_resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                    int64_t row_pitch, int64_t frame_pitch, int32_t fx, int32_t fy, int64_t out_row_pitch, int64_t out_frame_pitch,
-                    const sba_resize_opts& opts, uint8_t* out);
-int sba_to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
-                    int64_t frame_pitch, const sba_yuv_planes& out, const sba_rgb_matrix& matrix, const sba_to_yuv_opts& opts);
-int sba_undistort_yuv_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,
-                           const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
-                           const sba_undistort_yuv_opts& opts, uint8_t* flags_out, int32_t* map_out);
-int sba_hist_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
-                  int64_t frame_pitch, const sba_hist_opts& opts, uint32_t* hist, uint64_t* total);
-int sba_warp_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
-                  int64_t frame_pitch, const sba_lens& lens, const double* m, int32_t out_height, int32_t out_width, int64_t out_row_pitch,
-                  int64_t out_frame_pitch, const sba_undistort_opts& opts, uint8_t* out, uint8_t* flags_out, int32_t* map_out);
-int sba_corners_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                     int64_t row_pitch, int64_t frame_pitch, const int64_t* corner_start, const double* corners,
-                     const sba_corner_opts& opts, const double* weights, double* refined, int32_t* status, int32_t* iterations,
-                     double* tensor);
-int sba_adaptive_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                      int64_t row_pitch, int64_t frame_pitch, const sba_adaptive_opts& opts, int64_t out_row_pitch, int64_t out_frame_pitch,
-                      int64_t out_window_pitch, uint8_t* out, uint8_t* mean_out);
 
 // ============================================================================================== C ABI
 struct sba_handle {
@@ -404,16 +373,21 @@ int sba_reproj_stats(sba_handle* h, const sba_reproj_opts* opts, double* cam_sta
   });
 }
 
-// What sba_detect_dots and sba_detect_blobs (`fn`, for the error text) check of their frames, in the order both report it:
-// frame_args_invalid, then the entry point's own options, then frame_layout_invalid.
+// ---------------------------------------------------------------------------------------------- frame entry points
+// What an entry point (`fn`, for the error text) checks of its batch, in the order every one reports it: frame_args_invalid,
+// then its own options and outputs, then frame_layout_invalid (the pitches, the size limit, the device).
+//
+// ADDING A FRAME FUNCTION touches: include/sba_hip.h (the prototype and its options); a feature header with the kernels and
+// the *_call, included by sba_detect.hip and listed in the Makefile beside it; that *_call's declaration in sba_frame_calls.hpp;
+// the entry point here (FrameBatch, the checks below, guarded(*_call)); _native.py (signature, EXPORTED_SYMBOLS, wrapper); a
+// table in tests/test_frame_arg_errors.py and a tests/test_gpu_*.py.
 static int detect_invalid(const char* fn, const char* what) { g_last_error = std::string(fn) + ": " + what; return SBA_ERR_INVALID; }
 
-static int frame_args_invalid(const char* fn, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                              int32_t channel, int32_t threshold) {
-  if (n_frames < 0 || height < 0 || width < 0) return detect_invalid(fn, "negative size");
-  if (n_frames > 0 && !frames) return detect_invalid(fn, "null frames");
-  if (channels != 1 && channels != 3 && channels != 4) return detect_invalid(fn, "channels must be 1, 3 or 4");
-  if (channel < 0 || channel >= channels) return detect_invalid(fn, "channel out of range");
+static int frame_args_invalid(const char* fn, const FrameBatch& B, int32_t channel, int32_t threshold) {
+  if (B.n_frames < 0 || B.height < 0 || B.width < 0) return detect_invalid(fn, "negative size");
+  if (B.n_frames > 0 && !B.frames) return detect_invalid(fn, "null frames");
+  if (B.channels != 1 && B.channels != 3 && B.channels != 4) return detect_invalid(fn, "channels must be 1, 3 or 4");
+  if (channel < 0 || channel >= B.channels) return detect_invalid(fn, "channel out of range");
   if (threshold < 0 || threshold > 255) return detect_invalid(fn, "threshold must be in 0..255");
   return SBA_OK;
 }
@@ -428,22 +402,43 @@ static int frame_limit_invalid(const char* fn, int device, int32_t height, int32
 }
 
 // the pitches, then frame_limit_invalid
-static int frame_layout_invalid(const char* fn, int device, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                                int64_t row_pitch, int64_t frame_pitch, const char* why_limit) {
-  if (row_pitch < (int64_t)width * channels) return detect_invalid(fn, "row_pitch is smaller than width * channels");
-  if ((__int128)height * row_pitch > frame_pitch) return detect_invalid(fn, "frame_pitch is smaller than height * row_pitch");
-  if ((__int128)n_frames * frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * frame_pitch overflows");
-  return frame_limit_invalid(fn, device, height, width, why_limit);
+static int frame_layout_invalid(const char* fn, const FrameBatch& B, const char* why_limit) {
+  if (B.row_pitch < (int64_t)B.width * B.channels) return detect_invalid(fn, "row_pitch is smaller than width * channels");
+  if ((__int128)B.height * B.row_pitch > B.frame_pitch) return detect_invalid(fn, "frame_pitch is smaller than height * row_pitch");
+  if ((__int128)B.n_frames * B.frame_pitch > INT64_MAX) return detect_invalid(fn, "n_frames * frame_pitch overflows");
+  return frame_limit_invalid(fn, B.device, B.height, B.width, why_limit);
 }
 
 // The pitches of an output of n_frames frames of `rows` rows of `row_bytes` bytes.  Each entry point words the first two
 // texts in its own terms: `row_text` in full, `rows_text` is what it calls the rows; `overflow_text` as well where it differs.
-static int out_pitch_invalid(const char* fn, int64_t n_frames, int64_t rows, int64_t row_bytes, int64_t out_row_pitch, int64_t out_frame_pitch,
-                             const char* row_text, const char* rows_text, const char* overflow_text = "n_frames * out_frame_pitch overflows") {
-  if (out_row_pitch < row_bytes) return detect_invalid(fn, row_text);
-  if ((__int128)rows * out_row_pitch > out_frame_pitch)
+static int out_pitch_invalid(const char* fn, int64_t n_frames, int64_t rows, int64_t row_bytes, const FrameOut& out, const char* row_text,
+                             const char* rows_text, const char* overflow_text = "n_frames * out_frame_pitch overflows") {
+  if (out.row_pitch < row_bytes) return detect_invalid(fn, row_text);
+  if ((__int128)rows * out.row_pitch > out.frame_pitch)
     return detect_invalid(fn, (std::string("out_frame_pitch is smaller than ") + rows_text + " * out_row_pitch").c_str());
-  if ((__int128)n_frames * out_frame_pitch > INT64_MAX) return detect_invalid(fn, overflow_text);
+  if ((__int128)n_frames * out.frame_pitch > INT64_MAX) return detect_invalid(fn, overflow_text);
+  return SBA_OK;
+}
+
+// The weights of a grey value from `channels` channels: all zero means OpenCV's for B, G, R, and they are filled in.
+// `one_channel_text` is what the entry point says to a batch that has one channel only.
+static int gray_weights_invalid(const char* fn, int32_t channels, int32_t (&gray_w)[3], const char* one_channel_text) {
+  if (channels == 1) return detect_invalid(fn, one_channel_text);
+  if (gray_w[0] == 0 && gray_w[1] == 0 && gray_w[2] == 0) { gray_w[0] = 3735; gray_w[1] = 19235; gray_w[2] = 9798; }
+  if (gray_w[0] < 0 || gray_w[1] < 0 || gray_w[2] < 0) return detect_invalid(fn, "a gray weight is negative");
+  if ((int64_t)gray_w[0] + gray_w[1] + gray_w[2] != 1 << 15) return detect_invalid(fn, "the gray weights must sum to 2^15");
+  return SBA_OK;
+}
+
+// What the three calls that resample through a lens share of their options, in the order they report it.  The border is one
+// value for interleaved frames and three for YUV planes: the caller says whether it is in range and what to say if not.
+// `nothing_asked`: there are frames, and neither an output nor a diagnostic to write.
+static int resample_invalid(const char* fn, int32_t out_height, int32_t out_width, int32_t interpolation, bool border_ok,
+                            const char* border_text, bool nothing_asked) {
+  if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
+  if (interpolation != 0 && interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
+  if (!border_ok) return detect_invalid(fn, border_text);
+  if (nothing_asked) return detect_invalid(fn, "null out and no diagnostic asked for");
   return SBA_OK;
 }
 
@@ -480,17 +475,15 @@ int sba_detect_dots(int device, const uint8_t* frames, int64_t n_frames, int32_t
   sba_dot_opts o{};
   o.channel = 1; o.threshold = 50;
   if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, o.threshold);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  int rc = frame_args_invalid(fn, B, o.channel, o.threshold);
   if (rc) return rc;
   if (o.min_area < 0 || o.max_area < 0 || o.max_extent < 0) return detect_invalid(fn, "negative area or extent limit");
   // up to 16384 x 16384 every sum fits 64 bits: the largest a frame could ask for, sum w x^2 <= 255 * 16384 * 16384^3 / 3 = 6.1e18
   // < 2^64 = 1.8e19 (the sums actually returned are far smaller: sba_detect.hpp)
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch,
-                            " (the bound under which every sum fits 64 bits)");
+  rc = frame_layout_invalid(fn, B, " (the bound under which every sum fits 64 bits)");
   if (rc || n_frames == 0) return rc;
-  return guarded(nullptr, [&] {
-    return sba_detect_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, sums, box, centroid, status);
-  });
+  return guarded(nullptr, [&] { return sba_detect::dot_call(B, o, sums, box, centroid, status); });
 }
 
 int sba_detect_blobs(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -500,17 +493,42 @@ int sba_detect_blobs(int device, const uint8_t* frames, int64_t n_frames, int32_
   sba_blob_opts o{};
   o.channel = 1; o.threshold = 70; o.dilate_radius = 1; o.close_radius = 4;
   if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, o.threshold);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  int rc = frame_args_invalid(fn, B, o.channel, o.threshold);
   if (rc) return rc;
   if (o.dilate_radius < 0 || o.dilate_radius > 8 || o.close_radius < 0 || o.close_radius > 8) return detect_invalid(fn, "a radius must be in 0..8");
   if (o.max_blobs < 0 || o.max_blobs > 64) return detect_invalid(fn, "max_blobs must be in 0..64");
   if (o.min_area < 0 || o.max_area < 0 || o.max_centre_dist < 0) return detect_invalid(fn, "negative area or distance limit");
   // up to 16384 x 16384 a pixel's index y W + x fits the 32-bit labels, every sum 64 bits
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  rc = frame_layout_invalid(fn, B, "");
   if (rc || n_frames == 0) return rc;
+  return guarded(nullptr, [&] { return sba_detect::blob_call(B, o, n_components, blobs, accepted, centroid, status, mask_out, labels_out); });
+}
+
+// sba_undistort_frames and sba_warp_frames: the same call but for the model behind the lens -- `model` is new_k, or (warp) the
+// nine values of the matrix, which takes new_k's place
+static int lens_frames(const char* fn, bool warp, const FrameBatch& B, const sba_lens* lens, const double* model, int32_t out_height,
+                       int32_t out_width, const FrameOut& out, const sba_undistort_opts* opts, uint8_t* flags_out, int32_t* map_out) {
+  sba_undistort_opts o{};
+  if (opts) o = *opts;
+  static const double unit_k[4] = {1.0, 1.0, 0.0, 0.0};
+  int rc = frame_args_invalid(fn, B, 0, 0);
+  if (!rc) rc = lens_invalid(fn, lens, warp ? unit_k : model);
+  if (rc) return rc;
+  if (warp) {
+    if (!model) return detect_invalid(fn, "null m");
+    for (int k = 0; k < 9; ++k) if (!std::isfinite(model[k])) return detect_invalid(fn, "a value of m is not finite");
+  }
+  rc = resample_invalid(fn, out_height, out_width, o.interpolation, o.border_value >= 0 && o.border_value <= 255,
+                        "border_value must be in 0..255", !out.out && B.n_frames > 0 && !flags_out && !map_out);
+  if (rc) return rc;
+  if (out.out) rc = out_pitch_invalid(fn, B.n_frames, out_height, (int64_t)out_width * B.channels, out,
+                                      "out_row_pitch is smaller than out_width * channels", "out_height");
+  if (!rc) rc = frame_layout_invalid(fn, B, "");
+  if (rc) return rc;
   return guarded(nullptr, [&] {
-    return sba_blobs_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, n_components, blobs, accepted,
-                          centroid, status, mask_out, labels_out);
+    return warp ? sba_detect::warp_call(B, *lens, model, out_height, out_width, out, o, flags_out, map_out)
+                : sba_detect::undistort_call(B, *lens, model, out_height, out_width, out, o, flags_out, map_out);
   });
 }
 
@@ -518,51 +536,16 @@ int sba_undistort_frames(int device, const uint8_t* frames, int64_t n_frames, in
                          int64_t row_pitch, int64_t frame_pitch, const sba_lens* lens, const double* new_k, int32_t out_height,
                          int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts* opts, uint8_t* out,
                          uint8_t* flags_out, int32_t* map_out) {
-  const char* fn = "sba_undistort_frames";
-  sba_undistort_opts o{};
-  if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
-  if (!rc) rc = lens_invalid(fn, lens, new_k);
-  if (rc) return rc;
-  if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
-  if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
-  if (o.border_value < 0 || o.border_value > 255) return detect_invalid(fn, "border_value must be in 0..255");
-  if (!out && n_frames > 0 && !flags_out && !map_out) return detect_invalid(fn, "null out and no diagnostic asked for");
-  if (out) rc = out_pitch_invalid(fn, n_frames, out_height, (int64_t)out_width * channels, out_row_pitch, out_frame_pitch,
-                                  "out_row_pitch is smaller than out_width * channels", "out_height");
-  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
-  if (rc) return rc;
-  return guarded(nullptr, [&] {
-    return sba_undistort_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, *lens, new_k, out_height, out_width,
-                              out_row_pitch, out_frame_pitch, o, out, flags_out, map_out);
-  });
+  return lens_frames("sba_undistort_frames", false, {device, frames, n_frames, height, width, channels, row_pitch, frame_pitch}, lens, new_k,
+                     out_height, out_width, {out, out_row_pitch, out_frame_pitch}, opts, flags_out, map_out);
 }
 
 int sba_warp_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
                     int64_t row_pitch, int64_t frame_pitch, const sba_lens* lens, const double* m, int32_t out_height, int32_t out_width,
                     int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts* opts, uint8_t* out, uint8_t* flags_out,
                     int32_t* map_out) {
-  const char* fn = "sba_warp_frames";
-  sba_undistort_opts o{};
-  if (opts) o = *opts;
-  static const double unit_k[4] = {1.0, 1.0, 0.0, 0.0};      // the call has no new_k: the matrix takes its place
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
-  if (!rc) rc = lens_invalid(fn, lens, unit_k);
-  if (rc) return rc;
-  if (!m) return detect_invalid(fn, "null m");
-  for (int k = 0; k < 9; ++k) if (!std::isfinite(m[k])) return detect_invalid(fn, "a value of m is not finite");
-  if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
-  if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
-  if (o.border_value < 0 || o.border_value > 255) return detect_invalid(fn, "border_value must be in 0..255");
-  if (!out && n_frames > 0 && !flags_out && !map_out) return detect_invalid(fn, "null out and no diagnostic asked for");
-  if (out) rc = out_pitch_invalid(fn, n_frames, out_height, (int64_t)out_width * channels, out_row_pitch, out_frame_pitch,
-                                  "out_row_pitch is smaller than out_width * channels", "out_height");
-  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
-  if (rc) return rc;
-  return guarded(nullptr, [&] {
-    return sba_warp_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, *lens, m, out_height, out_width,
-                         out_row_pitch, out_frame_pitch, o, out, flags_out, map_out);
-  });
+  return lens_frames("sba_warp_frames", true, {device, frames, n_frames, height, width, channels, row_pitch, frame_pitch}, lens, m, out_height,
+                     out_width, {out, out_row_pitch, out_frame_pitch}, opts, flags_out, map_out);
 }
 
 int sba_background_accumulate(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -572,19 +555,17 @@ int sba_background_accumulate(int device, const uint8_t* frames, int64_t n_frame
   sba_background_accumulate_opts o{};
   o.channel = 1; o.threshold = 50;
   if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, o.threshold);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  int rc = frame_args_invalid(fn, B, o.channel, o.threshold);
   if (rc) return rc;
   // 255 * 2^24 < 2^32: below it `sum` cannot overflow
   if ((o.accumulate && n_used ? *n_used : 0) + (uint64_t)n_frames > ((uint64_t)1 << 24)) {
     g_last_error = std::string(fn) + ": more than 2^24 frames in all (the bound under which the 32-bit sum cannot overflow)";
     return SBA_ERR_UNSUPPORTED;
   }
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  rc = frame_layout_invalid(fn, B, "");
   if (rc) return rc;
-  return guarded(nullptr, [&] {
-    return sba_bg_accumulate_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, use, sum, sumsq, hot, vmax,
-                                  n_used);
-  });
+  return guarded(nullptr, [&] { return sba_detect::bg_accumulate_call(B, o, use, sum, sumsq, hot, vmax, n_used); });
 }
 
 int sba_background_suppress(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -594,17 +575,16 @@ int sba_background_suppress(int device, const uint8_t* frames, int64_t n_frames,
   sba_background_suppress_opts o{};
   o.channel = 1;
   if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, 0);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  const FrameOut O{out, out_row_pitch, out_frame_pitch};
+  int rc = frame_args_invalid(fn, B, o.channel, 0);
   if (rc) return rc;
   if (o.mode != SBA_BG_GATE && o.mode != SBA_BG_SUBTRACT) return detect_invalid(fn, "mode must be 0 (gate) or 1 (subtract)");
   if (!out && n_frames > 0) return detect_invalid(fn, "null out");
-  rc = out_pitch_invalid(fn, n_frames, height, width, out_row_pitch, out_frame_pitch, "out_row_pitch is smaller than width", "height");
-  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  rc = out_pitch_invalid(fn, n_frames, height, width, O, "out_row_pitch is smaller than width", "height");
+  if (!rc) rc = frame_layout_invalid(fn, B, "");
   if (rc || n_frames == 0) return rc;
-  return guarded(nullptr, [&] {
-    return sba_bg_suppress_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, level, mask, out_row_pitch,
-                                out_frame_pitch, o, out);
-  });
+  return guarded(nullptr, [&] { return sba_detect::bg_suppress_call(B, level, mask, O, o); });
 }
 
 int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n_frames, int32_t height, int32_t width,
@@ -630,12 +610,13 @@ int sba_convert_frames(int device, const uint8_t* y, const uint8_t* u, const uin
   const int64_t px = o.out_format <= SBA_PIX_RGB ? 3 : o.out_format <= SBA_PIX_RGBA ? 4 : 1;
   const sba_yuv_planes src{const_cast<uint8_t*>(y), const_cast<uint8_t*>(u), const_cast<uint8_t*>(v), y_row_pitch, y_frame_pitch, c_row_pitch,
                            c_frame_pitch, c_step, 0};
+  const FrameOut O{out, out_row_pitch, out_frame_pitch};
   int rc = yuv_planes_invalid(fn, "", src, n_frames, height, width);
-  if (!rc) rc = out_pitch_invalid(fn, n_frames, height, width * px, out_row_pitch, out_frame_pitch,
-                                  "out_row_pitch is smaller than width * bytes of a pixel", "height", "n_frames * a frame pitch overflows");
+  if (!rc) rc = out_pitch_invalid(fn, n_frames, height, width * px, O, "out_row_pitch is smaller than width * bytes of a pixel", "height",
+                                  "n_frames * a frame pitch overflows");
   if (!rc) rc = frame_limit_invalid(fn, device, height, width, "");
   if (rc || n_frames == 0) return rc;
-  return guarded(nullptr, [&] { return sba_convert_call(device, src, n_frames, height, width, m, out_row_pitch, out_frame_pitch, o, out); });
+  return guarded(nullptr, [&] { return sba_detect::convert_call(device, src, n_frames, height, width, m, O, o); });
 }
 
 int sba_resize_frames(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -644,25 +625,19 @@ int sba_resize_frames(int device, const uint8_t* frames, int64_t n_frames, int32
   const char* fn = "sba_resize_frames";
   sba_resize_opts o{};
   if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  const FrameOut O{out, out_row_pitch, out_frame_pitch};
+  int rc = frame_args_invalid(fn, B, 0, 0);
   if (rc) return rc;
   if (fx < 1 || fx > 16 || fy < 1 || fy > 16) return detect_invalid(fn, "fx and fy must be in 1..16");
   if (n_frames > 0 && (fx > width || fy > height)) return detect_invalid(fn, "a factor is larger than the frame: the output would have no pixels");
-  if (o.gray) {
-    if (channels == 1) return detect_invalid(fn, "gray needs 3 or 4 channels");
-    if (o.gray_w[0] == 0 && o.gray_w[1] == 0 && o.gray_w[2] == 0) { o.gray_w[0] = 3735; o.gray_w[1] = 19235; o.gray_w[2] = 9798; }   // OpenCV's B, G, R
-    if (o.gray_w[0] < 0 || o.gray_w[1] < 0 || o.gray_w[2] < 0) return detect_invalid(fn, "a gray weight is negative");
-    if ((int64_t)o.gray_w[0] + o.gray_w[1] + o.gray_w[2] != 1 << 15) return detect_invalid(fn, "the gray weights must sum to 2^15");
-  }
+  if (o.gray && (rc = gray_weights_invalid(fn, channels, o.gray_w, "gray needs 3 or 4 channels"))) return rc;
   if (!out && n_frames > 0) return detect_invalid(fn, "null out");
-  rc = out_pitch_invalid(fn, n_frames, height / fy, (int64_t)(width / fx) * (o.gray ? 1 : channels), out_row_pitch, out_frame_pitch,
+  rc = out_pitch_invalid(fn, n_frames, height / fy, (int64_t)(width / fx) * (o.gray ? 1 : channels), O,
                          "out_row_pitch is smaller than (width / fx) times the bytes of an output pixel", "(height / fy)");
-  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (!rc) rc = frame_layout_invalid(fn, B, "");
   if (rc || n_frames == 0) return rc;
-  return guarded(nullptr, [&] {
-    return sba_resize_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, fx, fy, out_row_pitch, out_frame_pitch,
-                           o, out);
-  });
+  return guarded(nullptr, [&] { return sba_detect::resize_call(B, fx, fy, O, o); });
 }
 
 int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -673,7 +648,8 @@ int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32
   if (opts) o = *opts;
   sba_rgb_matrix m{16, 269484, 528482, 102760, -155188, -305135, 460324, 460324, -385875, -74448};   // OpenCV's cvtColor(COLOR_BGR2YUV_I420)
   if (matrix) m = *matrix;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, 0, 0);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  int rc = frame_args_invalid(fn, B, 0, 0);
   if (rc) return rc;
   if (o.in_format < SBA_PIX_BGR || o.in_format > SBA_PIX_RGBA) return detect_invalid(fn, "in_format must be BGR, RGB, BGRA or RGBA");
   if (channels != 1 && channels != (o.in_format <= SBA_PIX_RGB ? 3 : 4)) return detect_invalid(fn, "in_format does not have `channels` bytes per pixel");
@@ -687,9 +663,9 @@ int sba_frames_to_yuv(int device, const uint8_t* frames, int64_t n_frames, int32
   }
   const sba_yuv_planes dst{y, u, v, y_row_pitch, y_frame_pitch, c_row_pitch, c_frame_pitch, c_step, 0};
   rc = yuv_planes_invalid(fn, "", dst, n_frames, height, width);
-  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  if (!rc) rc = frame_layout_invalid(fn, B, "");
   if (rc || n_frames == 0) return rc;
-  return guarded(nullptr, [&] { return sba_to_yuv_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, dst, m, o); });
+  return guarded(nullptr, [&] { return sba_detect::to_yuv_call(B, dst, m, o); });
 }
 
 int sba_undistort_yuv(int device, const sba_yuv_planes* src, int64_t n_frames, int32_t height, int32_t width, const sba_lens* lens,
@@ -703,16 +679,15 @@ int sba_undistort_yuv(int device, const sba_yuv_planes* src, int64_t n_frames, i
   int rc = yuv_planes_invalid(fn, "src", *src, n_frames, height, width);
   if (!rc) rc = lens_invalid(fn, lens, new_k);
   if (rc) return rc;
-  if (out_height < 0 || out_height > 16384 || out_width < 0 || out_width > 16384) return detect_invalid(fn, "the output size must be in 0..16384");
-  if (o.interpolation != 0 && o.interpolation != 1) return detect_invalid(fn, "interpolation must be 0 (bilinear) or 1 (nearest)");
-  if (o.border_y < 0 || o.border_y > 255 || o.border_u < 0 || o.border_u > 255 || o.border_v < 0 || o.border_v > 255)
-    return detect_invalid(fn, "border_y, border_u and border_v must be in 0..255");
-  if (!out && n_frames > 0 && !flags_out && !map_out) return detect_invalid(fn, "null out and no diagnostic asked for");
+  auto in_range = [](int32_t b) { return b >= 0 && b <= 255; };
+  rc = resample_invalid(fn, out_height, out_width, o.interpolation, in_range(o.border_y) && in_range(o.border_u) && in_range(o.border_v),
+                        "border_y, border_u and border_v must be in 0..255", !out && n_frames > 0 && !flags_out && !map_out);
+  if (rc) return rc;
   if (out) rc = yuv_planes_invalid(fn, "out", *out, n_frames, out_height, out_width);
   if (!rc) rc = frame_limit_invalid(fn, device, height, width, "");
   if (rc) return rc;
   return guarded(nullptr, [&] {
-    return sba_undistort_yuv_call(device, *src, n_frames, height, width, *lens, new_k, out_height, out_width, out, o, flags_out, map_out);
+    return sba_detect::undistort_yuv_call(device, *src, n_frames, height, width, *lens, new_k, out_height, out_width, out, o, flags_out, map_out);
   });
 }
 
@@ -722,14 +697,12 @@ int sba_frame_histograms(int device, const uint8_t* frames, int64_t n_frames, in
   sba_hist_opts o{};
   o.channel = 1;
   if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel, 0);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  int rc = frame_args_invalid(fn, B, o.channel, 0);
   // up to 16384 x 16384 a frame's count fits 32 bits: at most 2^28 pixels fall into one bin
-  if (!rc) rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch,
-                                     " (the bound under which a count fits 32 bits)");
+  if (!rc) rc = frame_layout_invalid(fn, B, " (the bound under which a count fits 32 bits)");
   if (rc || n_frames == 0 || (!hist && !total)) return rc;
-  return guarded(nullptr, [&] {
-    return sba_hist_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, hist, total);
-  });
+  return guarded(nullptr, [&] { return sba_detect::hist_call(B, o, hist, total); });
 }
 
 int sba_refine_corners(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -740,14 +713,10 @@ int sba_refine_corners(int device, const uint8_t* frames, int64_t n_frames, int3
   sba_corner_opts o{};
   o.eps = 1e-5; o.channel = channels == 1 ? 0 : -1; o.win_x = o.win_y = 3; o.zero_x = o.zero_y = -1; o.max_iter = 200;   // the reference's call
   if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel == -1 ? 0 : o.channel, 0);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  int rc = frame_args_invalid(fn, B, o.channel == -1 ? 0 : o.channel, 0);
   if (rc) return rc;
-  if (o.channel == -1) {
-    if (channels == 1) return detect_invalid(fn, "channel -1 (gray) needs 3 or 4 channels");
-    if (o.gray_w[0] == 0 && o.gray_w[1] == 0 && o.gray_w[2] == 0) { o.gray_w[0] = 3735; o.gray_w[1] = 19235; o.gray_w[2] = 9798; }   // OpenCV's B, G, R
-    if (o.gray_w[0] < 0 || o.gray_w[1] < 0 || o.gray_w[2] < 0) return detect_invalid(fn, "a gray weight is negative");
-    if ((int64_t)o.gray_w[0] + o.gray_w[1] + o.gray_w[2] != 1 << 15) return detect_invalid(fn, "the gray weights must sum to 2^15");
-  }
+  if (o.channel == -1 && (rc = gray_weights_invalid(fn, channels, o.gray_w, "channel -1 (gray) needs 3 or 4 channels"))) return rc;
   if (o.win_x < 1 || o.win_x > 15 || o.win_y < 1 || o.win_y > 15) return detect_invalid(fn, "win_x and win_y must be in 1..15");
   if (o.max_iter < 1 || o.max_iter > 10000) return detect_invalid(fn, "max_iter must be in 1..10000");
   if (!(o.eps >= 0.0)) return detect_invalid(fn, "eps must be >= 0");
@@ -764,12 +733,9 @@ int sba_refine_corners(int device, const uint8_t* frames, int64_t n_frames, int3
       if (!std::isfinite(weights[i]) || weights[i] < 0.0) return detect_invalid(fn, "a weight is negative or not finite");
   if (n > 0 && (!corners || !refined || !status)) return detect_invalid(fn, "null corners, refined or status");
   if (n > 0 && (height == 0 || width == 0)) return detect_invalid(fn, "corners in frames without pixels");
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  rc = frame_layout_invalid(fn, B, "");
   if (rc || n == 0) return rc;
-  return guarded(nullptr, [&] {
-    return sba_corners_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, corner_start, corners, o, weights,
-                            refined, status, iterations, tensor);
-  });
+  return guarded(nullptr, [&] { return sba_detect::corners_call(B, corner_start, corners, o, weights, refined, status, iterations, tensor); });
 }
 
 int sba_adaptive_threshold(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
@@ -780,7 +746,9 @@ int sba_adaptive_threshold(int device, const uint8_t* frames, int64_t n_frames, 
   o.n_windows = 3; o.block[0] = 3; o.block[1] = 13; o.block[2] = 23; o.delta[0] = o.delta[1] = o.delta[2] = 7;   // detectMarkers' call
   o.invert = 1; o.channel = channels == 1 ? 0 : -1;
   if (opts) o = *opts;
-  int rc = frame_args_invalid(fn, frames, n_frames, height, width, channels, o.channel == -1 ? 0 : o.channel, 0);
+  const FrameBatch B{device, frames, n_frames, height, width, channels, row_pitch, frame_pitch};
+  const FrameOut O{out, out_row_pitch, out_frame_pitch};
+  int rc = frame_args_invalid(fn, B, o.channel == -1 ? 0 : o.channel, 0);
   if (rc) return rc;
   if (o.n_windows < 1 || o.n_windows > 4) return detect_invalid(fn, "n_windows must be in 1..4");
   for (int k = 0; k < o.n_windows; ++k) {
@@ -789,24 +757,16 @@ int sba_adaptive_threshold(int device, const uint8_t* frames, int64_t n_frames, 
   }
   if (o.invert != 0 && o.invert != 1) return detect_invalid(fn, "invert must be 0 (binary) or 1 (binary, inverted)");
   if (o.max_value < 0 || o.max_value > 255) return detect_invalid(fn, "max_value must be in 0..255");
-  if (o.channel == -1) {
-    if (channels == 1) return detect_invalid(fn, "channel -1 (gray) needs 3 or 4 channels");
-    if (o.gray_w[0] == 0 && o.gray_w[1] == 0 && o.gray_w[2] == 0) { o.gray_w[0] = 3735; o.gray_w[1] = 19235; o.gray_w[2] = 9798; }   // OpenCV's B, G, R
-    if (o.gray_w[0] < 0 || o.gray_w[1] < 0 || o.gray_w[2] < 0) return detect_invalid(fn, "a gray weight is negative");
-    if ((int64_t)o.gray_w[0] + o.gray_w[1] + o.gray_w[2] != 1 << 15) return detect_invalid(fn, "the gray weights must sum to 2^15");
-  }
-  rc = out_pitch_invalid(fn, n_frames, height, width, out_row_pitch, out_frame_pitch, "out_row_pitch is smaller than width", "height");
+  if (o.channel == -1 && (rc = gray_weights_invalid(fn, channels, o.gray_w, "channel -1 (gray) needs 3 or 4 channels"))) return rc;
+  rc = out_pitch_invalid(fn, n_frames, height, width, O, "out_row_pitch is smaller than width", "height");
   if (rc) return rc;
   if (o.n_windows > 1 && (__int128)n_frames * out_frame_pitch > out_window_pitch)
     return detect_invalid(fn, "out_window_pitch is smaller than n_frames * out_frame_pitch");
   if ((__int128)o.n_windows * out_window_pitch > INT64_MAX) return detect_invalid(fn, "n_windows * out_window_pitch overflows");
   if (!out && !mean_out && n_frames > 0) return detect_invalid(fn, "null out and null mean_out");
-  rc = frame_layout_invalid(fn, device, n_frames, height, width, channels, row_pitch, frame_pitch, "");
+  rc = frame_layout_invalid(fn, B, "");
   if (rc || n_frames == 0) return rc;
-  return guarded(nullptr, [&] {
-    return sba_adaptive_call(device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, o, out_row_pitch, out_frame_pitch,
-                             out_window_pitch, out, mean_out);
-  });
+  return guarded(nullptr, [&] { return sba_detect::adaptive_call(B, o, O, out_window_pitch, mean_out); });
 }
 
 int sba_time_kernel(sba_handle* h, const char* name, int32_t reps, double* mean_us_out) {

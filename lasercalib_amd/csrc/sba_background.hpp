@@ -282,12 +282,13 @@ inline void bg_accumulate_launch(BgAccParams P, int channels, bool all, hipStrea
 
 // Arguments are checked by the caller (sba_api.hip); n_frames > 0.  Accumulators in host memory pass through device copies,
 // up before the first chunk (when the call adds to them) and down after the last.
-inline int bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                              int64_t row_pitch, int64_t frame_pitch, const sba_background_accumulate_opts& o, const uint8_t* use,
-                              uint32_t* sum, uint64_t* sumsq, uint32_t* hot, uint8_t* vmax, uint64_t* n_used) {
+int bg_accumulate_call(const FrameBatch& B, const sba_background_accumulate_opts& o, const uint8_t* use, uint32_t* sum, uint64_t* sumsq,
+                       uint32_t* hot, uint8_t* vmax, uint64_t* n_used) {
+  const int64_t n_frames = B.n_frames;
+  const int32_t height = B.height, width = B.width, channels = B.channels;
   const int64_t px = (int64_t)height * width;
   const bool fresh = o.accumulate == 0, frames_dev = o.frames_on_device != 0, stats_dev = o.stats_on_device != 0;
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, frames_dev ? 0 : (int64_t)width * channels * height);
+  const int64_t chunk = chunk_of(CHUNK_FRAMES, o.chunk_frames, B, frames_dev);      // no frames written, yet chunk_frames holds for device frames too
 
   // the frames that take part, chunk by chunk, numbered from the chunk's first frame
   const int64_t n_chunks = n_frames > 0 ? (n_frames + chunk - 1) / chunk : 0;
@@ -306,7 +307,7 @@ inline int bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frame
   const uint64_t n_after = (fresh || !n_used ? 0 : *n_used) + (uint64_t)used;
   if (px == 0 || (used == 0 && !fresh)) { if (n_used) *n_used = n_after; return SBA_OK; }
 
-  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(B.device));
   DotStream s0;
   DevBuf<uint32_t> d_sum, d_hot, d_max32;
   DevBuf<unsigned long long> d_sq;
@@ -342,8 +343,7 @@ inline int bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frame
     return SBA_OK;
   }
 
-  static const int32_t whole[4] = {0, 0, 0, 0};
-  P.V = frame_view(frames, row_pitch, frame_pitch, height, width, o.channel, o.threshold, whole, whole);
+  P.V = frame_view(B, o.channel, o.threshold);
   P.row_groups = (int32_t)(((int64_t)width * channels + 15) / 16);
   P.atomic = (int64_t)height * P.row_groups < BG_SPLIT_GROUPS && chunk > BG_SPLIT_FRAMES;
   const bool all = sumsq || hot || vmax;
@@ -392,16 +392,16 @@ inline int bg_accumulate_call(int device, const uint8_t* frames, int64_t n_frame
 
 // Arguments are checked by the caller (sba_api.hip).  Level and mask in host memory are copied to the device once; frames and
 // output pass through the device as sba_frames.hpp has it (frames_in_chunks, FrameOutput).
-inline int bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                            int64_t row_pitch, int64_t frame_pitch, const uint8_t* level, const uint8_t* mask, int64_t out_row_pitch,
-                            int64_t out_frame_pitch, const sba_background_suppress_opts& o, uint8_t* out) {
+int bg_suppress_call(const FrameBatch& B, const uint8_t* level, const uint8_t* mask, const FrameOut& out,
+                     const sba_background_suppress_opts& o) {
+  const int64_t n_frames = B.n_frames;
+  const int32_t height = B.height, width = B.width, channels = B.channels;
   const int64_t px = (int64_t)height * width;
   if (n_frames == 0 || px == 0) return SBA_OK;
-  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(B.device));
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
-  static const int32_t whole[4] = {0, 0, 0, 0};
   BgSupParams P{};
-  P.V = frame_view(frames, row_pitch, frame_pitch, height, width, o.channel, 0, whole, whole);
+  P.V = frame_view(B, o.channel, 0);
   P.level = level; P.mask = mask; P.mode = o.mode;
   P.row_groups = (width + 15) / 16;
   DevBuf<uint8_t> d_level, d_mask;
@@ -409,9 +409,8 @@ inline int bg_suppress_call(int device, const uint8_t* frames, int64_t n_frames,
     if (level) { d_level.alloc((size_t)px); HIPCHK(hipMemcpy(d_level.p, level, (size_t)px, hipMemcpyHostToDevice)); P.level = d_level.p; }
     if (mask) { d_mask.alloc((size_t)px); HIPCHK(hipMemcpy(d_mask.p, mask, (size_t)px, hipMemcpyHostToDevice)); P.mask = d_mask.p; }
   }
-  // the packed output of a frame is never larger than the frame
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : (int64_t)width * channels * height);
-  FrameOutput O(out, out_row_pitch, out_frame_pitch, width, height, out_dev, chunk);
+  const int64_t chunk = chunk_of(CHUNK_FRAMES, o.chunk_frames, B, in_dev, px, out_dev);   // px: never more than a frame takes
+  FrameOutput O(out, width, height, out_dev, chunk);
 
   const int64_t blocks = ((int64_t)height * P.row_groups + BG_THREADS - 1) / BG_THREADS;
   frames_in_chunks(

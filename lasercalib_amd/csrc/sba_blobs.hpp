@@ -587,9 +587,10 @@ inline void blob_judge(const sba_blob_opts& o, int K, int32_t ncomp, uint64_t* r
 // Arguments are checked by the caller (sba_api.hip).  Frames are taken in chunks: of a chunk the scratch above (labels, value
 // bytes, the two bit planes: about 5.3 bytes per pixel) stays within BLOB_SCRATCH_BYTES, a single frame always being allowed,
 // so device memory does not grow with n_frames.  frames_in_chunks drives them; one set of scratch serves every chunk.
-inline int blob_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                     int64_t row_pitch, int64_t frame_pitch, const sba_blob_opts& o, int32_t* n_components, uint64_t* blobs,
-                     int32_t* accepted, double* centroid, int32_t* status, uint8_t* mask_out, int32_t* labels_out) {
+int blob_call(const FrameBatch& B, const sba_blob_opts& o, int32_t* n_components, uint64_t* blobs, int32_t* accepted, double* centroid,
+              int32_t* status, uint8_t* mask_out, int32_t* labels_out) {
+  const int64_t n_frames = B.n_frames;
+  const int32_t height = B.height, width = B.width, channels = B.channels;
   if (n_frames == 0) return SBA_OK;
   const int K = o.max_blobs > 0 ? o.max_blobs : BLOB_DEFAULT_BLOBS;
   std::vector<uint64_t> h_table((size_t)K * BLOB_NREC);
@@ -601,20 +602,20 @@ inline int blob_call(int device, const uint8_t* frames, int64_t n_frames, int32_
     }
     return SBA_OK;
   }
-  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(B.device));
   BlobParams P{};
-  static_cast<FrameView&>(P) = frame_view(frames, row_pitch, frame_pitch, height, width, o.channel, o.threshold, o.roi_rect, o.roi_circle);
+  static_cast<FrameView&>(P) = frame_view(B, o.channel, o.threshold, o.roi_rect, o.roi_circle);
   P.ww = (width + 63) / 64;
   P.dh = o.dilate_radius + o.close_radius; P.eh = o.close_radius;
   blob_halfwidths(o.dilate_radius, o.close_radius, P.hwd, P.hwe);
   P.max_blobs = K; P.want_labels = labels_out ? 1 : 0;
 
   const bool on_device = o.frames_on_device != 0;
-  const int64_t tight_frame = (int64_t)width * channels * height;
   const int64_t px = (int64_t)height * width, words = (int64_t)height * P.ww;
   const int64_t per_frame = px * 5 + words * 16 + (int64_t)height * 8 + (int64_t)K * BLOB_NREC * 8 + 4;
-  // chunk_frames is a cap here, not a request: the library's own choice, within the scratch budget, bounds it
-  int64_t chunk = std::min(frames_per_chunk(0, n_frames, on_device ? 0 : tight_frame), std::max<int64_t>(1, BLOB_SCRATCH_BYTES / per_frame));
+  // neither policy of chunk_of: chunk_frames is a cap here, not a request: the library's own choice, within the scratch budget,
+  // bounds it
+  int64_t chunk = std::min(frames_per_chunk(0, n_frames, on_device ? 0 : frame_bytes(B)), std::max<int64_t>(1, BLOB_SCRATCH_BYTES / per_frame));
   if (o.chunk_frames > 0) chunk = std::min<int64_t>(chunk, o.chunk_frames);
 
   DevBuf<uint8_t> d_vals;

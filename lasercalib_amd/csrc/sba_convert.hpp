@@ -215,11 +215,11 @@ inline void cv_launch(const CvParams& P, int fmt, int64_t nf, hipStream_t st) {
   HIPCHK(hipGetLastError());
 }
 
-// Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (frames_per_chunk
-// on the larger side when one of them is host memory, frames_in_chunks over the planes of a YuvSource, FrameOutput).  Which
-// chunk or buffer a frame passes through does not enter its arithmetic.
-inline int convert_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_yuv_matrix& M,
-                        int64_t out_row_pitch, int64_t out_frame_pitch, const sba_convert_opts& o, uint8_t* out) {
+// Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (chunk_of by
+// CHUNK_FRAMES, frames_in_chunks over the planes of a YuvSource, FrameOutput).  Which chunk or buffer a frame passes through
+// does not enter its arithmetic.
+int convert_call(int device, const sba_yuv_planes& src, int64_t n_frames, int32_t height, int32_t width, const sba_yuv_matrix& M,
+                 const FrameOut& out, const sba_convert_opts& o) {
   if (n_frames == 0 || height == 0 || width == 0) return SBA_OK;
   HIPCHK(hipSetDevice(device));
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
@@ -229,8 +229,8 @@ inline int convert_call(int device, const sba_yuv_planes& src, int64_t n_frames,
   P.y_offset = M.y_offset; P.cy = M.cy; P.cvr = M.cvr; P.cug = M.cug; P.cvg = M.cvg; P.cub = M.cub;
 
   const int64_t out_row = (int64_t)width * cv_channels(o.out_format);
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(S.tight, out_row * height));
-  FrameOutput O(out, out_row_pitch, out_frame_pitch, out_row, height, out_dev, chunk);
+  const int64_t chunk = chunk_of(CHUNK_FRAMES, o.chunk_frames, n_frames, S.tight, in_dev, out_row * height, out_dev);
+  FrameOutput O(out, out_row, height, out_dev, chunk);
   frames_in_chunks(
       S.planes, S.n_planes, n_frames, in_dev, chunk,
       [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {

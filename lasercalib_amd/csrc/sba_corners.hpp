@@ -188,13 +188,12 @@ inline std::vector<double> cn_window(int wx, int wy, int zx, int zy) {
 // the grey weights set.  Chunks of frames as hist_call; the launch of a chunk gets the corners of its frames, and the device
 // buffers hold the corners of the largest chunk: they do not grow with n_frames.  Which chunk a corner passes through does not
 // enter its arithmetic.
-inline int corners_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                        int64_t row_pitch, int64_t frame_pitch, const int64_t* corner_start, const double* corners,
-                        const sba_corner_opts& o, const double* weights, double* refined, int32_t* status, int32_t* iterations,
-                        double* tensor) {
-  HIPCHK(hipSetDevice(device));
+int corners_call(const FrameBatch& B, const int64_t* corner_start, const double* corners, const sba_corner_opts& o, const double* weights,
+                 double* refined, int32_t* status, int32_t* iterations, double* tensor) {
+  const int64_t n_frames = B.n_frames;
+  HIPCHK(hipSetDevice(B.device));
   const bool on_device = o.frames_on_device != 0;
-  const int64_t chunk = frames_per_chunk(on_device ? 0 : o.chunk_frames, n_frames, on_device ? 0 : (int64_t)width * channels * height);
+  const int64_t chunk = chunk_of(CHUNK_RECORDS, o.chunk_frames, B, on_device);
   int64_t most = 0;
   for (int64_t lo = 0; lo < n_frames; lo += chunk) most = std::max(most, corner_start[std::min(lo + chunk, n_frames)] - corner_start[lo]);
 
@@ -211,7 +210,7 @@ inline int corners_call(int device, const uint8_t* frames, int64_t n_frames, int
   std::vector<int32_t> h_frame((size_t)most);
 
   CornerParams P{};
-  P.height = height; P.width = width; P.channels = channels; P.channel = o.channel;
+  P.height = B.height; P.width = B.width; P.channels = B.channels; P.channel = o.channel;
   P.w0 = o.gray_w[0]; P.w1 = o.gray_w[1]; P.w2 = o.gray_w[2];
   P.wx = wx; P.wy = wy; P.max_iter = o.max_iter; P.log2_g = cn_log2_group(wy);
   P.magic_s = cn_magic(2 * wx + 3); P.magic_t = cn_magic(2 * wx + 4);
@@ -221,7 +220,7 @@ inline int corners_call(int device, const uint8_t* frames, int64_t n_frames, int
   const int per_wave = 64 >> P.log2_g;
   const size_t lds = cn_lds_bytes(wx, wy);
 
-  const FramePlane plane{frames, row_pitch, frame_pitch, (int64_t)width * channels, height};
+  const FramePlane plane = frame_plane(B);
   frames_in_chunks(
       &plane, 1, n_frames, on_device, chunk,
       [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {

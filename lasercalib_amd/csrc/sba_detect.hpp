@@ -203,27 +203,26 @@ inline void dot_launch(DotParams P, int channels, int64_t nf, int64_t total_fram
 // Arguments are checked by the caller (sba_api.hip).  Device frames go DOT_MAX_CHUNK frames per launch, host frames
 // chunk_frames (by default what fits DOT_STAGE_BYTES) per staging copy: frames_in_chunks.  Device memory besides its staging
 // buffers: one set of results of a chunk, whatever n_frames is.
-inline int dot_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                    int64_t row_pitch, int64_t frame_pitch, const sba_dot_opts& o, uint64_t* sums, int32_t* box, double* centroid,
-                    int32_t* status) {
+int dot_call(const FrameBatch& B, const sba_dot_opts& o, uint64_t* sums, int32_t* box, double* centroid, int32_t* status) {
+  const int64_t n_frames = B.n_frames;
   if (n_frames == 0) return SBA_OK;
-  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(B.device));
   DotParams P{};
-  static_cast<FrameView&>(P) = frame_view(frames, row_pitch, frame_pitch, height, width, o.channel, o.threshold, o.roi_rect, o.roi_circle);
+  static_cast<FrameView&>(P) = frame_view(B, o.channel, o.threshold, o.roi_rect, o.roi_circle);
   P.min_area = o.min_area; P.max_area = o.max_area; P.max_extent = o.max_extent;
 
   const bool on_device = o.frames_on_device != 0;
-  const int64_t chunk = frames_per_chunk(on_device ? 0 : o.chunk_frames, n_frames, on_device ? 0 : (int64_t)width * channels * height);
+  const int64_t chunk = chunk_of(CHUNK_RECORDS, o.chunk_frames, B, on_device);
 
   DevBuf<unsigned long long> d_sums;
   DevBuf<int> d_box, d_st;
   DevBuf<double> d_cen;
   d_sums.alloc((size_t)chunk * DOT_NSUM); d_box.alloc((size_t)chunk * 4); d_cen.alloc((size_t)chunk * 4); d_st.alloc((size_t)chunk);
   frames_in_chunks(
-      P, channels, n_frames, on_device, chunk,
+      P, B.channels, n_frames, on_device, chunk,
       [&](const FrameView& V, int64_t, int64_t m, hipStream_t st) {
         static_cast<FrameView&>(P) = V;
-        dot_launch(P, channels, m, n_frames, d_sums.p, d_box.p, d_cen.p, d_st.p, st);
+        dot_launch(P, B.channels, m, n_frames, d_sums.p, d_box.p, d_cen.p, d_st.p, st);
       },
       [&](int64_t lo, int64_t m, hipStream_t st) {
         if (sums) HIPCHK(hipMemcpyAsync(sums + lo * DOT_NSUM, d_sums.p, sizeof(uint64_t) * m * DOT_NSUM, hipMemcpyDeviceToHost, st));

@@ -6,11 +6,15 @@
 // device helpers that more than one kernel uses (wave_lds_sync, channel_words / channel_byte) and ALL host-side plumbing of
 // every frame function (the "host side" below): chunk size, pitched copies, the loop over chunks with its staging, the output,
 // and a set of YUV 4:2:0 planes as the source or the output of a call (chroma_mode, YuvSource, YuvOutput).
+// A frame call arrives here as ABI scalars -> FrameBatch -> checks (sba_api.hip) -> *_call (a feature header).  FrameBatch and
+// FrameOut (sba_frame_calls.hpp) are host-only; what a *_call derives from them is here: frame_view(B, ...), frame_plane(B),
+// frame_bytes(B), chunk_of(policy, ...), FrameOutput(FrameOut, ...).  Nothing of them reaches a kernel.
 // (The store of a finished LDS row at any alignment stays written out in k_undistort and k_resize: as a shared function it
 // compiled to other instructions in both.)
 #pragma once
 #include <optional>
 #include "sba_common.hpp"
+#include "sba_frame_calls.hpp"
 
 namespace sba_detect {
 using namespace sba_host;
@@ -30,9 +34,12 @@ struct FrameView {
   int64_t r2;                                // the circle's r^2; < 0 = no circle
 };
 
-// roi_rect = (x0, y0, x1, y1), all zero = the whole frame; roi_circle = (cx, cy, r), r <= 0 = no circle
+// roi_rect = (x0, y0, x1, y1), all zero or none = the whole frame; roi_circle = (cx, cy, r), r <= 0 or none = no circle
 inline FrameView frame_view(const uint8_t* frames, int64_t row_pitch, int64_t frame_pitch, int32_t height, int32_t width, int32_t channel,
-                            int32_t threshold, const int32_t* rr, const int32_t* rc) {
+                            int32_t threshold, const int32_t* rr = nullptr, const int32_t* rc = nullptr) {
+  static const int32_t whole[4] = {0, 0, 0, 0};
+  if (!rr) rr = whole;
+  if (!rc) rc = whole;
   FrameView V{};
   V.frames = frames; V.row_pitch = row_pitch; V.frame_pitch = frame_pitch;
   V.height = height; V.width = width; V.channel = channel; V.threshold = threshold;
@@ -42,6 +49,13 @@ inline FrameView frame_view(const uint8_t* frames, int64_t row_pitch, int64_t fr
   V.r2 = rc[2] > 0 ? (int64_t)rc[2] * rc[2] : -1;
   return V;
 }
+
+// What every call derives from its batch: the view its kernels read, the one plane frames_in_chunks stages, the packed bytes of
+// a frame
+inline FrameView frame_view(const FrameBatch& B, int32_t channel, int32_t threshold, const int32_t* rr = nullptr, const int32_t* rc = nullptr) {
+  return frame_view(B.frames, B.row_pitch, B.frame_pitch, B.height, B.width, channel, threshold, rr, rc);
+}
+inline int64_t frame_bytes(const FrameBatch& B) { return (int64_t)B.width * B.channels * B.height; }
 
 // about 2048 workgroups over the whole call where the frames allow it, 4 to 32 rows each (one to eight per wave)
 inline int frame_rows_per_band(int64_t rows, int64_t total_frames) {
@@ -155,9 +169,9 @@ __device__ __forceinline__ bool scan_row(const uint8_t* __restrict__ rp, int xa,
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// Everything between a caller's pointers and pitches and the kernels of a chunk: the size of a chunk (frames_per_chunk), the
-// one routine that moves pitched frames (copy_frames), the loop over chunks with its staging (frames_in_chunks), the output
-// of a call that writes frames (FrameOutput), and what the YUV 4:2:0 calls build from these: how two chroma planes are treated
+// Everything between a caller's pointers and pitches and the kernels of a chunk: the size of a chunk (frames_per_chunk, and
+// chunk_of, which names the two policies the calls have for it), the one routine that moves pitched frames (copy_frames), the
+// loop over chunks with its staging (frames_in_chunks), the output of a call that writes frames (FrameOutput), and what the YUV 4:2:0 calls build from these: how two chroma planes are treated
 // (chroma_mode), their planes as a staged source (YuvSource) and as an output (YuvOutput).
 struct DotStream {
   hipStream_t s = nullptr;
@@ -179,6 +193,24 @@ inline int64_t frames_per_chunk(int64_t requested, int64_t n_frames, int64_t sta
   if (requested > 0) chunk = requested;
   else if (staged_bytes > 0) chunk = std::max<int64_t>(1, DOT_STAGE_BYTES / staged_bytes);
   return std::max<int64_t>(1, std::min(std::min(chunk, DOT_MAX_CHUNK), n_frames));
+}
+
+// The chunk of a call.  The frame functions have two policies, and both are here:
+//   CHUNK_RECORDS  calls whose results are small records per frame (dots, histograms, corners): chunk_frames is the size of a
+//                  staging copy, so frames on the device ignore it and go DOT_MAX_CHUNK a launch;
+//   CHUNK_FRAMES   calls that write frames, and the background statistics: chunk_frames is honoured wherever the frames are; by
+//                  default a chunk is sized by the larger of the two sides (in_bytes, out_bytes: packed bytes of a frame; 0 = the
+//                  call has no such side) as soon as ONE of them is host memory, whichever it is.
+// sba_detect_blobs (chunk_frames caps the library's own choice) and sba_adaptive_threshold (each side counts only when it is host
+// memory) follow neither and say so where they compute theirs.
+enum ChunkPolicy { CHUNK_RECORDS, CHUNK_FRAMES };
+inline int64_t chunk_of(ChunkPolicy policy, int64_t requested, int64_t n_frames, int64_t in_bytes, bool in_dev, int64_t out_bytes = 0,
+                        bool out_dev = true) {
+  if (policy == CHUNK_RECORDS) return frames_per_chunk(in_dev ? 0 : requested, n_frames, in_dev ? 0 : in_bytes);
+  return frames_per_chunk(requested, n_frames, in_dev && out_dev ? 0 : std::max(in_bytes, out_bytes));
+}
+inline int64_t chunk_of(ChunkPolicy policy, int64_t requested, const FrameBatch& B, bool in_dev, int64_t out_bytes = 0, bool out_dev = true) {
+  return chunk_of(policy, requested, B.n_frames, frame_bytes(B), in_dev, out_bytes, out_dev);
 }
 
 // m frames of `rows` rows of `row_bytes` bytes from one pitched layout to another, in either direction, queued on st.  Four
@@ -205,6 +237,7 @@ struct FramePlane {
   const uint8_t* base;
   int64_t row_pitch, frame_pitch, row_bytes, rows;
 };
+inline FramePlane frame_plane(const FrameBatch& B) { return {B.frames, B.row_pitch, B.frame_pitch, (int64_t)B.width * B.channels, B.height}; }
 constexpr int FRAME_MAX_PLANES = 3;
 struct FrameNoDone { void operator()(int64_t, int64_t) const {} };
 
@@ -285,8 +318,8 @@ struct FrameOutput {
   int64_t row_pitch, frame_pitch, row_bytes, rows;
   bool on_device;
   DevBuf<uint8_t> d_packed;
-  FrameOutput(uint8_t* out_, int64_t row_pitch_, int64_t frame_pitch_, int64_t row_bytes_, int64_t rows_, bool on_device_, int64_t chunk)
-      : out(out_), row_pitch(row_pitch_), frame_pitch(frame_pitch_), row_bytes(row_bytes_), rows(rows_), on_device(on_device_) {
+  FrameOutput(const FrameOut& o, int64_t row_bytes_, int64_t rows_, bool on_device_, int64_t chunk)
+      : out(o.out), row_pitch(o.row_pitch), frame_pitch(o.frame_pitch), row_bytes(row_bytes_), rows(rows_), on_device(on_device_) {
     if (!on_device) d_packed.alloc((size_t)(chunk * row_bytes * rows));
   }
   // what the kernels of the chunk that starts at frame lo write: its first frame and the two pitches
@@ -358,9 +391,10 @@ struct YuvOutput {
   void alloc(int64_t chunk) {
     if (spread) { h_u.resize((size_t)(chunk * cw * ch)); h_v.resize((size_t)(chunk * cw * ch)); }
     uint8_t* lower = mode == CV_VU ? D.v : D.u;
-    Oy.emplace(D.y, D.y_row_pitch, D.y_frame_pitch, w, h, on_device, chunk);
-    Ou.emplace(spread ? h_u.data() : lower, spread ? cw : D.c_row_pitch, spread ? cw * ch : D.c_frame_pitch, c_row, ch, on_device, chunk);
-    Ov.emplace(spread ? h_v.data() : D.v, spread ? cw : D.c_row_pitch, spread ? cw * ch : D.c_frame_pitch, c_row, paired ? 0 : ch, on_device, chunk);
+    const int64_t c_row_pitch = spread ? cw : D.c_row_pitch, c_frame_pitch = spread ? cw * ch : D.c_frame_pitch;
+    Oy.emplace(FrameOut{D.y, D.y_row_pitch, D.y_frame_pitch}, w, h, on_device, chunk);
+    Ou.emplace(FrameOut{spread ? h_u.data() : lower, c_row_pitch, c_frame_pitch}, c_row, ch, on_device, chunk);
+    Ov.emplace(FrameOut{spread ? h_v.data() : D.v, c_row_pitch, c_frame_pitch}, c_row, paired ? 0 : ch, on_device, chunk);
   }
   // what the kernels of the chunk that starts at frame lo write; paired: u is the lower address and v = u, not used
   void target(int64_t lo, uint8_t*& y, uint8_t*& u, uint8_t*& v, int64_t& y_row, int64_t& y_frame, int64_t& c_row_pitch, int64_t& c_frame) const {

@@ -160,15 +160,16 @@ __global__ void __launch_bounds__(HIST_BINS) k_hist_total(const uint32_t* __rest
 // ------------------------------------------------------------------------------------------------ host side
 // Arguments are checked by the caller (sba_api.hip).  Chunks as dot_call: device frames DOT_MAX_CHUNK per launch, host frames
 // chunk_frames per staging copy.  Device memory besides the staging buffers: one chunk's histograms and the 256 counters.
-inline int hist_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                     int64_t row_pitch, int64_t frame_pitch, const sba_hist_opts& o, uint32_t* hist, uint64_t* total) {
+int hist_call(const FrameBatch& B, const sba_hist_opts& o, uint32_t* hist, uint64_t* total) {
+  const int64_t n_frames = B.n_frames;
+  const int32_t channels = B.channels;
   if (n_frames == 0 || (!hist && !total)) return SBA_OK;
-  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(B.device));
   HistParams P{};
-  static_cast<FrameView&>(P) = frame_view(frames, row_pitch, frame_pitch, height, width, o.channel, 0, o.roi_rect, o.roi_circle);
+  static_cast<FrameView&>(P) = frame_view(B, o.channel, 0, o.roi_rect, o.roi_circle);
 
   const bool on_device = o.frames_on_device != 0;
-  const int64_t chunk = frames_per_chunk(on_device ? 0 : o.chunk_frames, n_frames, on_device ? 0 : (int64_t)width * channels * height);
+  const int64_t chunk = chunk_of(CHUNK_RECORDS, o.chunk_frames, B, on_device);
 
   DevBuf<uint32_t> d_hist;
   DevBuf<unsigned long long> d_total;

@@ -176,24 +176,23 @@ inline void rs_launch(RsParams P, int channels, bool gray, int64_t nf, hipStream
 }
 
 // Arguments are checked by the caller (sba_api.hip): n_frames > 0, both output sizes > 0, the weights set.  Chunks, staging
-// and output are those of sba_frames.hpp (frames_per_chunk on the source side, never the smaller one, when one of the two
-// sides is host memory; frames_in_chunks; FrameOutput).  Which chunk, workgroup or buffer a frame passes through does not
-// enter its arithmetic.
-inline int resize_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                       int64_t row_pitch, int64_t frame_pitch, int32_t fx, int32_t fy, int64_t out_row_pitch, int64_t out_frame_pitch,
-                       const sba_resize_opts& o, uint8_t* out) {
-  HIPCHK(hipSetDevice(device));
+// and output are those of sba_frames.hpp (chunk_of by CHUNK_FRAMES: the source is never the smaller side; frames_in_chunks;
+// FrameOutput).  Which chunk, workgroup or buffer a frame passes through does not enter its arithmetic.
+int resize_call(const FrameBatch& B, int32_t fx, int32_t fy, const FrameOut& out, const sba_resize_opts& o) {
+  const int32_t channels = B.channels;
+  HIPCHK(hipSetDevice(B.device));
   const bool gray = o.gray != 0, in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
   RsParams P{};
-  P.out_h = height / fy; P.out_w = width / fx; P.fx = fx; P.fy = fy;
+  P.out_h = B.height / fy; P.out_w = B.width / fx; P.fx = fx; P.fy = fy;
   P.w0 = o.gray_w[0]; P.w1 = o.gray_w[1]; P.w2 = o.gray_w[2];
   P.half_up = fx == 2 && fy == 2;
   P.scale = 1.0f / (float)(fx * fy);
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : (int64_t)width * channels * height);
-  FrameOutput O(out, out_row_pitch, out_frame_pitch, (int64_t)P.out_w * (gray ? 1 : channels), P.out_h, out_dev, chunk);
-  const FramePlane plane{frames, row_pitch, frame_pitch, (int64_t)width * channels, height};
+  const int64_t out_row = (int64_t)P.out_w * (gray ? 1 : channels);
+  const int64_t chunk = chunk_of(CHUNK_FRAMES, o.chunk_frames, B, in_dev, out_row * P.out_h, out_dev);
+  FrameOutput O(out, out_row, P.out_h, out_dev, chunk);
+  const FramePlane plane = frame_plane(B);
   frames_in_chunks(
-      &plane, 1, n_frames, in_dev, chunk,
+      &plane, 1, B.n_frames, in_dev, chunk,
       [&](const FramePlane* c, int64_t lo, int64_t m, hipStream_t st) {
         P.src = c->base; P.row_pitch = c->row_pitch; P.frame_pitch = c->frame_pitch;
         O.target(lo, P.out, P.out_row_pitch, P.out_frame_pitch);

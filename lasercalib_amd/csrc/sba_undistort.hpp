@@ -253,31 +253,29 @@ inline void ud_geometry_out(const Params& M, int channels, uint8_t* flags_out, i
   HIPCHK(hipStreamSynchronize(s.s));
 }
 
-// Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (frames_per_chunk
-// on the larger of the two sides when one of them is host memory, frames_in_chunks, FrameOutput).  Which chunk, workgroup or
-// buffer a frame passes through does not enter its arithmetic: any chunk_frames gives the same bytes.
-// `M` holds the model of the call (lens and front end); source, output and options are filled in here.
+// Arguments are checked by the caller (sba_api.hip).  Chunks, staging and output are those of sba_frames.hpp (chunk_of by
+// CHUNK_FRAMES, frames_in_chunks, FrameOutput).  Which chunk, workgroup or buffer a frame passes through does not enter its
+// arithmetic: any chunk_frames gives the same bytes.
+// `M` holds the model of the call (lens and front end); source (B), output (out) and options are filled in here.
 template <class Params>
-inline int ud_call(Params& M, int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                   int64_t row_pitch, int64_t frame_pitch, int32_t out_height, int32_t out_width, int64_t out_row_pitch,
-                   int64_t out_frame_pitch, const sba_undistort_opts& o, uint8_t* out, uint8_t* flags_out, int32_t* map_out) {
+inline int ud_call(Params& M, const FrameBatch& B, int32_t out_height, int32_t out_width, const FrameOut& out, const sba_undistort_opts& o,
+                   uint8_t* flags_out, int32_t* map_out) {
+  const int32_t channels = B.channels;
   const int64_t out_px = (int64_t)out_height * out_width;
   if (out_px == 0) return SBA_OK;
-  HIPCHK(hipSetDevice(device));
-  static const int32_t whole[4] = {0, 0, 0, 0};
+  HIPCHK(hipSetDevice(B.device));
   UdParams& P = ud_base(M);
-  P.src = frame_view(frames, row_pitch, frame_pitch, height, width, 0, 0, whole, whole);
+  P.src = frame_view(B, 0, 0);
   P.out_height = out_height; P.out_width = out_width; P.nearest = o.interpolation == 1; P.border = o.border_value;
   ud_geometry_out(M, channels, flags_out, map_out);
-  if (n_frames == 0 || !out) return SBA_OK;
+  if (B.n_frames == 0 || !out.out) return SBA_OK;
 
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
   const int64_t out_row = (int64_t)out_width * channels;
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames,
-                                         in_dev && out_dev ? 0 : std::max((int64_t)width * channels * height, out_row * out_height));
-  FrameOutput O(out, out_row_pitch, out_frame_pitch, out_row, out_height, out_dev, chunk);
+  const int64_t chunk = chunk_of(CHUNK_FRAMES, o.chunk_frames, B, in_dev, out_row * out_height, out_dev);
+  FrameOutput O(out, out_row, out_height, out_dev, chunk);
   frames_in_chunks(
-      P.src, channels, n_frames, in_dev, chunk,
+      P.src, channels, B.n_frames, in_dev, chunk,
       [&](const FrameView& V, int64_t lo, int64_t m, hipStream_t st) {
         P.src = V;
         O.target(lo, P.out, P.out_row_pitch, P.out_frame_pitch);
@@ -287,14 +285,11 @@ inline int ud_call(Params& M, int device, const uint8_t* frames, int64_t n_frame
   return SBA_OK;
 }
 
-inline int undistort_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                          int64_t row_pitch, int64_t frame_pitch, const sba_lens& L, const double* new_k, int32_t out_height,
-                          int32_t out_width, int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& o, uint8_t* out,
-                          uint8_t* flags_out, int32_t* map_out) {
+int undistort_call(const FrameBatch& B, const sba_lens& L, const double* new_k, int32_t out_height, int32_t out_width, const FrameOut& out,
+                   const sba_undistort_opts& o, uint8_t* flags_out, int32_t* map_out) {
   UdParams P{};
   ud_set_lens(P, L, new_k);
-  return ud_call(P, device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, out_height, out_width, out_row_pitch,
-                 out_frame_pitch, o, out, flags_out, map_out);
+  return ud_call(P, B, out_height, out_width, out, o, flags_out, map_out);
 }
 
 }  // namespace sba_detect

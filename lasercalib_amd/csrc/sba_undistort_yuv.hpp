@@ -284,16 +284,15 @@ inline void uy_launch(const UyParams& P, int64_t nf, hipStream_t st) {
 }
 
 // Arguments are checked by the caller (sba_api.hip).  The source is staged as a YuvSource and the planes are written through a
-// YuvOutput (sba_frames.hpp), in chunks of frames_per_chunk on the larger side when one of the two is host memory.  Which
-// chunk, workgroup or buffer a frame passes through does not enter its arithmetic: any chunk_frames gives the same bytes.
-inline int undistort_yuv_call(int device, const sba_yuv_planes& S, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,
-                              const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
-                              const sba_undistort_yuv_opts& o, uint8_t* flags_out, int32_t* map_out) {
+// YuvOutput (sba_frames.hpp), in chunks of chunk_of by CHUNK_FRAMES.  Which chunk, workgroup or buffer a frame passes through
+// does not enter its arithmetic: any chunk_frames gives the same bytes.
+int undistort_yuv_call(int device, const sba_yuv_planes& S, int64_t n_frames, int32_t height, int32_t width, const sba_lens& lens,
+                       const double* new_k, int32_t out_height, int32_t out_width, const sba_yuv_planes* out,
+                       const sba_undistort_yuv_opts& o, uint8_t* flags_out, int32_t* map_out) {
   if ((int64_t)out_height * out_width == 0) return SBA_OK;
   HIPCHK(hipSetDevice(device));
-  static const int32_t whole[4] = {0, 0, 0, 0};
   UyParams P{};
-  P.L.src = frame_view(S.y, S.y_row_pitch, S.y_frame_pitch, height, width, 0, 0, whole, whole);
+  P.L.src = frame_view(S.y, S.y_row_pitch, S.y_frame_pitch, height, width, 0, 0);
   ud_set_lens(P.L, lens, new_k);
   P.L.out_height = out_height; P.L.out_width = out_width; P.L.nearest = o.interpolation == 1; P.L.border = o.border_y;
   P.border_u = o.border_u; P.border_v = o.border_v;
@@ -304,7 +303,7 @@ inline int undistort_yuv_call(int device, const sba_yuv_planes& S, int64_t n_fra
   const YuvSource Sp(S, height, width);                                   // a source without pixels: every sample is the border
   YuvOutput O(*out, out_height, out_width, out_dev);
   P.sc_step = S.c_step; P.sc_mode = Sp.mode; P.oc_mode = O.mode;
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(Sp.tight, O.tight));
+  const int64_t chunk = chunk_of(CHUNK_FRAMES, o.chunk_frames, n_frames, Sp.tight, in_dev, O.tight, out_dev);
   O.alloc(chunk);
   frames_in_chunks(
       Sp.planes, Sp.n_planes, n_frames, in_dev, chunk,

@@ -37,16 +37,13 @@ __device__ __forceinline__ void model_pixel(const WarpParams& Q, int x, int y, i
 }
 
 // Arguments are checked by the caller (sba_api.hip); everything behind the model is ud_call
-inline int warp_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels,
-                     int64_t row_pitch, int64_t frame_pitch, const sba_lens& L, const double* m, int32_t out_height, int32_t out_width,
-                     int64_t out_row_pitch, int64_t out_frame_pitch, const sba_undistort_opts& o, uint8_t* out, uint8_t* flags_out,
-                     int32_t* map_out) {
+int warp_call(const FrameBatch& B, const sba_lens& L, const double* m, int32_t out_height, int32_t out_width, const FrameOut& out,
+              const sba_undistort_opts& o, uint8_t* flags_out, int32_t* map_out) {
   WarpParams Q{};
   static const double unit_k[4] = {1.0, 1.0, 0.0, 0.0};
   ud_set_lens(Q.U, L, unit_k);
   for (int k = 0; k < 9; ++k) Q.m[k] = m[k];
-  return ud_call(Q, device, frames, n_frames, height, width, channels, row_pitch, frame_pitch, out_height, out_width, out_row_pitch,
-                 out_frame_pitch, o, out, flags_out, map_out);
+  return ud_call(Q, B, out_height, out_width, out, o, flags_out, map_out);
 }
 
 }  // namespace sba_detect

@@ -202,12 +202,13 @@ inline void ty_launch(const TyParams& P, int in, int chroma, int64_t nf, hipStre
 }
 
 // Arguments are checked by the caller (sba_api.hip).  Chunks and staging of the source are those of sba_frames.hpp
-// (frames_per_chunk on the larger side when one of them is host memory, frames_in_chunks); the planes are written through a
-// YuvOutput of that file.  Which chunk or buffer a frame passes through does not enter its arithmetic.
-inline int to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, int64_t row_pitch,
-                       int64_t frame_pitch, const sba_yuv_planes& out, const sba_rgb_matrix& M, const sba_to_yuv_opts& o) {
+// (chunk_of by CHUNK_FRAMES, frames_in_chunks); the planes are written through a YuvOutput of that file.  Which chunk or buffer
+// a frame passes through does not enter its arithmetic.
+int to_yuv_call(const FrameBatch& B, const sba_yuv_planes& out, const sba_rgb_matrix& M, const sba_to_yuv_opts& o) {
+  const int64_t n_frames = B.n_frames;
+  const int32_t height = B.height, width = B.width, channels = B.channels;
   if (n_frames == 0 || height == 0 || width == 0) return SBA_OK;
-  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(B.device));
   const bool in_dev = o.frames_on_device != 0, out_dev = o.out_on_device != 0;
   YuvOutput O(out, height, width, out_dev);
   TyParams P{};
@@ -215,10 +216,9 @@ inline int to_yuv_call(int device, const uint8_t* frames, int64_t n_frames, int3
   P.yc = (1 << 19) + (M.y_offset << 20);
   P.cry = M.cry; P.cgy = M.cgy; P.cby = M.cby; P.cru = M.cru; P.cgu = M.cgu; P.cbu = M.cbu; P.crv = M.crv; P.cgv = M.cgv; P.cbv = M.cbv;
 
-  const int64_t in_row = (int64_t)width * channels;
-  const int64_t chunk = frames_per_chunk(o.chunk_frames, n_frames, in_dev && out_dev ? 0 : std::max(in_row * height, O.tight));
+  const int64_t chunk = chunk_of(CHUNK_FRAMES, o.chunk_frames, B, in_dev, O.tight, out_dev);
   O.alloc(chunk);
-  const FramePlane plane{frames, row_pitch, frame_pitch, in_row, height};
+  const FramePlane plane = frame_plane(B);
   const int in = channels == 1 ? TY_GRAY : o.in_format;
   frames_in_chunks(
       &plane, 1, n_frames, in_dev, chunk,
